@@ -51,7 +51,15 @@ def parse_args():
                     help="diagnostics: run ONE rank's slab (the middle one) of the N-way time-slab split on this GPU, with the "
                          "code path of a real rank and its neighbour messages as local copies (tools/loopback_rccl.cpp); "
                          "T(full grid) / T(this) is the compute-only ceiling of the N-GPU strong-scaling curve")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed run computed (iterates, sigma, KKT history) as "
+                         "DIR/<name>.npy, float64; one process on one GPU only")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and (args.gpus > 1 or args.rank_share > 1):
+        ap.error("--dump-outputs needs --gpus 1 and no --rank-share (the iterates of a slab run are per rank)")
+    return args
 
 
 def build_problem(D, workload, ny, nx, nt):
@@ -149,6 +157,32 @@ def cpu_baseline(workload, ny, nx, nt, budget_s):
                    f"single-threaded in both, like the reference's); scaled by the node ratio {nodes_s}/{nodes_f} to "
                    f"{ny}x{nx}x{nt}; CPU: {_cpu_model()}"),
     }
+
+
+DUMP_SAMPLE = 1 << 20       # elements kept per field: five fields of at most 8 MiB each stay well inside 64 MB
+DUMP_KKT_ROWS = 4096        # last rows of the KKT history kept
+
+
+def dump_outputs(D, ctx, var, hist, sigma, out_dir):
+    """--dump-outputs: what the caller of solver_socp_inPALM & co. receives after the timed run -- var.phi, q, z, alpha,
+    beta (alpha and beta multiplied by sigma, as finish() leaves them), sigma, cScale / dScale and the KKT history -- as
+    float64 DIR/<name>.npy.  A field of more than DUMP_SAMPLE elements is written as a sample of its column-major
+    elements at sorted positions drawn without replacement from a generator seeded by the field's index, so the same
+    grid gives the same positions in every run and two builds compare value for value."""
+    os.makedirs(out_dir, exist_ok=True)
+    shapes = {"phi": var.phi.shape, "q": (var.nq,), "z": var.zshape, "alpha": (var.nq,), "beta": var.zshape}
+    fields = {"phi": D.capi.F_PHI, "q": D.capi.F_Q, "z": D.capi.F_Z, "alpha": D.capi.F_ALPHA, "beta": D.capi.F_BETA}
+    for seed, (name, field) in enumerate(fields.items()):
+        a = ctx.download(field, np.broadcast_to(0.0, shapes[name]))
+        if a.size > DUMP_SAMPLE:
+            pos = np.sort(np.random.default_rng(seed).choice(a.size, DUMP_SAMPLE, replace=False))
+            a = a.ravel(order="F")[pos]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+        del a
+    np.save(os.path.join(out_dir, "sigma.npy"), np.array([sigma], dtype=np.float64))
+    np.save(os.path.join(out_dir, "scale.npy"), np.array([var.cScale, var.dScale], dtype=np.float64))
+    np.save(os.path.join(out_dir, "kkt.npy"), np.ascontiguousarray(hist["kkt"][-DUMP_KKT_ROWS:], dtype=np.float64))
+    np.save(os.path.join(out_dir, "kkt_iter.npy"), np.asarray(hist["iter"][-DUMP_KKT_ROWS:], dtype=np.float64))
 
 
 def copy_rate_gbs(torch, device):
@@ -366,6 +400,8 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
     hist, sigma = ctx.finish(download=False)
+    if args.dump_outputs:
+        dump_outputs(D, ctx, var, hist, sigma, args.dump_outputs)
 
     def emit(times, fallback_note=None):
         """build and print the JSON line (rank 0) from the timed pass's figures and the phase timers `times`"""

@@ -12,9 +12,15 @@ exactly W + K iterations.  Inputs are resident in HBM before the timed region st
 N = 1: dot2d 1024 x 1024 x 128 (BASELINE.json configs[2]).  N > 1: the same grid split into N time
 slabs, one process per GPU (strong scaling); `--grid 2048 2048 256 --gpus 8` is BASELINE.json configs[3].
 N > 1 runs either under `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...` or plainly
-as `python bench.py --gpus N ...`, which starts the N ranks itself (self_launch).  Rank 0 prints ONE JSON line; besides the contract
-fields it carries `roofline` (cone-projection kernel, HIP-event timing on the launch stream) and
-`cpu_baseline` (the CPU oracle timed on this box's host cores on a bounded sample).
+as `python bench.py --gpus N ...`, which starts the N ranks itself (self_launch).  Rank 0 prints ONE JSON line.
+
+A plain run does what its headline figure needs: set-up, W warm-up and K timed iterations, `--dump-outputs`, the line.
+With one process the line also carries `roofline` and `kernel_ms` (cone-projection kernel and the other phases,
+HIP-event timing on the launch stream of the timed iterations themselves).  `--full` adds what takes work of its own:
+`cpu_baseline` (the CPU oracle timed on the host's cores on a bounded sample; `--no-cpu-baseline` leaves it out),
+`config.box_copy_gbs` (device copy rate before the warm-up), the untimed instrumented second pass that fills `roofline` /
+`kernel_ms` when several ranks or `--rank-share` time their pass without per-phase events, and the full-grid run of
+`--rank-share` (`rank_share.ceiling`).
 """
 import argparse
 import json
@@ -43,14 +49,18 @@ def parse_args():
     ap.add_argument("--workload", choices=["dot2d", "wdot2d", "dot1d"], default="dot2d")
     ap.add_argument("--method", choices=["inPALM", "ALG2", "PALM", "acc-ADMM"], default="inPALM",
                     help="loop variant (diagnostic; BASELINE.json's metric is quoted on inPALM)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: CPU baseline, device copy rate, the "
+                         "instrumented second pass of a multi-rank or --rank-share run, --rank-share's full-grid run")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
     ap.add_argument("--nslabs", type=int, default=1,
                     help="diagnostics: run the time-slab algorithm with this many slabs inside ONE process / GPU")
-    ap.add_argument("--cpu-seconds", type=float, default=30.0, help="budget of the CPU baseline sample")
+    ap.add_argument("--cpu-seconds", type=float, default=30.0, help="budget of the CPU baseline sample (--full)")
     ap.add_argument("--rank-share", type=int, default=0, metavar="N",
                     help="diagnostics: run ONE rank's slab (the middle one) of the N-way time-slab split on this GPU, with the "
                          "code path of a real rank and its neighbour messages as local copies (tools/loopback_rccl.cpp); "
-                         "T(full grid) / T(this) is the compute-only ceiling of the N-GPU strong-scaling curve")
+                         "with --full the same process first times the full grid: T(full grid) / T(this) is the "
+                         "compute-only ceiling of the N-GPU strong-scaling curve")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the timed run computed (iterates, sigma, KKT history) as "
                          "DIR/<name>.npy, float64; one process on one GPU only")
@@ -325,15 +335,20 @@ def main():
 
     # --rank-share and N > 1: a rank's iteration is ~1.7 ms and issues ~40 launches; the ~20 per-phase HIP events per iteration that feed
     # `kernel_ms` cost it 4-5 % (they cost the 11 ms full-grid iteration nothing measurable).  Its timed pass therefore runs
-    # WITHOUT them and a second, untimed pass of the same length WITH them fills `kernel_ms` / `roofline`
-    two_pass = (bool(share) or world > 1) and not os.environ.get("DOTSOCP_BENCH_NOPROF")
+    # WITHOUT them; with --full a second, untimed pass of the same length WITH them fills `kernel_ms` / `roofline`
+    rank_path = bool(share) or world > 1
+    noprof = bool(os.environ.get("DOTSOCP_BENCH_NOPROF"))
+    events_in_timed = not rank_path and not noprof
+    two_pass = rank_path and args.full and not noprof
+    no_timers = "kernel_ms / roofline are empty: " + ("DOTSOCP_BENCH_NOPROF is set" if noprof else
+                                                      "--full fills them from a second, untimed run of the same W + K iterations")
     opts = dict(tau=1.0 if args.method == "ALG2" else 1.9, sigma=1.0, tol=0.0, maxit=args.warmup + args.steps, scaling=True,
                 ifCheckStepByStep=False, time_limit=1e9)
     full_ms = None
     # the device arrays of a context are about 46 doubles per node (49 GB at 1024 x 1024 x 128)
-    full_fits = share and 46 * 8 * ny * nx * nt < 0.92 * torch.cuda.mem_get_info(device)[0]
+    full_fits = share and args.full and 46 * 8 * ny * nx * nt < 0.92 * torch.cuda.mem_get_info(device)[0]
     if share and not full_fits:
-        # configs[3] (2048 x 2048 x 256 = 392 GB): the grid exists only as its slabs; the share is timed alone
+        # without --full, or configs[3] (2048 x 2048 x 256 = 392 GB: the grid exists only as its slabs): the share is timed alone
         weight = None
         share_rank = share // 2
         rccl = (bytes(128), share_rank, share)
@@ -384,10 +399,10 @@ def main():
             dist.barrier()
             torch.cuda.synchronize()
 
-    box_copy_gbs = copy_rate_gbs(torch, device)
+    box_copy_gbs = copy_rate_gbs(torch, device) if args.full else None
     done = ctx.run(args.warmup)
     assert done == args.warmup
-    if not os.environ.get("DOTSOCP_BENCH_NOPROF") and not two_pass:
+    if events_in_timed:
         D.capi.check(D.capi.lib().dotsocp_set_profiling(ctx._ctx, 1))
     fence()
     t0 = time.perf_counter()
@@ -494,7 +509,7 @@ def main():
                        "box_copy_gbs": box_copy_gbs,
                        # the timed region runs with the library's per-phase HIP events switched on (they feed roofline and
                        # kernel_ms); DOTSOCP_BENCH_NOPROF=1 times it without them
-                       "per_phase_hip_events_in_timed_region": not bool(os.environ.get("DOTSOCP_BENCH_NOPROF")) and not two_pass,
+                       "per_phase_hip_events_in_timed_region": events_in_timed,
                        "parallelism": (f"rank share: slab {share // 2} of {share} time slabs on 1 GPU, neighbour messages as local "
                                        f"copies (timing only, not a valid solve)") if share else
                                       ("1 GPU" if world == 1 else f"{world} time slabs")},
@@ -511,6 +526,8 @@ def main():
         if two_pass and not share:
             out["config"]["timed_pass"] = ("without per-phase HIP events (they cost a rank's 1.7 ms iteration 4-5 %); kernel_ms / roofline "
                                            "come from a second, untimed run of the same W + K iterations with them")
+        elif rank_path and not share:
+            out["config"]["timed_pass"] = "without per-phase HIP events (they cost a rank's 1.7 ms iteration 4-5 %); " + no_timers
         if share:
             out["rank_share"] = {"n": share, "slab": share // 2, "time_nodes": int(ntl),
                                  "kernel_ms_sum": round(sum(v[0] * v[1] for v in times.values()) / max(args.steps, 1), 4),
@@ -518,9 +535,11 @@ def main():
                                  "ceiling": (full_ms / (dt / args.steps * 1e3)) if full_ms else None,
                                  "ceiling_note": ("T(full grid) / T(this rank's share), both timed in THIS run (same process, same box, same "
                                                   "W and K, no per-phase events): the compute-only ceiling of the N-GPU strong-scaling curve")
-                                 if full_ms else "the full grid does not fit one GPU: the share is timed alone",
-                                 "timed_pass": "without per-phase HIP events; kernel_ms / roofline come from a second run of the same W + K "
-                                               "iterations with them" if two_pass else "with per-phase HIP events",
+                                 if full_ms else "the full grid does not fit one GPU: the share is timed alone" if args.full else
+                                 "the share is timed alone: --full also times the full grid in this process",
+                                 "timed_pass": "without per-phase HIP events; " + (
+                                     "kernel_ms / roofline come from a second run of the same W + K iterations with them" if two_pass
+                                     else no_timers),
                                  "note": "kernel_ms_sum = per-iteration sum of the phase timers (HIP events on the launch streams; "
                                          "phases on the second stream overlap the main one); ms_per_step - overlap-free kernel time = "
                                          "launch / dependency chain + host"}
@@ -530,7 +549,7 @@ def main():
         if fallback_note:
             out["config"]["timed_pass"] = fallback_note
         if rank == 0:
-            if not args.no_cpu_baseline and world == 1 and args.method == "inPALM" and not share:
+            if args.full and not args.no_cpu_baseline and world == 1 and args.method == "inPALM" and not share:
                 out["cpu_baseline"] = cpu_baseline(args.workload, ny, nx, nt, args.cpu_seconds)
             print(json.dumps(out), flush=True)
     phase_keys = ("rhs", "poisson", "cone_fused_a", "cone_fused_b", "cone_proj", "qstep", "beta", "materialise", "kkt", "comm",

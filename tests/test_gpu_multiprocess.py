@@ -203,7 +203,7 @@ def test_bench_under_torchrun_rehearsal(world):
     ref = json.loads(one.stdout.strip().splitlines()[-1])
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
-           "--gpus", str(world)] + common
+           "--gpus", str(world), "--full"] + common
     out = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -217,7 +217,7 @@ def test_bench_under_torchrun_rehearsal(world):
 
 
 def test_bench_line_survives_a_second_pass_that_does_not_finish():
-    """bench.py with several ranks times a pass without per-phase events and fills kernel_ms / roofline from a second,
+    """bench.py --full with several ranks times a pass without per-phase events and fills kernel_ms / roofline from a second,
     untimed pass on a communicator of its own.  Should that pass ever hang on real hardware, a watchdog prints the line with
     the timed pass's value and empty phase timers and every rank leaves: here the limit is zero, so it always fires."""
     import json
@@ -230,7 +230,7 @@ def test_bench_line_survives_a_second_pass_that_does_not_finish():
                DOTSOCP_BENCH_PASS2_LIMIT="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "12", "--warmup", "3",
-           "--no-cpu-baseline", "--grid", "64", "48", "16"]
+           "--full", "--no-cpu-baseline", "--grid", "64", "48", "16"]
     out = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -261,7 +261,7 @@ def test_bench_self_launch_rehearsal(world):
 
 
 def test_bench_rank_share_line():
-    """`bench.py --rank-share N` (one rank's slab of the N-way split through the code path of a real rank, its messages as
+    """`bench.py --rank-share N --full` (one rank's slab of the N-way split through the code path of a real rank, its messages as
     local copies in tools/libloopback_rccl.so) on a small grid: the line carries the full grid's time of the SAME process and
     the ratio of the two (round-3 verdict: same-run pairs only), and says that its timed pass ran without per-phase events."""
     import json
@@ -273,7 +273,7 @@ def test_bench_rank_share_line():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "DOTSOCP_RCCL_LIB"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--rank-share", "4", "--steps", "12", "--warmup", "3",
-           "--no-cpu-baseline", "--grid", "64", "48", "64"]
+           "--full", "--no-cpu-baseline", "--grid", "64", "48", "64"]
     out = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     rec = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
@@ -283,3 +283,42 @@ def test_bench_rank_share_line():
     assert rec["config"]["per_phase_hip_events_in_timed_region"] is False and "without per-phase" in rs["timed_pass"]
     assert rec["kernel_ms"]["poisson"] > 0 and rec["kernel_ms"]["comm"] > 0          # the second, instrumented pass
     assert rec["config"]["box_copy_gbs"] is None or rec["config"]["box_copy_gbs"] > 100
+
+
+def test_bench_plain_rank_lines_leave_the_second_runs_to_full():
+    """Without --full, several ranks and `--rank-share N` time their pass exactly as with it (no per-phase events) but run
+    nothing more: no instrumented second pass (kernel_ms empty, the line says how to get it) and no full-grid run."""
+    import json
+    import socket
+    _build_fake()
+    lb = os.path.join(ROOT, "tools", "libloopback_rccl.so")
+    if not os.path.exists(lb):
+        subprocess.check_call(["/opt/rocm/bin/hipcc", "-shared", "-fPIC", "-O2", "--offload-arch=gfx950", "-o", lb,
+                               os.path.join(ROOT, "tools", "loopback_rccl.cpp")])
+    with socket.socket() as s:
+        s.bind(("127.0.0.1", 0))
+        port = s.getsockname()[1]
+    env = dict(os.environ, DOTSOCP_RCCL_LIB=FAKE_SO, DOTSOCP_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
+    env.pop("DOTSOCP_BENCH_NOPROF", None)
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
+           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "12", "--warmup", "3",
+           "--grid", "64", "48", "16"]
+    out = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    rec = json.loads(lines[0])
+    assert rec["n_gpus"] == 2 and np.isfinite(rec["value"]) and rec["value"] > 0 and "cpu_baseline" not in rec
+    assert rec["config"]["per_phase_hip_events_in_timed_region"] is False and "--full" in rec["config"]["timed_pass"]
+    assert not any(rec["kernel_ms"].values())
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "DOTSOCP_RCCL_LIB", "DOTSOCP_BENCH_BACKEND"):
+        env.pop(k, None)
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--rank-share", "4", "--steps", "12", "--warmup", "3",
+           "--grid", "64", "48", "64"]
+    out = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-3000:]
+    rec = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
+    rs = rec["rank_share"]
+    assert rs["n"] == 4 and rs["time_nodes"] == 16 and rs["full_grid_ms_per_step"] is None and rs["ceiling"] is None
+    assert "--full" in rs["ceiling_note"] and "--full" in rs["timed_pass"] and not any(rec["kernel_ms"].values())
+    assert rec["config"]["per_phase_hip_events_in_timed_region"] is False and rec["config"]["box_copy_gbs"] is None

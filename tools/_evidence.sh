@@ -2,7 +2,7 @@
 cd $GRAFT_REPO_ROOT
 O=$GRAFT_REPO_ROOT/gpurun_out/ev
 mkdir -p $O
-B="timeout -k 10 400 python bench.py"
+B="timeout -k 10 400 python bench.py --full"
 $B > $O/r02_bench_default.json 2> $O/err.txt; echo default done
 $B --steps 20 --warmup 5 --no-cpu-baseline > $O/r02_bench_driver_window.json 2>> $O/err.txt
 $B --no-cpu-baseline --grid 256 256 64 > $O/r02_bench_256x256x64.json 2>> $O/err.txt

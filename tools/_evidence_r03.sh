@@ -3,7 +3,7 @@
 cd $GRAFT_REPO_ROOT
 O=$GRAFT_REPO_ROOT/gpurun_out/ev5
 mkdir -p $O
-B="timeout -k 10 400 python bench.py"
+B="timeout -k 10 400 python bench.py --full"
 $B > $O/r03_bench_default.json 2> $O/err.txt; echo default done
 $B --steps 20 --warmup 5 --no-cpu-baseline > $O/r03_bench_driver_window.json 2>> $O/err.txt
 for g in "256 256 64" "512 512 128" "1025 1025 129" "513 513 129" "257 257 65" "129 129 33" "2048 2048 32"; do

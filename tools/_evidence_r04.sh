@@ -3,7 +3,7 @@
 cd $GRAFT_REPO_ROOT
 O=$GRAFT_REPO_ROOT/gpurun_out/ev4
 mkdir -p $O
-B="timeout -k 10 400 python bench.py"
+B="timeout -k 10 400 python bench.py --full"
 $B > $O/r04_bench_default.json 2> $O/err.txt; echo default done
 $B --steps 20 --warmup 5 --no-cpu-baseline > $O/r04_bench_driver_window.json 2>> $O/err.txt
 for n in 8 4 2; do $B --no-cpu-baseline --rank-share $n > $O/r04_rank_share_n$n.json 2>> $O/err.txt; done

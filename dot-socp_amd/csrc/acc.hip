@@ -110,10 +110,7 @@ __global__ void __launch_bounds__(64 * XB) k_acc_cone(Grid g, LoopCoef c, AccArg
                             rs += r * r;
                         }
                         auto xj = [&](int j) { return v[j] - k.sigma * bp[j]; };
-                        double nn = xj(1) * xj(1);
-#pragma unroll
-                        for (int j = 2; j < 10; ++j) nn += xj(j) * xj(j);
-                        const double n = sqrt(nn), x0 = xj(0);
+                        const double n = sqrt(soc_norm2(xj, 10)), x0 = xj(0);
                         double cf = (x0 / n + 1.0) * 0.5;
                         cf = (cf > 1.0) ? 1.0 : cf;
                         cf = (cf < 0.0) ? 0.0 : cf;

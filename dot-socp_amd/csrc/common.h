@@ -14,6 +14,10 @@ namespace dotsocp {
 
 void set_error(const char *fmt, ...);
 
+// Edge factor of B F q (mexBFd / mexBFdConj): the scale times the 15-digit literal the reference binaries multiply by,
+// formed first and then applied to an edge value or an edge sum.  (s / sqrt(2.0) differs from it in the last bits.)
+__host__ __device__ inline double edge_factor(double s) { return s * 0.707106781186548; }
+
 #define DS_HIP(call)                                                                        \
     do {                                                                                    \
         hipError_t e__ = (call);                                                            \

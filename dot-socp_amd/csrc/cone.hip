@@ -35,12 +35,7 @@ __global__ void __launch_bounds__(256) k_proj_soc_any(double *__restrict__ out, 
                                                       i64 K) {
     for (i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x; i < M; i += (i64)gridDim.x * blockDim.x) {
         double x1 = in[i];
-        double nn = 0.0;
-        for (i64 j = 1; j < K; ++j) {
-            double t = in[j * M + i];
-            nn += t * t;
-        }
-        const double n = sqrt(nn);
+        const double n = sqrt(soc_norm2([&](i64 j) { return in[j * M + i]; }, K));
         double c = (x1 / n + 1.0) * 0.5;
         c = (c > 1.0) ? 1.0 : c;
         c = (c < 0.0) ? 0.0 : c;
@@ -93,7 +88,7 @@ __global__ void __launch_bounds__(TILE_Y *TILE_X) k_bfd(Grid g, double *__restri
 
 int launch_bfd(const Grid &g, double *z, const double *q, double s, double dF, hipStream_t st) {
     if (g.Nz <= 0) return 0;
-    DS_KLAUNCH(k_bfd, cell_grid(g, g.ncl), dim3(TILE_Y, TILE_X), 0, st, g, z, q, s, s / sqrt(2.0), dF);
+    DS_KLAUNCH(k_bfd, cell_grid(g, g.ncl), dim3(TILE_Y, TILE_X), 0, st, g, z, q, s, edge_factor(s), dF);
     DS_HIP(hipGetLastError());
     return 0;
 }
@@ -122,7 +117,7 @@ __global__ void __launch_bounds__(TILE_Y *TILE_X) k_bfd_conj(Grid g, double *__r
 
 int launch_bfd_conj(const Grid &g, double *q, const double *w, double s, hipStream_t st, const double *tail_bx,
                     const double *tail_by) {
-    const double sf = s / sqrt(2.0);
+    const double sf = edge_factor(s);
     if (!g.first && (!tail_bx || !tail_by)) {
         set_error("bfd_conj on a time slab needs the left neighbour's tails");
         return DOTSOCP_EINVAL;

@@ -61,15 +61,31 @@ __device__ __forceinline__ void st_stream(double *p, double v) {
 }
 bool stream_nt_enabled();          // fused.hip: DOTSOCP_NT=0 switches the non-temporal flavours off
 
+// ||x_2..K||^2 of one row, x(j) = entry j (0-based, j = 1..K-1), summed in the order of the reference's mexProjSoc
+// binary (Eigen's packet reduction): x(1)^2 first, then (x(j)^2 + x(j+1)^2) + (x(j+2)^2 + x(j+3)^2) for j = 2, 6, ...
+// while j - 1 < (K - 2) & ~3, then the remaining squares one at a time.  As many adds as left to right, another tree.
+// Every SOC projection of the library forms its norm here.
+template <class X, class I>
+__device__ __forceinline__ double soc_norm2(const X &x, I K) {
+    const I lim = (K - 2) & ~(I)3;
+    double p = x(1) * x(1);
+    I j = 2;
+#pragma unroll
+    for (; j - 1 < lim; j += 4) {
+        const double a = x(j), b = x(j + 1), c = x(j + 2), d = x(j + 3);
+        p += (a * a + b * b) + (c * c + d * d);
+    }
+#pragma unroll
+    for (; j < K; ++j) p += x(j) * x(j);
+    return p;
+}
+
 // Row projection onto {x1 >= ||x_2..K||}; literal restatement of mexProjSoc's arithmetic
-// (SURVEY.md 8a a1): n = ||x_2..K||, c = clamp((x1/n + 1)/2, 0, 1) with NaN passing through,
+// (SURVEY.md 8a a1): n = ||x_2..K|| (soc_norm2), c = clamp((x1/n + 1)/2, 0, 1) with NaN passing through,
 // x_j <- c x_j, x_1 <- (c >= 1) ? x_1 : c n.
 template <int K>
 __device__ __forceinline__ void proj_row(double (&v)[K]) {
-    double nn = v[1] * v[1];
-#pragma unroll
-    for (int j = 2; j < K; ++j) nn += v[j] * v[j];
-    const double n = sqrt(nn);
+    const double n = sqrt(soc_norm2([&](int j) { return v[j]; }, K));
     double c = (v[0] / n + 1.0) * 0.5;
     c = (c > 1.0) ? 1.0 : c;
     c = (c < 0.0) ? 0.0 : c;

@@ -8,7 +8,7 @@ namespace dotsocp {
 // Scalars of one inPALM iteration (solver_socp_inPALM.m:53-59,96-97,194-215).
 struct LoopCoef {
     double s;      // scaleBF = E / D
-    double sf;     // s / sqrt(2)
+    double sf;     // edge_factor(s)
     double dF;     // scaleD = E / dScale
     double at, ax, ay;   // D/ht, D/hx, D/hy  (entries of D * grad, initialize.m:67-87)
     double tau;

@@ -294,10 +294,7 @@ __global__ void __launch_bounds__(TILE_Y *TILE_X) k_kkt_cells(Grid g, LoopCoef c
                     // ||z - Pi_Q(z - sigma beta')||^2 (:240-241) with proj_row's arithmetic, the projected row never
                     // stored: x = z - sigma beta' is cheap to form twice, ten registers are not
                     auto xj = [&](int j) { return zo[j] - k.sigma * b[j]; };
-                    double nn = xj(1) * xj(1);
-#pragma unroll
-                    for (int j = 2; j < 10; ++j) nn += xj(j) * xj(j);
-                    const double n = sqrt(nn), x0 = xj(0);
+                    const double n = sqrt(soc_norm2(xj, 10)), x0 = xj(0);
                     double cf = (x0 / n + 1.0) * 0.5;
                     cf = (cf > 1.0) ? 1.0 : cf;
                     cf = (cf < 0.0) ? 0.0 : cf;

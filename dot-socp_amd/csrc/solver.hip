@@ -1154,7 +1154,7 @@ double Solver::elapsed() const {
 // --------------------------------------------------------------------------------------
 void Solver::update_coef() {
     lc.s = E / D;                       // scaleBF (:58)
-    lc.sf = lc.s / sqrt(2.0);
+    lc.sf = edge_factor(lc.s);
     lc.dF = E / dScale;                 // scaleD (:59,183)
     const double ht = 1.0 / (double)(nt - 1);
     lc.at = D * (1.0 / ht);             // D .* grad, entries 1/ht (initialize.m:68; solver_dotsocp2d.m:338)

@@ -4,8 +4,7 @@
  * CPU restatement (plain C, single-threaded like the originals) of the five MEX
  * operators on the inPALM hot path of chlhnu/DOT-SOCP.  The reference ships these
  * only as prebuilt binaries (socp/{dot1d,dot2d,wdot2d}/utils/mex*.mexa64 -- no C++
- * source in the tree); prebuilt reference binaries are never loaded or executed by
- * this repository, so the semantics restated here are the ones documented in
+ * source in the tree); the semantics restated here are the ones documented in
  * SURVEY.md section 8a (decoded from the disassembly) together with the reference's
  * own MATLAB call sites and the closed-form operators that must be consistent with
  * them:
@@ -13,10 +12,12 @@
  *   - diag(I + s^2 F*B*BF) must equal socp/dot2d/utils/oper_q.m:13-26 (dot1d/utils/oper_q.m:8-15)
  *   - cone geometry must reproduce socp/dot2d/utils/compute_kkt_dot_complement.m:3
  *
- * PARITY UNPINNED: the reference holds no tests, fixtures or golden vectors for this
- * path and neither MATLAB nor the prebuilt MEX binaries can be
- * run here, so this oracle is pinned only by algebraic invariants (adjointness,
- * idempotence, diagonal identity) -- see tests/test_oracle_invariants.py.
+ * PINNED TO THE BINARIES: the rounding follows them too -- the SOC row norm is summed in
+ * the binary's (Eigen's) order and the edge factor is the binary's 15-digit literal.
+ * oracle/ref_mex.py runs the prebuilt binaries through tests/fake_mx/fake_mx.c;
+ * tests/test_ref_operators.py checks this file against them bit for bit, both live
+ * (when oracle/_ref/ has been filled) and through the outputs recorded from them in
+ * tests/golden/ref_operators.npz (always).
  *
  * Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may use this file.
  *
@@ -29,6 +30,26 @@
 
 typedef long long i64;
 
+/* Squared norm of x_2..x_K of the row at x (entries M apart), summed in the order of the reference
+ * binary (Eigen's packet reduction, no FMA): x_2^2 first, then groups of four squares
+ * (x_j^2 + x_{j+1}^2) + (x_{j+2}^2 + x_{j+3}^2) for j = 3, 7, ... while j - 2 < (K - 2) & ~3, then
+ * the remaining squares one at a time.  Same adds as left to right, another tree. */
+static double soc_norm2(const double *x, i64 M, i64 K)
+{
+    const i64 lim = (K - 2) & ~(i64)3;
+    double p = x[M] * x[M];
+    i64 j = 2;                                       /* 0-based column */
+    for (; j - 1 < lim; j += 4) {
+        const double a = x[j * M], b = x[(j + 1) * M], c = x[(j + 2) * M], d = x[(j + 3) * M];
+        p += (a * a + b * b) + (c * c + d * d);
+    }
+    for (; j < K; ++j) p += x[j * M] * x[j * M];
+    return p;
+}
+
+/* mexBFd's edge factor: s times this 15-digit literal (formed first), not s / sqrt(2.0) */
+#define EDGE_FACTOR 0.707106781186548
+
 /* mexProjSoc(out, in): row-wise projection of an M x K column-major matrix onto
  * the second-order cone {x1 >= ||x_{2..K}||}  (SURVEY.md 8a row a1;
  * call sites solver_socp_inPALM.m:199,240).  Three passes like the original:
@@ -36,11 +57,7 @@ typedef long long i64;
 void oracle_proj_soc(double *out, const double *in, i64 M, i64 K, double *tmp)
 {
     double *nrm = tmp, *coef = tmp + M;
-    for (i64 i = 0; i < M; ++i) nrm[i] = 0.0;
-    for (i64 j = 1; j < K; ++j) {
-        const double *col = in + j * M;
-        for (i64 i = 0; i < M; ++i) nrm[i] += col[i] * col[i];
-    }
+    for (i64 i = 0; i < M; ++i) nrm[i] = (K > 1) ? soc_norm2(in + i, M, K) : 0.0;
     for (i64 i = 0; i < M; ++i) {
         double n = sqrt(nrm[i]);
         double c = (in[i] / n + 1.0) * 0.5;
@@ -67,7 +84,7 @@ void oracle_bfd(double *z, const double *q, i64 nt, i64 nx, i64 ny, double s, do
 {
     const i64 Nz = ny * nx * (nt - 1);
     const i64 offBx = Nz, offBy = Nz + ny * (nx - 1) * nt;
-    const double sf = s / sqrt(2.0);
+    const double sf = s * EDGE_FACTOR;
     for (i64 t = 0; t < nt - 1; ++t)
         for (i64 x = 0; x < nx; ++x)
             for (i64 y = 0; y < ny; ++y) {
@@ -92,7 +109,7 @@ void oracle_bfd_conj(double *q, const double *w, i64 nt, i64 nx, i64 ny, double 
 {
     const i64 Nz = ny * nx * (nt - 1);
     const i64 offBx = Nz, offBy = Nz + ny * (nx - 1) * nt;
-    const double sf = s / sqrt(2.0);
+    const double sf = s * EDGE_FACTOR;
     for (i64 i = 0; i < Nz; ++i) q[i] = s * (w[9 * Nz + i] - w[i]);
     for (i64 t = 0; t < nt; ++t)
         for (i64 xe = 0; xe < nx - 1; ++xe)
@@ -130,7 +147,7 @@ void oracle_bfd_conj(double *q, const double *w, i64 nt, i64 nx, i64 ny, double 
 void oracle_bfd1d(double *z, const double *q, i64 nt, i64 nx, double s, double dF)
 {
     const i64 Nz = nx * (nt - 1), offBx = Nz;
-    const double sf = s / sqrt(2.0);
+    const double sf = s * EDGE_FACTOR;
     for (i64 t = 0; t < nt - 1; ++t)
         for (i64 x = 0; x < nx; ++x) {
             i64 i = x + nx * t;
@@ -149,7 +166,7 @@ void oracle_bfd1d(double *z, const double *q, i64 nt, i64 nx, double s, double d
 void oracle_bfd_conj1d(double *q, const double *w, i64 nt, i64 nx, double s)
 {
     const i64 Nz = nx * (nt - 1), offBx = Nz;
-    const double sf = s / sqrt(2.0);
+    const double sf = s * EDGE_FACTOR;
     for (i64 i = 0; i < Nz; ++i) q[i] = s * (w[5 * Nz + i] - w[i]);
     for (i64 t = 0; t < nt; ++t)
         for (i64 xe = 0; xe < nx - 1; ++xe) {

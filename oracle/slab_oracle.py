@@ -158,7 +158,7 @@ class SlabInPALM:
     # ------------------------------------------------------------------------------------
     def _coef(self):
         self.s = self.E / self.D
-        self.sf = self.s / np.sqrt(2.0)
+        self.sf = self.s * 0.707106781186548     # the edge factor of mexBFd (oracle/mex_kernels.c EDGE_FACTOR)
         self.dF = self.E / self.dScale
         D = self.D
         self.at, self.ax, self.ay = D * (self.nt - 1), D * (self.nx - 1), D * (self.ny - 1)

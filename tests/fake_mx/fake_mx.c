@@ -1,8 +1,9 @@
 /* TEST INFRASTRUCTURE -- a stand-in for MATLAB's libmx / libmex, written from the public C Matrix API
  * documentation, just large enough to EXECUTE the MEX gateways of dot-socp_amd/mex/ on a box without MATLAB:
  * real double matrices, 1 x 1 structs, char row vectors, and mexErrMsgIdAndTxt as a non-local exit back to
- * the harness (fmx_call).  Nothing of MATLAB or of the reference is loaded.  tests/test_gpu_mex_gateways.py
- * builds it, builds the gateways against it and calls their mexFunction through ctypes. */
+ * the harness (fmx_call).  Nothing of MATLAB is loaded.  tests/test_gpu_mex_gateways.py builds it, builds the
+ * gateways against it and calls their mexFunction through ctypes; oracle/ref_mex.py builds it as libmx.so and
+ * libmex.so to run the reference's prebuilt operator binaries the same way. */
 #define _POSIX_C_SOURCE 200809L
 #include <setjmp.h>
 #include <stdarg.h>

@@ -168,6 +168,41 @@ def test_1d_gateways_and_their_error_identifiers(mx):
     assert err and err[0] == "mexBFd:invalidInput"
 
 
+def test_gateways_match_the_reference_fixture(mx):
+    """The five gateways as MATLAB calls them give what the reference's binaries gave (tests/golden/ref_operators.npz):
+    outputs bit for bit, and the 1-D binaries' error identifiers."""
+    from test_ref_operators import ERR_BINARIES, G, err_case_args, fixture_cases, same_bits
+    L, g = mx
+
+    class Gate:
+        """fixture_cases() drives the gateways through these: dimensions go in as the doubles MATLAB passes"""
+        @staticmethod
+        def mexProjSoc(out, x):
+            assert Call(L).run(g["mexProjSoc"], [out, x])[0] is None
+
+        @staticmethod
+        def mexBFd(z, q, nt, nx, ny, s, dF):
+            assert Call(L).run(g["mexBFd"], [z, q, nt + 0.75, nx + 0.5, ny + 0.25, s, dF])[0] is None
+
+        @staticmethod
+        def mexBFdConj(q, w, nt, nx, ny, s):
+            assert Call(L).run(g["mexBFdConj"], [q, w, nt + 0.75, nx + 0.5, ny + 0.25, s])[0] is None
+
+        @staticmethod
+        def mexBFd1d(z, q, nt, nx, *sdF):
+            assert Call(L).run(g["mexBFd1d"], [z, q, nt + 0.5, nx + 0.75, *sdF])[0] is None
+
+        @staticmethod
+        def mexBFdConj1d(q, w, nt, nx, *s):
+            assert Call(L).run(g["mexBFdConj1d"], [q, w, nt + 0.5, nx + 0.75, *s])[0] is None
+
+    bad = [label for label, got, exp in fixture_cases(Gate) if not same_bits(got, exp, nan_bits=False)]
+    assert not bad, bad
+    for (b, nrhs, nlhs, badpos), ident in zip(G["err1d_case"].tolist(), G["err1d_id"].tolist()):
+        err, _ = Call(L).run(g[ERR_BINARIES[b]], err_case_args(b, nrhs, badpos), nlhs=nlhs)
+        assert (err[0] if err else "") == ident, (ERR_BINARIES[b], nrhs, nlhs, badpos)
+
+
 @pytest.mark.parametrize("method,weighted", [("inPALM", False), ("accADMM", False), ("PALM", False), ("inPALM", True),
                                              ("accADMM", True)])
 def test_solver_gateway_matches_the_python_binding(mx, method, weighted):

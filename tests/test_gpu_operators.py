@@ -94,6 +94,15 @@ def test_bfd1d_and_conj1d(nt, nx):
     assert np.array_equal(qg, qr)
 
 
+def test_operators_match_the_reference_fixture():
+    """Each C-ABI operator equals the outputs recorded from the reference's binaries (tests/golden/ref_operators.npz)
+    bit for bit: apex and edge rows of the projection at K = 2, 3, 6, 10, 13, sentinels in the unwritten slots of
+    B F q + d and its adjoint, every argument count.  (The oracle reproduces the same fixture on the CPU.)"""
+    from test_ref_operators import fixture_cases, same_bits
+    bad = [label for label, got, exp in fixture_cases(D) if not same_bits(got, exp, nan_bits=False)]
+    assert not bad, bad
+
+
 @pytest.mark.parametrize("shape", [(8, 4, 2), (64, 32, 16), (256, 8, 4), (16, 256, 8), (4, 16, 128), (1024, 2, 2),
                                    (5, 6, 7), (33, 17, 9), (129, 3, 2), (16, 1, 8), (129, 1, 33),
                                    (129, 65, 33), (65, 129, 40), (257, 257, 5),

@@ -204,7 +204,7 @@ def test_free_running_solve_dot2d():
     assert timeML[0]["Iters"] == hist["iter"][-1]
 
 
-def test_free_running_solve_dot1d():
+def test_free_running_solve_dot1d_known_answer():
     rho0, rho1 = get_example_1d("gaussian", 129)
     ovar, omodel, o_hist, o_sigma = OD.solve_single_level(rho0, rho1, 33, dict(tol=1e-4))
     out, timeML, histML, hist = D.solver_dotsocp1d(rho0, rho1, 33, 1, dict(tol=1e-4), "inPALM")
@@ -213,9 +213,14 @@ def test_free_running_solve_dot1d():
     # recoverable (it is described as "rescale block disabled", but the restated loop stops at 339 that way and at 364
     # only with the block enabled), so the digits can only be held loosely: every KKT entry of the
     # 364-iteration run lies within 10 % of the recorded one, sigma (0.686 here) within 20 %.
+    # Entry 5 (sigma ||F*B*beta + D alpha||, zero in exact arithmetic) is rounding noise: its digits move with the
+    # operators' rounding, which follows the reference binaries (tests/test_ref_operators.py; 2.36e-16 here), so it is
+    # held to the recorded order of magnitude instead.
     survey_kkt = np.array([6.8e-5, 6.7e-5, 9.0e-5, 1.7e-5, 1.9e-16, 2.6e-5, 8.2e-5])
-    np.testing.assert_allclose(hist["kkt"][-1], survey_kkt, rtol=0.10)
-    np.testing.assert_allclose(o_hist["kkt"][-1], survey_kkt, rtol=0.10)
+    rest = [0, 1, 2, 3, 5, 6]
+    for kkt in (hist["kkt"][-1], o_hist["kkt"][-1]):
+        np.testing.assert_allclose(kkt[rest], survey_kkt[rest], rtol=0.10)
+        assert 0.0 <= kkt[4] < 2 * survey_kkt[4]
     assert abs(o_sigma - 0.592) <= 0.2 * 0.592
     assert D.check_massConservation(out["rho"], 1e-2)
     rho_o, Ex_o = OD.recover_RhoE_1d(ovar, omodel)

@@ -72,6 +72,7 @@ SYMBOLS = {
     "dotsocp_attach_rccl": (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.c_int]),
     "dotsocp_slab_range": (ctypes.c_int, [i64, ctypes.c_int, ctypes.c_int, ctypes.POINTER(i64), ctypes.POINTER(i64)]),
     "dotsocp_field_len": (i64, [ctypes.POINTER(Problem), ctypes.c_int]),
+    "dotsocp_dct_algorithm": (ctypes.c_int, [i64]),
     "dotsocp_release_cache": (i64, []),
     "dotsocp_upload": (ctypes.c_int, [vp, ctypes.c_int, vp]),
     "dotsocp_upload_layers": (ctypes.c_int, [vp, ctypes.c_int, vp, i64, i64]),
@@ -159,3 +160,12 @@ def rccl_unique_id():
     buf = (ctypes.c_ubyte * 128)()
     check(lib().dotsocp_rccl_unique_id(buf))
     return bytes(buf)
+
+
+DCT_ALGORITHMS = ("none", "fft", "pfa", "rader", "bluestein", "dense")
+
+
+def dct_algorithm(n):
+    """The transform the DCT passes use for an axis of length n: "fft" (power of two), "pfa" (prime-factor lengths),
+    "rader" (257), "bluestein" (other lengths up to 1024), "dense" (DCT-matrix product) or "none" (n <= 1).  No device needed."""
+    return DCT_ALGORITHMS[lib().dotsocp_dct_algorithm(int(n))]

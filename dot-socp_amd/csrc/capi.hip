@@ -2,6 +2,7 @@
 #include <cstring>
 #include <new>
 
+#include "cdft.h"
 #include "comm.h"
 #include "solver.h"
 
@@ -300,6 +301,8 @@ int dotsocp_attach_rccl(dotsocp_ctx *ctx, const unsigned char id[128], int rank,
         if (!ctx) { set_error("ctx is NULL"); return DOTSOCP_EINVAL; } \
         (void)hipGetLastError();   /* a stale error of an earlier, failed call must not be blamed on this one */ \
     } while (0)
+
+int dotsocp_dct_algorithm(dotsocp_i64 n) { return dct_choose_algorithm(n); }
 
 dotsocp_i64 dotsocp_field_len(const dotsocp_problem *p, int field) {
     if (!p || (p->dim != 1 && p->dim != 2) || p->nt < 2 || p->nx < 1 || (p->dim == 2 && p->ny < 1)) return -1;

@@ -6,9 +6,11 @@
 // in the real part, line b in the imaginary part), entirely in LDS: one HBM read and one HBM
 // write per element and axis.  A workgroup stages TL lines; for the strided axes (x, t) the TL
 // lines are consecutive in y so that global accesses stay coalesced.
-// Other lengths (the 2^k+1 grids of the multilevel driver): dense DCT matrix applied from an
-// LDS-staged tile (exact, O(n^2) per line; fallback path).
+// The 2^k+1 grids of the multilevel driver: prime-factor transform (pfa.hip); 257 and the other lengths up to 1024:
+// Rader / Bluestein convolution (cdft.hip); the rest: dense DCT matrix product (exact, O(n^2) per line).
+#include "cdft.h"
 #include "device_utils.h"
+#include "fft_lds.h"
 #include "kernels.h"
 #include "pfa.h"
 
@@ -34,6 +36,7 @@ struct DctPlan {
     double *Ei, *Oi;   // Ei[k'*njE + j] = C[2k'][j],          Oi[k'*h + j]  = C[2k'+1][j]
     int ne, no, h, njE;
     PfaPlan *pfa;   // prime-factor transform for the 2^k+1 lengths (pfa.hip); nullptr: dense product
+    CdftPlan *cdft; // Rader / Bluestein convolution (cdft.hip) for 257 and the other lengths up to 1024; nullptr: dense product
 };
 
 DctPlan *dct_plan_create(i64 n) {
@@ -46,6 +49,7 @@ DctPlan *dct_plan_create(i64 n) {
     p->Ef = p->Of = p->Ei = p->Oi = nullptr;
     p->ne = p->no = p->h = p->njE = 0;
     p->pfa = nullptr;
+    p->cdft = nullptr;
     if (n <= 1) return p;
     const long double PI = 3.141592653589793238462643383279502884L;
     if ((n & (n - 1)) == 0) {
@@ -71,12 +75,21 @@ DctPlan *dct_plan_create(i64 n) {
         (void)hipMemcpy(p->tw, tw.data(), sizeof(double2) * (n / 2), hipMemcpyHostToDevice);
         (void)hipMemcpy(p->ww, ww.data(), sizeof(double2) * n, hipMemcpyHostToDevice);
     } else {
-        static const bool pfa_on = !(getenv("DOTSOCP_PFA") && atoi(getenv("DOTSOCP_PFA")) == 0);
-        if (pfa_supported(n) && pfa_on) {
+        const int alg = dct_choose_algorithm(n);      // the one place that reads DOTSOCP_PFA / DOTSOCP_CDFT / DOTSOCP_CDFT_MIN
+        if (alg == DCT_ALG_PFA) {
             // the prime-factor transform needs three small tables; the n x n matrices of the dense product (16 MB and
             // two million long-double cosines at n = 1025) are not built
             p->pfa = pfa_plan_create(n);
             if (!p->pfa) {
+                dct_plan_destroy(p);
+                return nullptr;
+            }
+            return p;
+        }
+        if (alg == DCT_ALG_RADER || alg == DCT_ALG_BLUESTEIN) {
+            // a handful of tables of length n or M = 2^k < 4n instead of the n x n matrices
+            p->cdft = cdft_plan_create(n);
+            if (!p->cdft) {
                 dct_plan_destroy(p);
                 return nullptr;
             }
@@ -135,45 +148,13 @@ void dct_plan_destroy(DctPlan *p) {
     if (p->Ei) (void)hipFree(p->Ei);
     if (p->Oi) (void)hipFree(p->Oi);
     pfa_plan_destroy(p->pfa);
+    cdft_plan_destroy(p->cdft);
     delete p;
 }
-
-// Line addressing shared by all axes: line L, element k lives at
-//   (L % nin) + (L / nin) * outerStride + k * nin
-// axis 0: nin = 1, outerStride = n;  axis 1: nin = n0, outerStride = n0*n1;  axis 2: nin = n0*n1.
-// With pitched rows (pitch >= n0) the element stride is no longer the line count per group:
-// axis 0: nin = 1, outerStride = pitch, es = 1;  axis 1: nin = n0, outerStride = pitch*n1, es = pitch;
-// axis 2: nin = n0, outerStride = pitch, es = pitch*n1.  (The power-of-two kernels run unpitched: es == nin there.)
-struct LineMap {
-    i64 nin, outerStride, nLines, es;
-    __device__ __forceinline__ i64 base(i64 L) const { return (L % nin) + (L / nin) * outerStride; }
-    __device__ __forceinline__ i64 addr(i64 L, i64 k) const { return base(L) + k * es; }
-};
-
-__device__ __forceinline__ double2 cmul(double2 a, double2 b) {
-    return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
-}
-
-__device__ __forceinline__ int bitrev(int k, int lg) { return (int)(__brev((unsigned)k) >> (32 - lg)); }
 
 #define DCT_THREADS 256
 #define DCT_WAVES 4
 #define DCT_BATCH 8   // global loads in flight per lane before the first dependent LDS write
-// Position of element p inside its LDS row: the low four bits (which sixteenth of the 64 banks a 16-byte element
-// falls on) are XOR-ed with the next two groups of four bits, so that the stride-16 / stride-64 / ... accesses of the
-// grouped FFT stages AND the bit-reversed reads of the post-processing (consecutive k -> multiples of n / 16 apart)
-// spread over all banks; a permutation inside aligned blocks of 16, so rows need no padding.  (Additive padding
-// p + p / 16 left the bit-reversed reads four deep on the same banks and cost n / 16 elements per row.)
-__device__ __host__ __forceinline__ int padi(int p) { return p ^ ((p >> 4) & 15) ^ ((p >> 8) & 15); }
-__device__ __host__ __forceinline__ int row_stride(int n) { return n + (n >> 4) + 1; }
-
-// LDS hand-off between the lanes of ONE wavefront: DS operations of a wave execute in order, so
-// draining the wave's outstanding LDS operations is all the synchronisation that is needed.
-__device__ __forceinline__ void wave_lds_sync() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
-}
-
 // Twiddle tables as the kernels see them: a plain pointer, or -- for the 2048-point lines of the pipelined kernels, whose
 // two tile buffers leave 32 KB of LDS for tables -- the symmetric part only:
 //   exp(-2 pi i (j + n/4) / n) = -i exp(-2 pi i j / n)               -> a quarter of the FFT twiddles,
@@ -194,146 +175,6 @@ struct WwHalf {
         return (m <= h) ? v : make_double2(-v.y, -v.x);
     }
 };
-
-// d * exp(-2 pi i t / 16), t in [0, 8): the constant part of the twiddles inside a register group
-__device__ __forceinline__ double2 mul_w16(double2 d, int t) {
-    const double h = 0.70710678118654752440;   // cos(pi/4)
-    const double c1 = 0.92387953251128675613;  // cos(pi/8)
-    const double s1 = 0.38268343236508977173;  // sin(pi/8)
-    switch (t) {
-        case 0: return d;
-        case 1: return make_double2(d.x * c1 + d.y * s1, d.y * c1 - d.x * s1);
-        case 2: return make_double2(h * (d.x + d.y), h * (d.y - d.x));
-        case 3: return make_double2(d.x * s1 + d.y * c1, d.y * s1 - d.x * c1);
-        case 4: return make_double2(d.y, -d.x);
-        case 5: return make_double2(d.y * c1 - d.x * s1, -(d.x * c1 + d.y * s1));
-        case 6: return make_double2(h * (d.y - d.x), -h * (d.x + d.y));
-        default: return make_double2(d.y * s1 - d.x * c1, -(d.x * s1 + d.y * c1));
-    }
-}
-
-// One group of LR radix-2 decimation-in-frequency stages done in registers: the lane owns the
-// R = 2^LR elements base + m * (S/R) of one sub-transform of span S = 2^sl and performs the
-// butterflies of spans S, S/2, ..., S/2^(LR-1) on them (same data flow as LR passes of the
-// textbook in-place radix-2 DIF, so the output order is plain bit reversal).
-// LES > 0: the rows of a tile are interleaved element by element (element p of row r at (padi(p) << LES) + r, `row`
-// = tile + r) -- the image an LDS-DMA piece leaves when each lane fetches one (pair, k) element; LES = 0: plain rows
-template <int LR, int LES = 0, class TW = const double2 *>
-__device__ __forceinline__ void dif_group(double2 *__restrict__ row, int sl, int bidx, int lg, TW tw) {
-    constexpr int R = 1 << LR;
-    const int strideLog = sl - LR;
-    const int j = bidx & ((1 << strideLog) - 1);
-    const int base = ((bidx >> strideLog) << sl) + j;
-    double2 x[R];
-#pragma unroll
-    for (int m = 0; m < R; ++m) x[m] = row[padi(base + (m << strideLog)) << LES];
-    const int tj = j << (lg - sl);   // j * N / S
-#pragma unroll
-    for (int u = 0; u < LR; ++u) {
-        const int hm = R >> (u + 1);
-        const double2 bu = tw[tj << u];
-#pragma unroll
-        for (int m = 0; m < R; ++m) {
-            if ((m / hm) & 1) continue;
-            const int mm = m % hm;
-            const double2 a = x[m], b = x[m + hm];
-            x[m] = make_double2(a.x + b.x, a.y + b.y);
-            double2 d = make_double2(a.x - b.x, a.y - b.y);
-            d = mul_w16(d, (mm << u) * (16 / R));
-            x[m + hm] = cmul(d, bu);
-        }
-    }
-#pragma unroll
-    for (int m = 0; m < R; ++m) row[padi(base + (m << strideLog)) << LES] = x[m];
-}
-
-// FFT of the `nrows` = 2^lrw complex rows (length n = 2^lg) owned by the CALLING WAVE, in LDS:
-// natural order in, bit-reversed order out; ceil(lg/4) register groups with a wave-level LDS
-// hand-off after each (no workgroup barrier).
-__device__ __forceinline__ void fft_rows_wave(double2 *rows, int lrw, int lg, int rowStride, int lane,
-                                              const double2 *__restrict__ tw) {
-    const int nst = (lg + 3) >> 2;
-    const int baseBits = lg / nst, extra = lg % nst;
-    int sl = lg;
-    for (int st = 0; st < nst; ++st) {
-        const int lr = baseBits + (st < extra ? 1 : 0);
-        const int lpr = lg - lr;                        // log2(butterflies per row)
-        const int total = 1 << (lrw + lpr);
-        for (int b = lane; b < total; b += 64) {
-            double2 *r = rows + (b >> lpr) * rowStride;
-            const int bidx = b & ((1 << lpr) - 1);
-            switch (lr) {
-                case 4: dif_group<4>(r, sl, bidx, lg, tw); break;
-                case 3: dif_group<3>(r, sl, bidx, lg, tw); break;
-                case 2: dif_group<2>(r, sl, bidx, lg, tw); break;
-                default: dif_group<1>(r, sl, bidx, lg, tw); break;
-            }
-        }
-        sl -= lr;
-        wave_lds_sync();
-    }
-}
-
-// Decimation-in-time twin of dif_group: same element set (base + m * S/R), the butterflies of spans S/2^(LR-1),
-// ..., S/2, S in INCREASING order with the twiddle applied before the add / subtract -- bit-reversed input,
-// natural-order output.  Used where the spectrum is needed in place in natural order (fused t-axis solve).
-template <int LR, int LES = 0, class TW = const double2 *>
-__device__ __forceinline__ void dit_group(double2 *__restrict__ row, int sl, int bidx, int lg, TW tw) {
-    constexpr int R = 1 << LR;
-    const int strideLog = sl - LR;
-    const int j = bidx & ((1 << strideLog) - 1);
-    const int base = ((bidx >> strideLog) << sl) + j;
-    double2 x[R];
-#pragma unroll
-    for (int m = 0; m < R; ++m) x[m] = row[padi(base + (m << strideLog)) << LES];
-    const int tj = j << (lg - sl);   // j * N / S
-#pragma unroll
-    for (int u = LR - 1; u >= 0; --u) {
-        const int hm = R >> (u + 1);
-        const double2 bu = tw[tj << u];
-#pragma unroll
-        for (int m = 0; m < R; ++m) {
-            if ((m / hm) & 1) continue;
-            const int mm = m % hm;
-            const double2 a = x[m];
-            const double2 t = cmul(mul_w16(x[m + hm], (mm << u) * (16 / R)), bu);
-            x[m] = make_double2(a.x + t.x, a.y + t.y);
-            x[m + hm] = make_double2(a.x - t.x, a.y - t.y);
-        }
-    }
-#pragma unroll
-    for (int m = 0; m < R; ++m) row[padi(base + (m << strideLog)) << LES] = x[m];
-}
-
-// FFT of the calling wave's rows, bit-reversed order in, natural order out (the register groups of
-// fft_rows_wave in reverse order).
-__device__ __forceinline__ void fft_rows_wave_dit(double2 *rows, int lrw, int lg, int rowStride, int lane,
-                                                  const double2 *__restrict__ tw) {
-    const int nst = (lg + 3) >> 2;
-    const int baseBits = lg / nst, extra = lg % nst;
-    int sl = 0;
-    for (int st = nst - 1; st >= 0; --st) {
-        const int lr = baseBits + (st < extra ? 1 : 0);
-        sl += lr;
-        const int lpr = lg - lr;
-        const int total = 1 << (lrw + lpr);
-        for (int b = lane; b < total; b += 64) {
-            double2 *r = rows + (b >> lpr) * rowStride;
-            const int bidx = b & ((1 << lpr) - 1);
-            switch (lr) {
-                case 4: dit_group<4>(r, sl, bidx, lg, tw); break;
-                case 3: dit_group<3>(r, sl, bidx, lg, tw); break;
-                case 2: dit_group<2>(r, sl, bidx, lg, tw); break;
-                default: dit_group<1>(r, sl, bidx, lg, tw); break;
-            }
-        }
-        wave_lds_sync();
-    }
-}
-
-// Makhoul reordering v[j] = x[2j], v[n-1-j] = x[2j+1] (mirt_dctn.m:71) -- also the output
-// reordering of the inverse (mirt_idctn.m:71-73,120).
-__device__ __forceinline__ int makhoul(int k, int n) { return (k & 1) ? (n - 1 - (k >> 1)) : (k >> 1); }
 
 // LDS position of input element k while staging a line: forward transforms take the Makhoul order, the inverse
 // the natural one, the fused t-axis solve the bit-reversed Makhoul order (its forward FFT is decimation-in-time)
@@ -615,31 +456,6 @@ __global__ void __launch_bounds__(DCT_THREADS) k_dct_strided(const double *__res
 // staged row of the per-wave flavour above at the same LDS footprint -- the footprint, not registers,
 // caps the resident workgroups per CU, so this doubles the waves that overlap VALU, LDS and HBM phases.
 // ---------------------------------------------------------------------------------------------
-template <bool RAWB = false>
-__device__ __forceinline__ void fft_rows_wg(double2 *rows, int lrows, int lg, int rowStride, int t, int T,
-                                            const double2 *__restrict__ tw) {
-    const int nst = (lg + 3) >> 2;
-    const int baseBits = lg / nst, extra = lg % nst;
-    int sl = lg;
-    for (int st = 0; st < nst; ++st) {
-        const int lr = baseBits + (st < extra ? 1 : 0);
-        const int lpr = lg - lr;
-        const int total = 1 << (lrows + lpr);
-        for (int b = t; b < total; b += T) {
-            double2 *r = rows + (b >> lpr) * rowStride;
-            const int bidx = b & ((1 << lpr) - 1);
-            switch (lr) {
-                case 4: dif_group<4>(r, sl, bidx, lg, tw); break;
-                case 3: dif_group<3>(r, sl, bidx, lg, tw); break;
-                case 2: dif_group<2>(r, sl, bidx, lg, tw); break;
-                default: dif_group<1>(r, sl, bidx, lg, tw); break;
-            }
-        }
-        sl -= lr;
-        if (RAWB) lds_barrier(); else __syncthreads();
-    }
-}
-
 template <bool RAWB = false, class WW = const double2 *>
 __device__ __forceinline__ void idct_combine_wg(double2 *rows, int lrows, int lg, int rowStride, int t, int T, WW ww) {
     const int n = 1 << lg, lh = lg - 1;
@@ -1519,7 +1335,6 @@ __global__ void __launch_bounds__(256) k_copy(const double *__restrict__ src, do
 }
 
 #define DCT_LDS_BUDGET (72 * 1024)
-#define DCT_LDS_MAX (160 * 1024)
 
 static int floor_log2(i64 v) {
     int l = 0;
@@ -1541,36 +1356,9 @@ static int tile_log2_rows(int n, i64 nLines, int nbuf) {
     return lp;
 }
 
-template <class K>
-static void allow_big_lds(K kernel) {
-    (void)hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, DCT_LDS_MAX);
-}
-
-// Function attributes belong to the (function, device) pair: a process that drives several GPUs (dotsocp_create_multi)
-// has to raise the dynamic-LDS limit once on EVERY device it launches on.  true = not done yet on the current device.
-static std::mutex attr_mutex;
-struct DeviceOnce {
-    // `if (DeviceOnce once(mask); once) { raise the attributes }`: the lock is held while they are raised and the device's
-    // bit is set only afterwards, so a second host thread can neither skip the block early nor launch in between
-    std::unique_lock<std::mutex> lock;
-    unsigned long long *mask;
-    unsigned long long bit = 0;
-    bool first = true;
-    explicit DeviceOnce(unsigned long long &m) : lock(attr_mutex), mask(&m) {
-        int dev = 0;
-        if (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64) {
-            bit = 1ull << dev;
-            first = !(m & bit);
-        }
-    }
-    ~DeviceOnce() { if (first && bit) *mask |= bit; }
-    explicit operator bool() const { return first; }
-};
-
 bool dct_plan_is_pow2(const DctPlan *p) { return p->log2n > 0; }
 bool dct_plan_has_tsolve(const DctPlan *p) {
-    static const bool pfa_on = !(getenv("DOTSOCP_PFA") && atoi(getenv("DOTSOCP_PFA")) == 0);
-    return p->log2n > 0 || (p->pfa && pfa_on);
+    return p->log2n > 0 || p->pfa != nullptr;
 }
 
 static int device_cus() {
@@ -1859,12 +1647,12 @@ int launch_dct_axis(const DctPlan *p, const double *src, double *dst, i64 n0, i6
                                lg, lrw, p->tw, p->ww);
     } else {
         // DOTSOCP_PFA=0: the dense product also for the lengths that have a prime-factor transform
-        static const bool pfa_on = !(getenv("DOTSOCP_PFA") && atoi(getenv("DOTSOCP_PFA")) == 0);
-        if (p->pfa && pfa_on) {
+        if (p->pfa) {
             if (axis == 0) return pfa_launch_axis0(p->pfa, src, dst, map.nLines, P0, P0, inverse, st);
             if (axis == 1) return pfa_launch_strided(p->pfa, src, dst, n0, n2, P0 * n1, P0, P0 * n1, P0, inverse ? 1 : 0, nullptr, st);
             return pfa_launch_strided(p->pfa, src, dst, n0, n1, P0, P0 * n1, P0, P0 * n1, inverse ? 1 : 0, nullptr, st);
         }
+        if (p->cdft) return cdft_launch(p->cdft, src, dst, map, axis == 0, inverse, st);
         if (src == dst) {
             set_error("dense DCT path needs distinct src/dst");
             return DOTSOCP_EINVAL;

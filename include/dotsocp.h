@@ -209,6 +209,11 @@ int dotsocp_slab_range(dotsocp_i64 nt, int world, int rank, dotsocp_i64 *t0, dot
  * before any pointer reaches the library. */
 dotsocp_i64 dotsocp_field_len(const dotsocp_problem *prob, int field);
 
+/* Which transform the DCT passes use for an axis of length n (pure host arithmetic, no device; honours the switches
+ * DOTSOCP_PFA, DOTSOCP_CDFT, DOTSOCP_CDFT_MIN): 0 none (n <= 1), 1 power-of-two FFT, 2 prime-factor FFT, 3 Rader (257),
+ * 4 Bluestein (other lengths up to 1024), 5 dense DCT-matrix product. */
+int dotsocp_dct_algorithm(dotsocp_i64 n);
+
 int dotsocp_upload(dotsocp_ctx *ctx, int field, const double *host);
 int dotsocp_download(dotsocp_ctx *ctx, int field, double *host);
 /* Extension for drivers: time layers [t0, t0 + n) of a NODE field (DOTSOCP_F_PHI, DOTSOCP_F_C) from a host buffer that

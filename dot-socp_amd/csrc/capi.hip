@@ -2,7 +2,6 @@
 #include <cstring>
 #include <new>
 
-#include "cdft.h"
 #include "comm.h"
 #include "solver.h"
 
@@ -225,28 +224,14 @@ int dotsocp_oper_poisson(double *res, const double *rhs, dotsocp_i64 ny, dotsocp
     DS_CHECK(table(cx, nx));
     DS_CHECK(table(ct, nt));
     DS_HIP(hipMemcpy(da.p, rhs, sizeof(double) * n, hipMemcpyHostToDevice));
-    const char *ts = getenv("DOTSOCP_TSOLVE");
-    if (!(ts && strcmp(ts, "dct") == 0) && tsolve_tri_preferred(nt, dct_plan_is_pow2(pl.pt), ny * nx)) {
-        // the sequence of Solver::poisson_all where the t axis is solved as tridiagonal systems (tri.hip): no transform along t
-        Grid g;
-        g.set(ny, nx, nt, 0, nt);
-        DS_CHECK(launch_dct_axis(pl.py, da.p, db.p, ny, nx, nt, 0, 0, nullptr));
-        DS_CHECK(launch_dct_axis(pl.px, db.p, da.p, ny, nx, nt, 1, 0, nullptr));
-        DS_CHECK(launch_tsolve_tri(g, nt, kernelScale, cy.p, cx.p, da.p, nullptr));
-        DS_CHECK(launch_dct_axis(pl.px, da.p, db.p, ny, nx, nt, 1, 1, nullptr));
-        DS_CHECK(launch_dct_axis(pl.py, db.p, da.p, ny, nx, nt, 0, 1, nullptr));
-    } else if (dct_plan_has_tsolve(pl.pt)) {
-        // the sequence of Solver::poisson_all: y, x forward, the fused t pass (forward, division, inverse), x, y inverse
-        DS_CHECK(launch_dct_axis(pl.py, da.p, db.p, ny, nx, nt, 0, 0, nullptr));
-        DS_CHECK(launch_dct_axis(pl.px, db.p, da.p, ny, nx, nt, 1, 0, nullptr));
-        DS_CHECK(launch_dct_t_solve(pl.pt, da.p, da.p, ny, ny * nx, 0, ny * nx, nt, kernelScale, cy.p, cx.p, ct.p, nullptr));
-        DS_CHECK(launch_dct_axis(pl.px, da.p, db.p, ny, nx, nt, 1, 1, nullptr));
-        DS_CHECK(launch_dct_axis(pl.py, db.p, da.p, ny, nx, nt, 0, 1, nullptr));
-    } else {
-        DS_CHECK(dctn_dev(da.p, db.p, ny, nx, nt, 0, pl.py, pl.px, pl.pt));
-        DS_CHECK(launch_spectral_divide(db.p, ny, nx, nt, 0, nx, kernelScale, cy.p, cx.p, ct.p, nullptr));
-        DS_CHECK(dctn_dev(db.p, da.p, ny, nx, nt, 1, pl.py, pl.px, pl.pt));
-    }
+    // y, x forward, the t step in place (unpitched rows), x, y inverse
+    Grid g;
+    g.set(ny, nx, nt, 0, nt);
+    DS_CHECK(launch_dct_axis(pl.py, da.p, db.p, ny, nx, nt, 0, 0, nullptr));
+    DS_CHECK(launch_dct_axis(pl.px, db.p, da.p, ny, nx, nt, 1, 0, nullptr));
+    DS_CHECK(launch_poisson_t_single(pl.pt, g, kernelScale, cy.p, cx.p, ct.p, da.p, db.p, 0, nullptr, tsolve_tri_allowed()));
+    DS_CHECK(launch_dct_axis(pl.px, da.p, db.p, ny, nx, nt, 1, 1, nullptr));
+    DS_CHECK(launch_dct_axis(pl.py, db.p, da.p, ny, nx, nt, 0, 1, nullptr));
     DS_HIP(hipDeviceSynchronize());
     DS_HIP(hipMemcpy(res, da.p, sizeof(double) * n, hipMemcpyDeviceToHost));
     return 0;

@@ -8,11 +8,7 @@ namespace dotsocp {
 struct CdftPlan;
 struct LineMap;
 
-// Which transform a DCT plan of length n uses (dotsocp_dct_algorithm of include/dotsocp.h).
-enum { DCT_ALG_NONE = 0, DCT_ALG_FFT = 1, DCT_ALG_PFA = 2, DCT_ALG_RADER = 3, DCT_ALG_BLUESTEIN = 4, DCT_ALG_DENSE = 5 };
-
-// Pure host arithmetic (no HIP call); honours DOTSOCP_PFA, DOTSOCP_CDFT and DOTSOCP_CDFT_MIN, each read once per process.
-int dct_choose_algorithm(i64 n);
+#define CDFT_MAX_N 1024
 
 CdftPlan *cdft_plan_create(i64 n);      // n = 257: Rader; any other 48 <= n <= 1024: Bluestein; nullptr otherwise
 void cdft_plan_destroy(CdftPlan *p);

@@ -1,4 +1,4 @@
-// DCT-II / DCT-III for the lengths that are neither powers of two (dct.hip) nor prime-factor lengths (pfa.hip): the
+// DCT-II / DCT-III for the lengths that are neither powers of two (dct_pow2.hip) nor prime-factor lengths (pfa.hip): the
 // length-n complex DFT behind Makhoul's DCT (mirt_dctn.m:100-141, mirt_idctn.m:98-128 are FFT-based for ANY length) as a
 // cyclic convolution of power-of-two length M, entirely in LDS (tools/cdft_proto.py is the numpy model):
 //   gather through a position table (x input multiplier) -> zero-fill to M -> forward FFT (decimation in frequency,
@@ -17,7 +17,6 @@
 #include "device_utils.h"
 #include "fft_lds.h"
 #include "kernels.h"
-#include "pfa.h"
 
 #include <cmath>
 #include <complex>
@@ -26,27 +25,6 @@
 #include <vector>
 
 namespace dotsocp {
-
-// smallest length that takes Bluestein by default: the measured crossover against the dense product on both axis kinds
-// (profiles/cdft_pass_times.csv); DOTSOCP_CDFT_MIN overrides, never below 48
-#define CDFT_DEFAULT_MIN 500
-#define CDFT_MAX_N 1024
-
-int dct_choose_algorithm(i64 n) {
-    static const bool pfa_on = !(getenv("DOTSOCP_PFA") && atoi(getenv("DOTSOCP_PFA")) == 0);
-    static const bool cdft_on = !(getenv("DOTSOCP_CDFT") && atoi(getenv("DOTSOCP_CDFT")) == 0);
-    static const i64 nb = [] {
-        const char *e = getenv("DOTSOCP_CDFT_MIN");
-        const i64 v = e ? atoll(e) : CDFT_DEFAULT_MIN;
-        return v < 48 ? (i64)48 : v;
-    }();
-    if (n <= 1) return DCT_ALG_NONE;
-    if ((n & (n - 1)) == 0) return DCT_ALG_FFT;
-    if (pfa_supported(n)) return pfa_on ? DCT_ALG_PFA : DCT_ALG_DENSE;
-    if (cdft_on && n == 257) return DCT_ALG_RADER;
-    if (cdft_on && n >= nb && n <= CDFT_MAX_N) return DCT_ALG_BLUESTEIN;
-    return DCT_ALG_DENSE;
-}
 
 struct CdftPlan {
     int n, lg;             // line length; the convolution has M = 2^lg points

@@ -1,0 +1,30 @@
+// The two transform families that live beside pfa.hip and cdft.hip: powers of two (dct_pow2.hip) and the dense
+// product (dct_dense.hip).  dct.hip picks one family per plan (dct_choose_algorithm) and dispatches on that choice.
+#pragma once
+#include "common.h"
+
+namespace dotsocp {
+
+struct LineMap;      // fft_lds.h
+struct Pow2Plan;
+struct DensePlan;
+
+#define DCT_THREADS 256
+
+Pow2Plan *pow2_plan_create(i64 n);      // n = 2^k >= 2; nullptr on allocation failure
+void pow2_plan_destroy(Pow2Plan *p);
+// DCT-II (inverse = 0) / DCT-III of the lines of `map`; src == dst is allowed.
+// axis 0: line L starts at L * map.outerStride, elements contiguous; strided: the x and t axes
+int pow2_launch_axis0(const Pow2Plan *p, const double *src, double *dst, const LineMap &map, int inverse, hipStream_t st);
+int pow2_launch_strided(const Pow2Plan *p, const double *src, double *dst, const LineMap &map, int inverse, hipStream_t st);
+// DCT-II along t, division by kscale * lambda, DCT-III along t in one pass (arguments: launch_dct_t_solve of kernels.h)
+int pow2_launch_tsolve(const Pow2Plan *p, const double *src, double *dst, i64 ny, i64 nplane, i64 line0, i64 nl,
+                       double kscale, const double *cy, const double *cx, const double *ct, hipStream_t st, i64 pitch0);
+
+DensePlan *dense_plan_create(i64 n);    // any n >= 2; nullptr on allocation failure
+void dense_plan_destroy(DensePlan *p);
+// axis0: line L starts at L * map.outerStride, elements contiguous.  Needs src != dst.
+int dense_launch(const DensePlan *p, const double *src, double *dst, const LineMap &map, bool axis0, int inverse,
+                 hipStream_t st);
+
+}  // namespace dotsocp

@@ -1,4 +1,4 @@
-// LDS FFT building blocks shared by the power-of-two DCT kernels (dct.hip) and the convolution-based DFT
+// LDS FFT building blocks shared by the power-of-two DCT kernels (dct_pow2.hip) and the convolution-based DFT
 // (cdft.hip): line addressing, the bank-spreading row layout, radix-2 register groups (decimation in frequency
 // and in time) and the per-wave / per-workgroup drivers over them.
 #pragma once

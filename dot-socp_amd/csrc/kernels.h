@@ -278,17 +278,22 @@ int launch_norms(const Grid &g, const LoopCoef &c, const KktCoef &k, const Fused
 double *kkt_qstep_partials(const Grid &g, const KktWork &w);
 int launch_kkt_final(const Grid &g, const KktWork &w, hipStream_t st);
 
-// ---------------- dct.hip ----------------
-struct DctPlan;   // twiddles / dense matrices for one axis length
+// ---------------- dct.hip: plan, choice of the transform family, dispatch, spectral division ----------------
+// (the families: dct_pow2.hip, pfa.hip, cdft.hip, dct_dense.hip -- dct_families.h, pfa.h, cdft.h)
+// Which transform a DCT plan of length n uses (dotsocp_dct_algorithm of include/dotsocp.h).
+enum { DCT_ALG_NONE = 0, DCT_ALG_FFT = 1, DCT_ALG_PFA = 2, DCT_ALG_RADER = 3, DCT_ALG_BLUESTEIN = 4, DCT_ALG_DENSE = 5 };
+// Pure host arithmetic (no HIP call); honours DOTSOCP_PFA, DOTSOCP_CDFT and DOTSOCP_CDFT_MIN, each read once per process.
+int dct_choose_algorithm(i64 n);
+struct DctPlan;   // the choice for one axis length and the chosen family's tables
 DctPlan *dct_plan_create(i64 n);
 void dct_plan_destroy(DctPlan *p);
 // Orthonormal DCT-II (inverse=0) / DCT-III (inverse=1) along one axis of an [n0][n1][n2] array
-// (n0 fastest), src -> dst.  axis = 0, 1 or 2.  src == dst is allowed for power-of-two and prime-factor lengths.
+// (n0 fastest), src -> dst.  axis = 0, 1 or 2.  src == dst is allowed for every length but those of the dense product.
 // pitch0 > n0: the rows of both arrays are pitch0 doubles apart ([pitch0][n1][n2] with n0 valid entries per row);
 // power-of-two n0 is never pitched.
 int launch_dct_axis(const DctPlan *p, const double *src, double *dst, i64 n0, i64 n1, i64 n2, int axis,
                     int inverse, hipStream_t st, i64 pitch0 = 0);
-// Power-of-two nt only: DCT-II along t, spectral division, DCT-III along t in ONE pass over a
+// Power-of-two and prime-factor nt (dct_plan_has_tsolve): DCT-II along t, spectral division, DCT-III along t in ONE pass over a
 // pencil [nl][nt]: the columns line0 .. line0+nl-1 of the ny*nx = nplane (y, x) columns (y fastest),
 // all nt time nodes; src -> dst (may alias).
 bool dct_plan_is_pow2(const DctPlan *p);
@@ -296,12 +301,19 @@ bool dct_plan_has_tsolve(const DctPlan *p);   // fused forward / divide / invers
 int launch_dct_t_solve(const DctPlan *p, const double *src, double *dst, i64 ny, i64 nplane, i64 line0, i64 nl,
                        i64 nt, double kscale, const double *cy, const double *cx, const double *ct, hipStream_t st,
                        i64 pitch0 = 0);   // pitch0 > ny: whole layers (line0 = 0, nl = nplane) with pitched rows
-// same pencil, non-power-of-two nt: spectral division only (between two dense DCT passes)
-int launch_spectral_divide_pencil(double *data, i64 ny, i64 nplane, i64 line0, i64 nl, i64 nt, double kscale,
-                                  const double *cy, const double *cx, const double *ct, hipStream_t st);
+// same pencil, an nt without the fused pass: spectral division only (between two DCT passes)
+int launch_spectral_divide_pencil(double *data, i64 ny, i64 line0, i64 nl, i64 nt, double kscale, const double *cy,
+                                  const double *cx, const double *ct, hipStream_t st);
 // data[i] /= kscale * lambda(i)  with lambda the DCT eigenvalues of initialize_FFTkernel.m:6-15
 // for global dims (ny, nx, nt); the local block covers x in [x0, x0+nxl) (pencil mode) and all y, t.
-int launch_spectral_divide(double *data, i64 ny, i64 nx, i64 nt, i64 x0, i64 nxl, double kscale,
-                           const double *cy, const double *cx, const double *ct, hipStream_t st, i64 pitch0 = 0);
+int launch_spectral_divide(double *data, i64 ny, i64 nt, i64 x0, i64 nxl, double kscale, const double *cy,
+                           const double *cx, const double *ct, hipStream_t st, i64 pitch0 = 0);
+// DOTSOCP_TSOLVE=dct switches the tridiagonal t solves (tri.hip) off
+bool tsolve_tri_allowed();
+// The single slab's t step of the Poisson solve, in place on p = [pitch0 or ny][nx][nt] (p2: scratch of the same size),
+// by the fastest of: the tridiagonal solve (allow_tri and tsolve_tri_preferred), the fused t pass (dct_plan_has_tsolve),
+// forward transform + spectral division + inverse transform.
+int launch_poisson_t_single(const DctPlan *pt, const Grid &g, double kscale, const double *cy, const double *cx,
+                            const double *ct, double *p, double *p2, i64 pitch0, hipStream_t st, bool allow_tri);
 
 }  // namespace dotsocp

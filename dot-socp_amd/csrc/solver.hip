@@ -1,7 +1,7 @@
 // Host side of the device-resident inPALM / ALG2 loop.  The scalar control flow (sigma rule,
 // rescale triggers, KKT ratios, stop test) restates socp/dot2d/algorithms/solver_socp_inPALM.m
 // (and solver_wsocp_inPALM.m for the weighted variant) line by line; all array work is done by the
-// kernels of cone.hip / fused.hip / stencil.hip / dct.hip / kkt.hip on the slab's HIP streams.
+// kernels of cone.hip / fused.hip / stencil.hip / dct*.hip / kkt.hip on the slab's HIP streams.
 //
 // Time-slab mode (world > 1): the grid is cut along t (common.h: Grid).  Per iteration a slab
 // exchanges six ny x nx layers with its neighbours (u0 tail, phi head, adjoint tails, bx/by heads)
@@ -325,7 +325,7 @@ int Solver::init(const dotsocp_problem *p, int dev, int nslabs, bool multi_dev) 
     if (const char *e = getenv("DOTSOCP_OVERLAP")) overlap = (atoi(e) != 0);
     if (const char *e = getenv("DOTSOCP_KKT_FOLD")) kkt_fold = (atoi(e) != 0);
     if (const char *e = getenv("DOTSOCP_NORM_CACHE")) norm_cache = (atoi(e) != 0);
-    if (const char *e = getenv("DOTSOCP_TSOLVE")) tri_tsolve = (strcmp(e, "dct") != 0);
+    tri_tsolve = tsolve_tri_allowed();
     DS_HIP(hipHostMalloc((void **)&h_sums, sizeof(double) * (S_COUNT + 1)));
     DS_CHECK(dmalloc(&d_red, S_COUNT + 1));
     if (!res_for(dev)) return DOTSOCP_EHIP;
@@ -1339,23 +1339,13 @@ int Solver::poisson_all(const PhiHooks *hooks) {
         double *p2 = multi() ? s.pencil2 : s.w1;
         if (!multi()) {
             // the single slab: rows may be pitched (common.h), the (y, x) columns of a layer are ny lines in each of nx rows
-            const Grid &g = s.g;
-            if (tri_tsolve && tsolve_tri_preferred(nt, dct_plan_is_pow2(s.res->pt), g.plane)) {
-                // no transform along t: the (ky, kx) modes are tridiagonal systems in t (tri.hip: k_tsolve_single / _pipe);
-                // DOTSOCP_TSOLVE=dct: the transform passes below for every length
-                DS_CHECK(launch_tsolve_tri(g, nt, D * D, s.res->cy, s.res->cx, p, s.st));
-            } else if (tp2) {
-                DS_CHECK(launch_dct_t_solve(s.res->pt, p, p, ny, ny * nx, 0, ny * nx, nt, D * D, s.res->cy, s.res->cx, s.res->ct, s.st, g.py));
-            } else {
-                DS_CHECK(launch_dct_axis(s.res->pt, p, p2, g.ny, g.nx, nt, 2, 0, s.st, g.py));
-                DS_CHECK(launch_spectral_divide(p2, ny, nx, nt, 0, nx, D * D, s.res->cy, s.res->cx, s.res->ct, s.st, g.py));
-                DS_CHECK(launch_dct_axis(s.res->pt, p2, p, g.ny, g.nx, nt, 2, 1, s.st, g.py));
-            }
+            // (DOTSOCP_TSOLVE=dct: the transform passes for every length)
+            DS_CHECK(launch_poisson_t_single(s.res->pt, s.g, D * D, s.res->cy, s.res->cx, s.res->ct, p, p2, s.g.py, s.st, tri_tsolve));
         } else if (tp2) {
             DS_CHECK(launch_dct_t_solve(s.res->pt, p, p, s.g.py, plane, s.l0, s.nl, nt, D * D, s.res->cy, s.res->cx, s.res->ct, s.st));
         } else {
             DS_CHECK(launch_dct_axis(s.res->pt, p, p2, s.nl, 1, nt, 2, 0, s.st));
-            DS_CHECK(launch_spectral_divide_pencil(p2, s.g.py, plane, s.l0, s.nl, nt, D * D, s.res->cy, s.res->cx, s.res->ct, s.st));
+            DS_CHECK(launch_spectral_divide_pencil(p2, s.g.py, s.l0, s.nl, nt, D * D, s.res->cy, s.res->cx, s.res->ct, s.st));
             DS_CHECK(launch_dct_axis(s.res->pt, p2, p, s.nl, 1, nt, 2, 1, s.st));
         }
     }

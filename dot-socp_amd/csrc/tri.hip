@@ -582,7 +582,7 @@ __global__ void __launch_bounds__(64 * NSUB) k_tsolve_single(TriGeom g, i64 nt, 
     }
 }
 
-// The same solve as a PERSISTENT kernel fed by LDS-DMA (the recipe of dct.hip's pipelined passes): a workgroup walks tiles of
+// The same solve as a PERSISTENT kernel fed by LDS-DMA (the recipe of dct_pow2.hip's pipelined passes): a workgroup walks tiles of
 // 64 modes; the rows of the NEXT tile travel into an LDS image [row][mode] by global_load_lds_dwordx4 (no registers) while
 // the current tile is eliminated in registers and stored, so loads are in flight all the time -- the one-tile-per-workgroup
 // kernel above alternates between loading and computing (0.62 ms at nt = 128 where the traffic takes 0.4).  One LDS image:

@@ -214,8 +214,8 @@ def test_pipelined_dct_kernels_against_the_workgroup_wide_ones():
     """DOTSOCP_DCT_PIPE=0 (read once per process, hence the subprocesses) switches the persistent LDS-DMA kernels off; both
     families run the same butterflies on the same operands, so transforms and Poisson solves agree to rounding of the
     few places where the order of operations differs or where the compiler contracts a * b + c differently in the two
-    families (dct.hip is built with -ffp-contract=fast since round 3: the FFT has no operation-by-operation counterpart
-    in the reference)."""
+    families (dct.hip, dct_pow2.hip, dct_dense.hip and cdft.hip are built with -ffp-contract=fast: the FFT has no
+    operation-by-operation counterpart in the reference)."""
     import os
     import subprocess
     import sys

@@ -162,10 +162,8 @@ __global__ void __launch_bounds__(TILE_Y *TILE_X) k_cone_march(Grid g, LoopCoef 
             for (int j = 0; j < 10; ++j) zout[j * g.Nc + i] = v[j];
         } else {
 #pragma unroll
-            for (int j = 0; j < 10; ++j) {
-                const double r = zin[j * g.Nc + i] - v[j];
-                betaout[j * g.Nc + i] = betain[j * g.Nc + i] + c.tau * r;
-            }
+            for (int j = 0; j < 10; ++j)
+                betaout[j * g.Nc + i] = mult_finish(mult_carry(betain[j * g.Nc + i], zin[j * g.Nc + i], c.tau), v[j], c.tau);
         }
         cur = nxt;
     }

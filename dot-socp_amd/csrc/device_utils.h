@@ -94,6 +94,13 @@ __device__ __forceinline__ void proj_row(double (&v)[K]) {
     v[0] = (c >= 1.0) ? v[0] : c * n;
 }
 
+// The multiplier step beta^k = beta^{k-1} + tau z^k - tau v^k (v = BF q^k + d, solver_socp_inPALM.m:212-215) in two
+// halves with explicit fma, the same at every site: gamma = mult_carry(beta, z, tau) may be formed by one pass and stored,
+// beta = mult_finish(gamma, v, tau) by the next (fused.hip: the gamma form) -- gamma is an exact double, so a pass that
+// reads it from memory gets the bits of a pass that formed it in a register.
+__device__ __forceinline__ double mult_carry(double b, double z, double tau) { return fma(tau, z, b); }
+__device__ __forceinline__ double mult_finish(double g, double v, double tau) { return fma(-tau, v, g); }
+
 // The four staggered edge values around cell column (y, x) at time layer tt (pre-multiplied
 // by sf); edges outside the domain contribute exact zeros (mexBFd never writes those slots).
 struct EdgeQuad {
@@ -180,6 +187,7 @@ struct RhsArgs {
     Grid g;
     double at, ax, ay;
     const double *q, *alpha, *cvec, *weight, *u0_prev;
+    int c_ends;        // c is zero off the two global end layers (Slab::c_ends): those alone are loaded
 };
 
 template <bool WEIGHTED>
@@ -199,7 +207,9 @@ __device__ __forceinline__ double rhs_value(const RhsArgs &a, i64 y, i64 x, i64 
     const i64 byo = g.offBy + g.byLayer * tl;
     if (y >= 1) r += a.ay * u(byo + (y - 1) + g.pyb * x);
     if (y <= g.ny - 2) r += (-a.ay) * u(byo + y + g.pyb * x);
-    return r + a.cvec[node];
+    const bool tbnd = (g.t0 + tl == 0) || (g.t0 + tl == g.nt - 1);
+    const double cv = (a.c_ends && !tbnd) ? 0.0 : a.cvec[node];
+    return r + cv;
 }
 
 }  // namespace dotsocp

@@ -8,6 +8,12 @@
 //     q2       = F* B* (z^{k+1} + beta^k)              adjoint gather for the q-step        (:205)
 //   traffic: beta in + beta out + q_old + q + q2 = 8 (20 Nz + 3 Nq) bytes; the beta streams non-temporal (device_utils.h:
 //   ld_stream / st_stream; the cell entries of q and the gather's stores the same way: no further gain, measured).
+//   MODE_B, the gamma form (template flags GIN / GOUT; scheduled by Solver::step, solver.h).  The multiplier step is
+//     beta^k = beta^{k-1} + tau z^k - tau (BF q^k + d), and z^k was in registers one pass earlier.  GOUT: store
+//     gamma^k = beta^k + tau z^{k+1} (mult_carry) where beta^k would go.  GIN: beta_in holds gamma^{k-1}, beta^k =
+//     gamma^{k-1} - tau (BF q^k + d) (mult_finish) -- no q_old, no first projection: 8 (20 Nz + 2 Nq) bytes.
+//     (GIN, GOUT) = (0,0) as above, (0,1) entry, (1,1) steady state, (1,0) exit.  The recomputed cell in front of a
+//     chunk reads gamma from the input buffer like every other cell.
 //   MODE_A: same without the deferred update (beta already current): 8 (10 Nz + 2 Nq) bytes.
 //   MODE_M (2): materialise -- beta update + write z (needed by the rescale block / outputs).
 //   MODE_Z (3): z = Pi_Q(BF q_old + d - beta_in) only (z of the last iteration from the kept beta^k).
@@ -37,8 +43,9 @@
 
 namespace dotsocp {
 
-template <int MODE, int XB, bool NT = false>
+template <int MODE, int XB, bool NT = false, bool GIN = false, bool GOUT = false>
 __global__ void __launch_bounds__(64 * XB) k_cone_fused(Grid g, LoopCoef c, FusedArgs a) {
+    static_assert(MODE == 1 || !(GIN || GOUT), "the gamma form exists between two MODE_B passes only");
     constexpr bool DUAL = (MODE >= 5);              // second gather (PALM)
     constexpr bool UPD = (MODE != 0 && MODE != 6);  // deferred multiplier step in front of the projection
     constexpr bool PROJ = (MODE < 2 || MODE >= 5);  // new projection + gather
@@ -61,7 +68,7 @@ __global__ void __launch_bounds__(64 * XB) k_cone_fused(Grid g, LoopCoef c, Fuse
     const i64 nxblk = gridDim.y, nyblk = gridDim.x;
 
     EdgeQuad cur = load_edges(g, a.q, yc, xc, tstart, c.sf), curo, cur3;
-    if (UPD) curo = load_edges(g, a.q_old, yc, xc, tstart, c.sf);
+    if (UPD && !GIN) curo = load_edges(g, a.q_old, yc, xc, tstart, c.sf);
     if (MODE == 5) cur3 = load_edges(g, a.q3, yc, xc, tstart, c.sf);
     GatherCarry gc, gcp;
     if (carried) {
@@ -81,7 +88,7 @@ __global__ void __launch_bounds__(64 * XB) k_cone_fused(Grid g, LoopCoef c, Fuse
             double b[10], v[10];
 #pragma unroll
             for (int j = 0; j < 10; ++j) b[j] = ld_stream<NT>(a.beta_in + j * g.Nc + i);
-            if (a.bpend) {
+            if (!GIN && a.bpend) {         // gamma never carries a pending scaling (Solver::phase_z)
 #pragma unroll
                 for (int j = 0; j < 10; ++j) b[j] = b[j] * a.bmul / a.bdiv;
                 if (a.bpend > 1) {
@@ -90,7 +97,14 @@ __global__ void __launch_bounds__(64 * XB) k_cone_fused(Grid g, LoopCoef c, Fuse
                 }
             }
             build_z2(v, a.q[i], cur, nxt, c.s, c.dF);
-            if (UPD) {
+            if constexpr (GIN) {           // beta_in holds gamma^{k-1} = beta^{k-1} + tau z^k
+#pragma unroll
+                for (int j = 0; j < 10; ++j) b[j] = mult_finish(b[j], v[j], c.tau);
+                if (!GOUT && own && inb) {
+#pragma unroll
+                    for (int j = 0; j < 10; ++j) st_stream<NT>(a.beta_out + j * g.Nc + i, b[j]);
+                }
+            } else if constexpr (UPD) {
                 const EdgeQuad nxto = load_edges(g, a.q_old, yc, xc, tl + 1, c.sf);
                 double zo[10];
                 build_z2(zo, a.q_old[i], curo, nxto, c.s, c.dF);
@@ -98,12 +112,9 @@ __global__ void __launch_bounds__(64 * XB) k_cone_fused(Grid g, LoopCoef c, Fuse
                 for (int j = 0; j < 10; ++j) zo[j] = zo[j] - b[j];
                 proj_row<10>(zo);
 #pragma unroll
-                for (int j = 0; j < 10; ++j) {
-                    const double r = zo[j] - v[j];
-                    b[j] = b[j] + c.tau * r;
-                }
+                for (int j = 0; j < 10; ++j) b[j] = mult_finish(mult_carry(b[j], zo[j], c.tau), v[j], c.tau);
                 if (own && inb) {
-                    if (MODE != 3) {
+                    if (MODE != 3 && !GOUT) {
 #pragma unroll
                         for (int j = 0; j < 10; ++j) st_stream<NT>(a.beta_out + j * g.Nc + i, b[j]);
                     }
@@ -129,6 +140,10 @@ __global__ void __launch_bounds__(64 * XB) k_cone_fused(Grid g, LoopCoef c, Fuse
 #pragma unroll
                 for (int j = 0; j < 10; ++j) v[j] = v[j] - b[j];
                 proj_row<10>(v);
+                if (GOUT && own && inb) {  // gamma^k = beta^k + tau z^{k+1}: the next pass needs no q^k and no second projection
+#pragma unroll
+                    for (int j = 0; j < 10; ++j) st_stream<NT>(a.beta_out + j * g.Nc + i, mult_carry(b[j], v[j], c.tau));
+                }
 #pragma unroll
                 for (int j = 0; j < 10; ++j) w[j] = v[j] + b[j];
                 if (own && inb) a.q2[i] = c.s * (w[9] - w[0]);
@@ -200,7 +215,7 @@ int fused_geometry(const Grid &g, FusedGeom &fg) {
 }
 
 int launch_cone_fused(int mode, const Grid &g, const LoopCoef &c, const FusedGeom &fg, FusedArgs a,
-                      hipStream_t st, i64 z0, i64 zcount) {
+                      hipStream_t st, i64 z0, i64 zcount, int flavour) {
     if (g.Nz <= 0) return 0;
     if (zcount < 0) zcount = fg.chunks - z0;
     if (z0 < 0 || zcount <= 0 || z0 + zcount > fg.chunks) return 0;
@@ -215,6 +230,19 @@ int launch_cone_fused(int mode, const Grid &g, const LoopCoef &c, const FusedGeo
         if (nt) DS_KLAUNCH((k_cone_fused<M, 4, true>), grid, blk, 0, st, g, c, a);       \
         else DS_KLAUNCH((k_cone_fused<M, 4>), grid, blk, 0, st, g, c, a);                \
         break;
+    if (flavour != 0) {          // gamma form: CONE_GIN / CONE_GOUT flavours of mode 1
+        if (mode != 1 || (flavour & ~(CONE_GIN | CONE_GOUT))) { set_error("bad fused flavour"); return DOTSOCP_EINVAL; }
+        if ((flavour & CONE_GIN) && a.bpend) { set_error("internal: gamma with a pending scaling"); return DOTSOCP_ESTATE; }
+#define CONE_FLAV(GI, GO)                                                                          \
+        if (nt) DS_KLAUNCH((k_cone_fused<1, 4, true, GI, GO>), grid, blk, 0, st, g, c, a);         \
+        else DS_KLAUNCH((k_cone_fused<1, 4, false, GI, GO>), grid, blk, 0, st, g, c, a);
+        if (flavour == CONE_GOUT) { CONE_FLAV(false, true) }
+        else if (flavour == CONE_GIN) { CONE_FLAV(true, false) }
+        else { CONE_FLAV(true, true) }
+#undef CONE_FLAV
+        DS_HIP(hipGetLastError());
+        return 0;
+    }
     switch (mode) {
         CONE_MODE(0) CONE_MODE(1) CONE_MODE(2) CONE_MODE(3) CONE_MODE(4) CONE_MODE(5) CONE_MODE(6)
 #undef CONE_MODE

@@ -85,8 +85,11 @@ int fused_geometry(const Grid &g, FusedGeom &fg);
 // mode 0: projection + gather; 1: deferred beta update + projection + gather; 2: materialise beta and z;
 // 3: z only, from (q_old, beta_in); 4: deferred beta update + gather of (z^k + beta^k) (PALM's first q-step)
 // [z0, z0 + zcount) = the chunks to launch (zcount < 0: all from z0 on); chunks are independent of each other
+// flavour (mode 1 only): CONE_GIN -- beta_in holds gamma^{k-1} = beta^{k-1} + tau z^k, q_old is not read;
+// CONE_GOUT -- beta_out receives gamma^k = beta^k + tau z^{k+1} instead of beta^k
+enum { CONE_GIN = 1, CONE_GOUT = 2 };
 int launch_cone_fused(int mode, const Grid &g, const LoopCoef &c, const FusedGeom &fg, FusedArgs a,
-                      hipStream_t st, i64 z0 = 0, i64 zcount = -1);
+                      hipStream_t st, i64 z0 = 0, i64 zcount = -1, int flavour = 0);
 // time-slab mode: split every slab's cone pass into >= 2 chunks so that the chunks in front of the last one --
 // which alone reads the q halo -- can start before the halo has arrived
 bool cone_split_enabled();
@@ -160,6 +163,7 @@ struct QStepExtra {
     double *partials, *resid;
     double kappa, dsD;       // KktCoef
     double *u0_tail;         // time slabs: w.*q0^+ - alpha0^+ of the last owned cell layer goes here too (the right slab's rhs)
+    int c_ends;              // c is zero off the two global end layers: they alone are loaded
 };
 int launch_qstep_rhs(const Grid &g, const LoopCoef &c, const FusedGeom &fg, const double *phi, const double *q2,
                      const double *sx, const double *sy, const double *weight, const double *tail_bx,
@@ -168,7 +172,12 @@ int launch_qstep_rhs(const Grid &g, const LoopCoef &c, const FusedGeom &fg, cons
                      const QStepExtra *ex = nullptr);
 i64 qstep_rhs_blocks(const Grid &g, const FusedGeom &fg);
 // rhs <- (rhs + r) - r / factor, c <- c / factor  (sigma update without a new pass over q and alpha)
-int launch_rhs_sigma_fix(double *rhs, const double *r, double *cvec, i64 n, double factor, hipStream_t st);
+// (c_ends: c is zero off the two global end layers, which alone are divided)
+int launch_rhs_sigma_fix(const Grid &g, double *rhs, const double *r, double *cvec, double factor, hipStream_t st,
+                         bool c_ends = false);
+// *flag (device, cleared by the caller) |= 1 unless every layer of the slab's c except global layer 0 and nt - 1 is
+// all-zero bits
+int launch_c_interior_test(const Grid &g, const double *cvec, int *flag, hipStream_t st);
 // chunks of time layers of that launch (z0 + i * zstride, i < zcount, selects chunks; chunks are independent of each other: only
 // chunk 0 reads the adjoint tails of the left neighbour slab and only the last one the phi halo of the right one -- and
 // writes the u0 tail)
@@ -195,7 +204,7 @@ int launch_kkt_tail(const Grid &g, const double *alpha, const double *beta, cons
                     double *a0w, double *bt_bx, double *bt_by, hipStream_t st);
 // rhs = A'(w.*q - alpha) + c   (solver_socp_inPALM.m:194, solver_wsocp_inPALM.m:200)
 int launch_rhs(const Grid &g, const LoopCoef &c, const double *q, const double *alpha, const double *cvec,
-               const double *weight, const double *u0_prev, double *rhs, hipStream_t st);
+               const double *weight, const double *u0_prev, double *rhs, hipStream_t st, bool c_ends = false);
 // q-step + alpha update (solver_socp_inPALM.m:204-206,211,214; solver_wsocp_inPALM.m:210-217)
 int launch_qstep(const Grid &g, const LoopCoef &c, const double *phi, const double *z, const double *beta,
                  const double *weight, const double *tail_bx, const double *tail_by, double *q,

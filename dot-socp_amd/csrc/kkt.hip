@@ -277,7 +277,7 @@ __global__ void __launch_bounds__(TILE_Y *TILE_X) k_kkt_cells(Grid g, LoopCoef c
 #pragma unroll
                 for (int j = 0; j < 10; ++j) {
                     const double r = zo[j] - v[j];
-                    b[j] = b[j] + c.tau * r;
+                    b[j] = mult_finish(mult_carry(b[j], zo[j], c.tau), v[j], c.tau);
                     zs += zo[j] * zo[j];
                     bs += b[j] * b[j];
                     rs += r * r;

@@ -77,6 +77,7 @@ struct Slab {
     double *z = nullptr;        // 10 * Nz
     double *beta = nullptr;     // 10 * Nz
     double *c = nullptr;        // Nphi
+    bool c_ends = false;        // every layer of c but global layer 0 and nt - 1 is all-zero bits (Solver::detect_c_ends, at begin())
     double *weight = nullptr;   // NqAlloc (weighted only)
     double *w0 = nullptr, *w1 = nullptr;   // Poisson work arrays (slab layout)
     // Poisson t-axis: this slab's pencil = columns [l0, l0+nl) of the ny*nx (y, x) columns, all nt nodes
@@ -111,7 +112,17 @@ struct Slab {
 bool if_adjust_sigma(double iter, double last_iter);   // IfAdjustSigma (solver_socp_inPALM.m:361-379)
 
 enum Phase { PH_RHS = 0, PH_POISSON, PH_PROJ, PH_QSTEP, PH_BETA, PH_KKT, PH_FUSED_A, PH_FUSED_B, PH_MATERIALISE,
-             PH_COMM, PH_INTERP, PH_ACC_CONE, PH_ACC_GATHER, PH_QSTEP0, PH_TRANSPOSE, PH_COUNT };
+             PH_COMM, PH_INTERP, PH_ACC_CONE, PH_ACC_GATHER, PH_QSTEP0, PH_TRANSPOSE, PH_CONE_CARRY, PH_COUNT };
+
+// The schedule of the gamma form (fused.hip, Solver::step): pure host arithmetic, also behind the C ABI.
+// rescale_due: the rescale block of iteration `it` takes its norms or rescales (solver_socp_inPALM.m:138-151), given the
+// state it finds -- it reads beta.
+bool rescale_due(i64 it, int rescale, double maxFeas, double relGap);
+// The cone pass of iteration `it` must leave beta (not gamma) behind: the iteration ends in a KKT check, ends the run()
+// call, or the next iteration's rescale block reads beta.  (maxFeas / relGap change at KKT checks only, so the present
+// values are the ones iteration it + 1 will see whenever this iteration has no check.)
+bool cone_writes_beta(i64 it, double lastSigmaIt, i64 maxit, bool checkStepByStep, bool last_of_run, int rescale,
+                      double maxFeas, double relGap);
 
 struct Solver {
     dotsocp_problem prob{};
@@ -194,6 +205,20 @@ struct Solver {
     bool z_valid = true;     // s.z holds the z of the last completed iteration
     bool z_prev_ok = false;  // s.beta2 / s.q_old still hold (beta^k, q^k): z can be regenerated (MODE_Z)
     int ensure_z();
+    // The gamma form.  Between two plain iterations the cone pass stores gamma^k = beta^k + tau z^{k+1} where it would
+    // store beta^k; the next pass forms beta^{k+1} = gamma^k - tau (BF q^{k+1} + d) from the q it reads anyway -- no q_old,
+    // no second projection.  Every other reader of beta or z needs the beta form: an iteration known (at its start) to be
+    // followed by one writes beta (cone_writes_beta).
+    bool cone_carry = true;      // DOTSOCP_CONE_CARRY=0: every deferred pass reads and writes beta
+    bool beta_gamma = false;     // s.beta holds gamma (deferred only)
+    bool cone_gout = false;      // this iteration's pass writes gamma (set by step())
+    bool last_of_run = false;    // this iteration is the last of its run() call (set by run())
+    i64 timeout_at = -1;         // DOTSOCP_TEST_TIMEOUT_AT (test hook): the time limit counts as passed from this iteration on
+    bool timeout_pending = false;   // the time limit passed in an iteration that wrote gamma: the next one checks and stops
+    int need_beta_form(const char *who) const;
+    // c is zero off its two end layers (model.c of initialize.m:42-50): the q-step, k_rhs and the sigma fix skip the rest
+    bool c_ends_on = true;       // DOTSOCP_C_ENDS=0: load all of c
+    int detect_c_ends();
     // fused path: a scaling of beta that the next pass over beta applies on load (saves a 20 Nz pass)
     int bpend = 0;           // pending operations on beta: 0, 1 or 2 (x * bmul / bdiv, then x * bmul2 / bdiv2)
     double bmul = 1.0, bdiv = 1.0, bmul2 = 1.0, bdiv2 = 1.0;

@@ -1053,6 +1053,25 @@ int Solver::upload(int field, const double *host) {
     return copy_field(*this, field, const_cast<double *>(host), true);
 }
 
+// model.c of initialize.m:42-50 is zero except on its first and last time layer, and every operation of the loop on c
+// (x * mul / div with positive factors) keeps a +0.0 what it is.  One reduction per slab at begin(), when every upload
+// of c is over (upload() after begin() is refused); a c that was never uploaded is the zeros of its allocation and passes.
+int Solver::detect_c_ends() {
+    FOR_SLABS(s) {
+        int *flag = nullptr, h = 1;
+        DS_CHECK(dmalloc(&flag, 1));
+        int rc = 0;
+        if (ds_memset_async(flag, 0, sizeof(int), s.st) != hipSuccess) rc = DOTSOCP_EHIP;
+        if (!rc) rc = launch_c_interior_test(s.g, s.c, flag, s.st);
+        if (!rc && ds_memcpy_async(&h, flag, sizeof(int), hipMemcpyDeviceToHost, s.st) != hipSuccess) rc = DOTSOCP_EHIP;
+        if (!rc && ds_stream_synchronize(s.st) != hipSuccess) rc = DOTSOCP_EHIP;
+        dfree(flag);
+        if (rc) { if (rc == DOTSOCP_EHIP) set_error("the zero test of c failed"); return rc; }
+        s.c_ends = (h == 0);
+    }
+    return 0;
+}
+
 // time layers [t0, t0 + n) of a node field (phi, c) from a host buffer that holds only those layers; the other layers
 // keep what they have (zeros after create).  model.c of initialize.m:42-50 is zero except for its first and last layer:
 // a driver uploads those two instead of a vector as long as the grid (1 GB at 1025 x 1025 x 129).
@@ -1087,6 +1106,7 @@ int Solver::download(int field, double *host) {
     DS_CHECK(use_dev(device));
     DS_CHECK(ensure_alloc());
     if (field == DOTSOCP_F_Z || field == DOTSOCP_F_BETA) {
+        DS_CHECK(need_beta_form("download"));
         DS_CHECK(ensure_z());
         DS_CHECK(flush_beta());
     }
@@ -1168,7 +1188,15 @@ void Solver::update_coef() {
     lc.dinv2 = 1.0 / lc.c2;
 }
 
+// Every reader of beta other than a CONE_GIN pass: by the schedule of step() none ever meets gamma
+int Solver::need_beta_form(const char *who) const {
+    if (!beta_gamma) return 0;
+    set_error("internal: %s met the gamma form of beta", who);
+    return DOTSOCP_ESTATE;
+}
+
 int Solver::flush_beta() {
+    DS_CHECK(need_beta_form("flush_beta"));
     if (!bpend) return 0;
     FOR_SLABS(s) {
         DS_CHECK(launch_scale(s.beta, 10 * s.g.Nc, bmul, bdiv, s.st));
@@ -1210,11 +1238,12 @@ int Solver::sigma_scale_folded(double factor) {
         apend = true; amul = 1.0; adiv = factor;
     }
     u0_fresh = false;
-    FOR_SLABS(s) DS_CHECK(launch_rhs_sigma_fix(s.w0, s.w1, s.c, s.g.Nphi, factor, s.st));
+    FOR_SLABS(s) DS_CHECK(launch_rhs_sigma_fix(s.g, s.w0, s.w1, s.c, factor, s.st, c_ends_on && s.c_ends));
     return 0;
 }
 
 int Solver::scale_state(double a_mul, double a_div, double q_div, bool with_c) {
+    DS_CHECK(need_beta_form("scale_state"));
     DS_CHECK(flush_alpha());
     if (begun) DS_CHECK(ensure_halo());
     u0_made = false;
@@ -1266,6 +1295,19 @@ int Solver::begin(const dotsocp_opts *o) {
         fused = false;       // z is a stored state variable of this loop: the generic helpers take their "z in memory" paths
     }
     opts = *o;
+    cone_carry = true;
+    if (const char *e = getenv("DOTSOCP_CONE_CARRY")) cone_carry = (atoi(e) != 0);     // read per begin(), like the others
+    c_ends_on = true;
+    if (const char *e = getenv("DOTSOCP_C_ENDS")) c_ends_on = (atoi(e) != 0);
+    if (c_ends_on) DS_CHECK(detect_c_ends());
+    // test hook: the time limit counts as passed from this iteration on (tests/test_gpu_cone_carry.py takes the
+    // "time limit in a gamma iteration" branch of step() at a chosen iteration instead of at a wall-clock moment)
+    timeout_at = -1;
+    if (const char *e = getenv("DOTSOCP_TEST_TIMEOUT_AT")) timeout_at = atoll(e);
+    beta_gamma = false;
+    cone_gout = false;
+    last_of_run = false;
+    timeout_pending = false;
     checkPrimDualFeas = (o->checkPrimDualFeas < 0) ? !prob.weighted : (o->checkPrimDualFeas != 0);   // :20-24 / wsocp :25-29
     time_limit = (o->time_limit > 0) ? o->time_limit : 3600.0;                                        // :26-30
     sigma = o->sigma;
@@ -1374,7 +1416,7 @@ int Solver::phase_phi(const PhiHooks *hooks) {
     prof_begin(PH_RHS);
     if (!rhs_valid) {
         DS_CHECK(flush_alpha());
-        FOR_SLABS(s) DS_CHECK(launch_rhs(s.g, lc, s.q, s.alpha, s.c, s.weight, s.u0_prev, s.w0, s.st));
+        FOR_SLABS(s) DS_CHECK(launch_rhs(s.g, lc, s.q, s.alpha, s.c, s.weight, s.u0_prev, s.w0, s.st, c_ends_on && s.c_ends));
     } else if (multi()) {
         // the q-step left rhs in w0; its first layer still lacks the left neighbour's last cell
         FOR_SLABS(s)
@@ -1400,7 +1442,15 @@ int Solver::phase_z(int part) {
         prof_end(PH_PROJ);
         return 0;
     }
-    const int ph = deferred ? PH_FUSED_B : PH_FUSED_A;
+    // flavour of the deferred pass (kernels.h): reads gamma if the last pass left it, writes what step() scheduled.  The
+    // passes that do not read q_old move fewer bytes and are timed as a phase of their own.
+    const bool gin = beta_gamma, gout = deferred && cone_gout;
+    if (gin && (!deferred || bpend)) {
+        set_error("internal: gamma form %s", deferred ? "with a pending scaling of beta" : "without a pending multiplier step");
+        return DOTSOCP_ESTATE;
+    }
+    const int flavour = (gin ? CONE_GIN : 0) | (gout ? CONE_GOUT : 0);
+    const int ph = deferred ? (gin ? PH_CONE_CARRY : PH_FUSED_B) : PH_FUSED_A;
     z_valid = false;          // the fused pass forms z^{k+1} in registers only
     z_prev_ok = false;        // ... and (mode B) overwrites the kept beta^{k-1}
     prof_begin(ph);
@@ -1425,16 +1475,19 @@ int Solver::phase_z(int part) {
             for (i64 z = z0; z < z0 + zc; ++z) {
                 a.carry_in = (z > 0) ? s.carry : nullptr;
                 a.carry_out = (z + 1 < C) ? s.carry : nullptr;
-                DS_CHECK(launch_cone_fused(mode, s.g, lc, s.fg, a, s.st, z, 1));
+                DS_CHECK(launch_cone_fused(mode, s.g, lc, s.fg, a, s.st, z, 1, flavour));
             }
         } else {
-            DS_CHECK(launch_cone_fused(mode, s.g, lc, s.fg, a, s.st, z0, zc));
+            DS_CHECK(launch_cone_fused(mode, s.g, lc, s.fg, a, s.st, z0, zc, flavour));
         }
         if (deferred && part != 1) std::swap(s.beta, s.beta2);
     }
     prof_end(ph);
     if (part == 1) return 0;
-    if (deferred) bpend = 0;          // mode B rewrote beta with the scaling applied
+    if (deferred) {
+        bpend = 0;                    // mode B rewrote beta with the scaling applied
+        beta_gamma = gout;
+    }
     return 0;
 }
 
@@ -1509,6 +1562,7 @@ int Solver::phase_q(int part, bool kkt) {
                 else if (part == 2) { z0 = C - 1; zc = 1; }        // the last chunk
                 QStepExtra ex{};
                 ex.apend = apend ? 1 : 0; ex.amul = amul; ex.adiv = adiv;
+                ex.c_ends = (c_ends_on && s.c_ends) ? 1 : 0;
                 if (multi() && !s.g.last && part != 1) ex.u0_tail = s.send_plane;
                 if (kkt) {
                     const KktCoef k = kkt_coef();
@@ -1552,6 +1606,7 @@ int Solver::phase_mult() {
 // 212-215) so that beta, z are the iterates the KKT block, the rescale block and the outputs see.
 int Solver::materialise() {
     if (!fused || !deferred) return 0;
+    DS_CHECK(need_beta_form("materialise"));
     DS_CHECK(ensure_halo());
     prof_begin(PH_MATERIALISE);
     FOR_SLABS(s) {
@@ -1574,6 +1629,7 @@ int Solver::materialise() {
 // z of the last completed iteration in s.z (outputs, rescale block, unfused-style cell sums)
 int Solver::ensure_z() {
     if (!fused || z_valid) return 0;
+    DS_CHECK(need_beta_form("ensure_z"));
     if (deferred) return materialise();
     if (!z_prev_ok) {
         set_error("internal: z cannot be regenerated");
@@ -1599,6 +1655,7 @@ int Solver::ensure_z() {
 // folded: this iteration's q-step ran in its KKT variant (phase_q(.., true)): region 0 of the partial sums holds its
 // share, the cell pass adds the F*B*beta terms of the edges, and no node / edge launch follows
 int Solver::kkt_sums(double *S, bool folded) {
+    DS_CHECK(need_beta_form("kkt_sums"));
     DS_CHECK(ensure_halo());
     const KktCoef k = kkt_coef();
     if (method == DOTSOCP_METHOD_ACCADMM && folded) {
@@ -1705,6 +1762,7 @@ int Solver::reduce_sums(double *S) {
 // The five norms of solver_socp_inPALM.m:140-141 for an iterate whose multiplier step is still pending (the state between
 // two iterations of the fused loop): one pass over beta that stores nothing, three sums of squares.  S as from kkt_sums().
 int Solver::norms_light(double *S) {
+    DS_CHECK(need_beta_form("norms_light"));
     DS_CHECK(ensure_halo());
     DS_CHECK(flush_alpha());
     const KktCoef k = kkt_coef();
@@ -1747,6 +1805,7 @@ int Solver::rescale_block() {
         nAlps = std::max(normAlpha, normBeta);
         return 0;
     };
+    if (rescale_due(it, rescale, maxFeas, relGap)) DS_CHECK(need_beta_form("rescale_block"));
     if (rescale >= 3 && (it % 100) == 0) {
         DS_CHECK(norms(normPhis, normAlps));
         const double ratio = std::max(normAlps, normPhis) / std::min(normAlps, normPhis);
@@ -1775,6 +1834,20 @@ int Solver::rescale_block() {
     update_coef();                                       // scaleD = E / dScale (:183); z2 is regenerated on the fly
     rescale += 1;
     return 0;
+}
+
+bool rescale_due(i64 it, int rescale, double maxFeas, double relGap) {
+    if (rescale >= 3 && (it % 100) == 0) return true;                                   // :139-146, the norm check
+    if (rescale == 1 && maxFeas < 2e-2 && it >= 10 && relGap < 5e-2) return true;       // :148
+    if (rescale == 2 && maxFeas < 5e-3 && it >= 50 && relGap < 1e-2) return true;       // :149
+    return false;
+}
+
+bool cone_writes_beta(i64 it, double lastSigmaIt, i64 maxit, bool checkStepByStep, bool last_of_run, int rescale,
+                      double maxFeas, double relGap) {
+    if (checkStepByStep || if_adjust_sigma((double)it, lastSigmaIt) || it >= maxit) return true;   // ends in a KKT check
+    if (last_of_run) return true;                                                                  // the caller may read anything
+    return rescale_due(it + 1, rescale, maxFeas, relGap);
 }
 
 bool if_adjust_sigma(double iter, double last_iter) {   // :361-379
@@ -1892,7 +1965,12 @@ int Solver::step(bool *brk) {
     DS_CHECK(rescale_block());
     const bool adjustSigmaYes = if_adjust_sigma((double)it, lastSigmaIt);                  // :220
     // known before the q-step (the time limit is the one trigger that is not: such a check takes the unfolded path)
-    const bool kkt_due = opts.ifCheckStepByStep || adjustSigmaYes || it == opts.maxit;
+    // ... and a time limit that passed in an iteration which left gamma behind: this one checks (folded) and stops
+    const bool kkt_due = opts.ifCheckStepByStep || adjustSigmaYes || it == opts.maxit || timeout_pending;
+    // what this iteration's cone pass leaves in s.beta (solver.h: the gamma form)
+    // (cone_writes_beta covers every term of kkt_due but timeout_pending, which only step() knows: hence !kkt_due)
+    cone_gout = cone_carry && fused && deferred && !kkt_due &&
+                !cone_writes_beta(it, lastSigmaIt, opts.maxit, opts.ifCheckStepByStep != 0, last_of_run, rescale, maxFeas, relGap);
     // fused dataflow: the q-step of a checking iteration accumulates its share of the KKT sums itself
     const bool fold = kkt_due && kkt_fold && fused && qrhs;
     // Time slabs, messages on the second streams (solver.h: comm_z): kernels on the main streams in an order that leaves
@@ -1955,7 +2033,13 @@ int Solver::step(bool *brk) {
     }
     DS_CHECK(phase_mult());
     // with one slab per process a per-rank clock could split the ranks: see kkt_block()
-    const bool timed_out = remote() ? false : (elapsed() > time_limit);
+    const bool timed_out = timeout_pending || (remote() ? false : (elapsed() > time_limit || (timeout_at > 0 && it >= timeout_at)));
+    timeout_pending = false;
+    if (timed_out && beta_gamma) {
+        // the unscheduled check would read beta: it is taken at the end of the next iteration, which writes beta
+        timeout_pending = true;
+        return 0;
+    }
     if (kkt_due || timed_out)                                                             // :221
         DS_CHECK(kkt_block(adjustSigmaYes, timed_out, brk, fold));
     return 0;
@@ -1977,10 +2061,12 @@ int Solver::run(i64 n_iters, i64 *done) {
     while (it < opts.maxit && !stopped) {
         if (n_iters >= 0 && n >= n_iters) break;
         bool brk = false;
+        last_of_run = (n_iters >= 0 && n + 1 >= n_iters);
         DS_CHECK(step(&brk));
         if (brk) stopped = true;
         ++n;
     }
+    DS_CHECK(need_beta_form("the end of run()"));
     DS_CHECK(ensure_halo());          // callers between run() calls see exchanged halos
     DS_CHECK(sync_all());
     DS_CHECK(prof_flush());
@@ -2019,7 +2105,7 @@ int Solver::finish(dotsocp_result *res) {
         res->dScale = dScale;
         // device time per step (HIP events) when profiling is on; Total_Time is host wall time
         res->times[0] = (phase_ms[PH_RHS] + phase_ms[PH_POISSON]) * 1e-3;
-        res->times[1] = (phase_ms[PH_PROJ] + phase_ms[PH_FUSED_A] + phase_ms[PH_FUSED_B]) * 1e-3;
+        res->times[1] = (phase_ms[PH_PROJ] + phase_ms[PH_FUSED_A] + phase_ms[PH_FUSED_B] + phase_ms[PH_CONE_CARRY]) * 1e-3;
         res->times[2] = phase_ms[PH_QSTEP] * 1e-3;
         res->times[3] = (phase_ms[PH_BETA] + phase_ms[PH_MATERIALISE]) * 1e-3;
         res->times[4] = phase_ms[PH_KKT] * 1e-3;

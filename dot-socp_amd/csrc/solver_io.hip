@@ -14,6 +14,7 @@ namespace dotsocp {
 int Solver::recover_outputs(const double *rho0, const double *rho1, double *rho, double *Ex, double *Ey, double *q0,
                             double *bx, double *by) {
     if (!finished) { set_error("recover_outputs() needs finish()"); return DOTSOCP_ESTATE; }
+    DS_CHECK(need_beta_form("recover_outputs"));
     DS_ARG(rho == nullptr || (rho0 != nullptr && rho1 != nullptr), "rho needs rho0 and rho1");
     cur_dev = -1;
     DS_CHECK(use_dev(device));

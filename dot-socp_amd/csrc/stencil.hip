@@ -28,9 +28,9 @@ __global__ void __launch_bounds__(TILE_Y *TILE_X) k_rhs(RhsArgs a, double *__res
 }
 
 int launch_rhs(const Grid &g, const LoopCoef &c, const double *q, const double *alpha, const double *cvec,
-               const double *weight, const double *u0_prev, double *rhs, hipStream_t st) {
+               const double *weight, const double *u0_prev, double *rhs, hipStream_t st, bool c_ends) {
     if (g.Nphi <= 0) return 0;
-    RhsArgs a{g, c.at, c.ax, c.ay, q, alpha, cvec, weight, u0_prev};
+    RhsArgs a{g, c.at, c.ax, c.ay, q, alpha, cvec, weight, u0_prev, c_ends ? 1 : 0};
     if (weight)
         DS_KLAUNCH(k_rhs<true>, tile_grid(g, g.ntl), dim3(TILE_Y, TILE_X), 0, st, a, rhs);
     else
@@ -388,6 +388,7 @@ struct QRhsArgs {
     // KKT variant (VAR 0, single slab): per-workgroup partial sums, r = A' alpha^+ - c per node, DOT complementarity scalars
     double *partials, *resid;
     double kappa, dsD;
+    int c_ends;        // c is zero off the two global end layers (Slab::c_ends): the steps on other layers take cv = 0
 };
 
 // VAR 0: inPALM / ALG2; 1: acc-ADMM multiplier arithmetic, raw outputs; 2: acc-ADMM with the Halpern step of q and
@@ -527,7 +528,10 @@ __global__ void __launch_bounds__(TILE_Y *QTX, (QTX > TILE_X && !WEIGHTED ? 4 : 
         double k0v = 0.0, kXv = 0.0, kYv = 0.0;
         const bool pcorr = (VAR == 3) && (a.qk != nullptr);
         if (pcorr) { k0v = a.qk[k0]; kXv = a.qk[eX]; kYv = a.qk[eY]; }
-        const double cv = a.cvec[node];
+        // c of an interior layer is known to be zero: no load (the condition is uniform over the workgroup; cv keeps all
+        // its uses below, so the results are those of loading the zero)
+        double cv = 0.0;
+        if (!a.c_ends || tbnd) cv = a.cvec[node];
         double w0 = 1.0, wX = 1.0, wY = 1.0;
         if (WEIGHTED) { w0 = a.weight[k0]; wX = a.weight[eX]; wY = a.weight[eY]; }
         const double sxv = a.sx[sxOwn ? (tl * fg.nxblk + (x / fg.XB + 1)) * g.ny + y : 0];
@@ -769,6 +773,7 @@ int launch_qstep_rhs(const Grid &g, const LoopCoef &c, const FusedGeom &fg, cons
         a.u0_tail = ex->u0_tail;
         a.kappa = ex->kappa;
         a.dsD = ex->dsD;
+        a.c_ends = ex->c_ends;
     }
     return launch_qstep_rhs_var(0, g, c, fg, a, st, z0, zcount, zstride);
 }
@@ -779,18 +784,48 @@ i64 qstep_rhs_blocks(const Grid &g, const FusedGeom &fg) { return fg.nyblk * fg.
 // After a sigma update (alpha, c <- / factor, solver_socp_inPALM.m:312-314) the right-hand side A'(w.*q - alpha) + c the
 // q-step left behind becomes  A'(w.*q) - (A' alpha - c) / factor = (rhs + r) - r / factor  with the r = A' alpha - c the
 // KKT variant of the q-step stored; c is divided on the way (alpha stays pending: APend).
+// c is divided in [0, c_lo) and [c_hi, n) only: everything (c_lo = n), or the end layers a slab holds when the rest of c is
+// known to be zero (Slab::c_ends).
 __global__ void __launch_bounds__(256) k_rhs_sigma_fix(double *__restrict__ rhs, const double *__restrict__ r,
-                                                        double *__restrict__ cvec, i64 n, double factor) {
+                                                        double *__restrict__ cvec, i64 n, double factor, i64 c_lo, i64 c_hi) {
     for (i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (i64)gridDim.x * blockDim.x) {
         const double rv = r[i];
         rhs[i] = (rhs[i] + rv) - rv / factor;
-        cvec[i] = cvec[i] / factor;
+        if (i < c_lo || i >= c_hi) cvec[i] = cvec[i] / factor;
     }
 }
 
-int launch_rhs_sigma_fix(double *rhs, const double *r, double *cvec, i64 n, double factor, hipStream_t st) {
+// the index range of c that holds no global end layer: [c_lo, c_hi)
+static inline void c_interior(const Grid &g, i64 &c_lo, i64 &c_hi) {
+    c_lo = g.first ? g.plane : 0;
+    c_hi = g.last ? g.Nphi - g.plane : g.Nphi;
+    if (c_hi < c_lo) c_hi = c_lo;
+}
+
+int launch_rhs_sigma_fix(const Grid &g, double *rhs, const double *r, double *cvec, double factor, hipStream_t st,
+                         bool c_ends) {
+    const i64 n = g.Nphi;
     if (n <= 0) return 0;
-    DS_KLAUNCH(k_rhs_sigma_fix, dim3(launch_blocks(n, 256, 1 << 22)), dim3(256), 0, st, rhs, r, cvec, n, factor);
+    i64 c_lo = n, c_hi = n;
+    if (c_ends) c_interior(g, c_lo, c_hi);
+    DS_KLAUNCH(k_rhs_sigma_fix, dim3(launch_blocks(n, 256, 1 << 22)), dim3(256), 0, st, rhs, r, cvec, n, factor, c_lo, c_hi);
+    DS_HIP(hipGetLastError());
+    return 0;
+}
+
+// *flag |= 1 if any double of c[lo, hi) is not the all-zero bit pattern (a -0.0 counts as non-zero)
+__global__ void __launch_bounds__(256) k_any_nonzero_bits(const double *__restrict__ c, i64 lo, i64 hi, int *flag) {
+    bool any = false;
+    for (i64 i = lo + (i64)blockIdx.x * blockDim.x + threadIdx.x; i < hi; i += (i64)gridDim.x * blockDim.x)
+        any = any || (__double_as_longlong(c[i]) != 0);
+    if (any) atomicOr(flag, 1);
+}
+
+int launch_c_interior_test(const Grid &g, const double *cvec, int *flag, hipStream_t st) {
+    i64 lo, hi;
+    c_interior(g, lo, hi);
+    if (hi <= lo) return 0;
+    DS_KLAUNCH(k_any_nonzero_bits, dim3(launch_blocks(hi - lo, 256, 1 << 14)), dim3(256), 0, st, cvec, lo, hi, flag);
     DS_HIP(hipGetLastError());
     return 0;
 }

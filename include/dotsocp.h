@@ -214,6 +214,17 @@ dotsocp_i64 dotsocp_field_len(const dotsocp_problem *prob, int field);
  * 4 Bluestein (other lengths up to 1024), 5 dense DCT-matrix product. */
 int dotsocp_dct_algorithm(dotsocp_i64 n);
 
+/* The schedule of the cone pass's gamma form (pure host arithmetic, no device).  Between two plain inPALM iterations
+ * the cone pass leaves gamma = beta + tau z in the multiplier array instead of beta; only the next cone pass can read
+ * that.  dotsocp_cone_writes_beta: 1 if the pass of iteration `it` must leave beta -- the iteration ends in a KKT check
+ * (ifCheckStepByStep, the IfAdjustSigma cadence of solver_socp_inPALM.m:361-379 counted from `last_sigma_it`, it ==
+ * maxit), is the last of its run() call, or the rescale block of iteration it + 1 will read the state -- else 0.
+ * dotsocp_rescale_due: 1 if the rescale block of iteration `it` (:138-151) takes its norms or rescales, given the loop
+ * state it finds (`rescale` = the counter of :64-68, maxFeas / relGap of the last KKT check). */
+int dotsocp_cone_writes_beta(dotsocp_i64 it, double last_sigma_it, dotsocp_i64 maxit, int check_step_by_step,
+                             int last_of_run, int rescale, double maxFeas, double relGap);
+int dotsocp_rescale_due(dotsocp_i64 it, int rescale, double maxFeas, double relGap);
+
 int dotsocp_upload(dotsocp_ctx *ctx, int field, const double *host);
 int dotsocp_download(dotsocp_ctx *ctx, int field, double *host);
 /* Extension for drivers: time layers [t0, t0 + n) of a NODE field (DOTSOCP_F_PHI, DOTSOCP_F_C) from a host buffer that
@@ -265,7 +276,8 @@ int dotsocp_get_history(dotsocp_ctx *ctx, double *kkt, double *time, double *ite
  * between two run() calls to cover only what follows (bench.py switches it on after its warm-up iterations).
  * dotsocp_kernel_time: average device time in ms of the named kernel family over the profiled launches since
  * begin(), and their count; names: "rhs", "poisson", "cone_proj", "qstep", "beta", "kkt", "cone_fused_a",
- * "cone_fused_b", "materialise", "comm", "interp", "acc_cone", "acc_gather", "qstep_first", "transpose". */
+ * "cone_fused_b", "materialise", "comm", "interp", "acc_cone", "acc_gather", "qstep_first", "transpose", "cone_carry"
+ * (the cone passes that read gamma and no q^{k-1}; "cone_fused_b" keeps the passes that move 8 (20 Nz + 3 Nq) bytes). */
 int dotsocp_set_profiling(dotsocp_ctx *ctx, int on);
 int dotsocp_kernel_time(dotsocp_ctx *ctx, const char *name, double *avg_ms, dotsocp_i64 *launches);
 

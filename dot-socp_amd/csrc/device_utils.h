@@ -1,6 +1,7 @@
 // Device-side helpers shared by cone.hip, stencil.hip and kkt.hip.
 #pragma once
 #include "common.h"
+#include "kernels.h"
 
 namespace dotsocp {
 
@@ -52,6 +53,19 @@ __device__ __forceinline__ void glds16(const void *gsrc, unsigned lds_dst) {
 // no effect, measured; its loads of neighbour tiles' entries rely on the L2.  The pipelined DCT kernels with `nt` on
 // their LDS-DMA loads and stores: 2.50 -> 2.60 ms at 1024-point lines, 3.1 -> 5.3 ms at 2048 -- tiles narrower than a
 // 128-byte line share every line with a neighbour workgroup.)
+// a row of cone entries as loaded from an array with a pending scaling (kernels.h: ScaleOps), with k_scale's arithmetic
+// (the ops BY VALUE: through a reference to the kernel argument the compiler schedules the callers differently)
+__device__ __forceinline__ void apply_scale_ops(double (&b)[10], const ScaleOps o) {
+    if (o.n) {
+#pragma unroll
+        for (int j = 0; j < 10; ++j) b[j] = b[j] * o.mul / o.div;
+        if (o.n > 1) {
+#pragma unroll
+            for (int j = 0; j < 10; ++j) b[j] = b[j] * o.mul2 / o.div2;
+        }
+    }
+}
+
 template <bool NT>
 __device__ __forceinline__ double ld_stream(const double *p) { return NT ? __builtin_nontemporal_load(p) : *p; }
 template <bool NT>

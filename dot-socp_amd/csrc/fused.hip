@@ -88,14 +88,7 @@ __global__ void __launch_bounds__(64 * XB) k_cone_fused(Grid g, LoopCoef c, Fuse
             double b[10], v[10];
 #pragma unroll
             for (int j = 0; j < 10; ++j) b[j] = ld_stream<NT>(a.beta_in + j * g.Nc + i);
-            if (!GIN && a.bpend) {         // gamma never carries a pending scaling (Solver::phase_z)
-#pragma unroll
-                for (int j = 0; j < 10; ++j) b[j] = b[j] * a.bmul / a.bdiv;
-                if (a.bpend > 1) {
-#pragma unroll
-                    for (int j = 0; j < 10; ++j) b[j] = b[j] * a.bmul2 / a.bdiv2;
-                }
-            }
+            if (!GIN) apply_scale_ops(b, a.bops);      // gamma never carries a pending scaling (Solver::phase_z)
             build_z2(v, a.q[i], cur, nxt, c.s, c.dF);
             if constexpr (GIN) {           // beta_in holds gamma^{k-1} = beta^{k-1} + tau z^k
 #pragma unroll
@@ -232,7 +225,7 @@ int launch_cone_fused(int mode, const Grid &g, const LoopCoef &c, const FusedGeo
         break;
     if (flavour != 0) {          // gamma form: CONE_GIN / CONE_GOUT flavours of mode 1
         if (mode != 1 || (flavour & ~(CONE_GIN | CONE_GOUT))) { set_error("bad fused flavour"); return DOTSOCP_EINVAL; }
-        if ((flavour & CONE_GIN) && a.bpend) { set_error("internal: gamma with a pending scaling"); return DOTSOCP_ESTATE; }
+        if ((flavour & CONE_GIN) && !a.bops.empty()) { set_error("internal: gamma with a pending scaling"); return DOTSOCP_ESTATE; }
 #define CONE_FLAV(GI, GO)                                                                          \
         if (nt) DS_KLAUNCH((k_cone_fused<1, 4, true, GI, GO>), grid, blk, 0, st, g, c, a);         \
         else DS_KLAUNCH((k_cone_fused<1, 4, false, GI, GO>), grid, blk, 0, st, g, c, a);

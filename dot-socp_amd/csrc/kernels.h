@@ -30,6 +30,23 @@ struct KktCoef {
     double dsE;        // dScale / E
 };
 
+// A scaling x <- x * mul / div (then x * mul2 / div2) that is still pending in memory: whoever loads x next applies it with
+// k_scale's arithmetic (device_utils.h: apply_scale_ops) instead of a pass of its own.  Plain data: travels inside kernel
+// arguments (FusedArgs, QStepExtra).
+struct ScaleOps {
+    int n;                  // number of pending operations (0, 1 or 2: a sigma update followed by a rescale)
+    double mul, div;
+    double mul2, div2;      // second pending operation, applied after the first
+    bool empty() const { return n == 0; }
+    void clear() { n = 0; }
+    bool push(double m, double d) {      // false: both slots are taken (flush first)
+        if (n >= 2) return false;
+        if (n == 0) { mul = m; div = d; } else { mul2 = m; div2 = d; }
+        n += 1;
+        return true;
+    }
+};
+
 // ---------------- cone.hip ----------------
 int launch_proj_soc(double *out, const double *in, i64 M, i64 K, hipStream_t st);
 int launch_bfd(const Grid &g, double *z, const double *q, double s, double dF, hipStream_t st);
@@ -68,10 +85,8 @@ struct FusedArgs {
     double *p2, *sxp, *syp; // modes 5, 6: second gather, F*B*((1 + tau) z + beta), layout of q2 / sx / sy
     i64 TC;
     // pending scaling of beta_in (sigma update / rescale block, solver_socp_inPALM.m:176,313), applied on
-    // load exactly like k_scale would have: b = b * bmul / bdiv
-    int bpend;              // number of pending operations (0, 1 or 2: a sigma update followed by a rescale)
-    double bmul, bdiv;
-    double bmul2, bdiv2;    // second pending operation, applied after the first
+    // load exactly like k_scale would have: b = b * mul / div
+    ScaleOps bops;
     int xcd;                // permute the tile order so that y-neighbouring tiles share an XCD (device_utils.h)
     int z0;                 // first chunk of this launch (launch_cone_fused can launch a range of chunks)
     // chunks launched ONE PER LAUNCH in ascending order on one stream (time slabs): the last cell's "t + 1" cone entries
@@ -158,8 +173,7 @@ int launch_qstep_fused(const Grid &g, const LoopCoef &c, const FusedGeom &fg, co
 // slab only -- the KKT variant: the sums of the KKT block that need only phi, q^+, alpha^+, A phi and c are accumulated in
 // the same pass (one row of S_COUNT partial sums per workgroup at `partials`), r = A' alpha^+ - c goes to `resid`
 struct QStepExtra {
-    int apend;
-    double amul, adiv;
+    ScaleOps aops;           // pending scaling of alpha_in (one slot is ever used)
     double *partials, *resid;
     double kappa, dsD;       // KktCoef
     double *u0_tail;         // time slabs: w.*q0^+ - alpha0^+ of the last owned cell layer goes here too (the right slab's rhs)

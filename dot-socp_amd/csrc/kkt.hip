@@ -260,14 +260,7 @@ __global__ void __launch_bounds__(TILE_Y *TILE_X) k_kkt_cells(Grid g, LoopCoef c
                 double v[10], zo[10];
 #pragma unroll
                 for (int j = 0; j < 10; ++j) b[j] = ld_stream<NT>(a.beta_in + j * g.Nc + i);
-                if (a.bpend) {
-#pragma unroll
-                    for (int j = 0; j < 10; ++j) b[j] = b[j] * a.bmul / a.bdiv;
-                    if (a.bpend > 1) {
-#pragma unroll
-                        for (int j = 0; j < 10; ++j) b[j] = b[j] * a.bmul2 / a.bdiv2;
-                    }
-                }
+                apply_scale_ops(b, a.bops);
                 build_z2(v, q0, cur, nxt, c.s, c.dF);
                 build_z2(zo, a.q_old[i], curo, nxto, c.s, c.dF);
 #pragma unroll

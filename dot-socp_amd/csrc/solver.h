@@ -35,12 +35,6 @@ inline int dmalloc(T **p, i64 n) {
     return guarded_malloc((void **)p, sizeof(T) * (size_t)n);
 }
 
-inline int dzalloc(double **p, i64 n, hipStream_t st) {
-    DS_CHECK(dmalloc(p, n));
-    DS_HIP(hipMemsetAsync(*p, 0, sizeof(double) * (size_t)(n > 0 ? n : 1), st));
-    return 0;
-}
-
 inline void dfree(void *p) {
     if (p) guarded_free(p);
 }
@@ -57,20 +51,35 @@ struct DevRes {
 // dotsocp_create: all on one device), its own pair of streams and peer copies between neighbours as
 // "communication"; with an RCCL communicator attached the process holds the single slab `rank` of `world`.
 #define DS_XEV 8
+enum SlabEvent { EV_FORK = 0, EV_JOIN, EV_HALO, EV_CJOIN, EV_TRI, EV_MSG, EV_GOT, EV_X0 };
 struct Slab {
     int index = 0;              // global slab number
     int dev = 0;                // HIP device this slab lives on
     hipStream_t st = nullptr;   // main stream of the slab (slab 0: Solver::stream)
     hipStream_t st_z = nullptr; // second stream: carries the slab's communication in time-slab mode (Solver::comm_z)
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_halo = nullptr;
-    hipEvent_t ev_cjoin = nullptr;        // synchronous communication on the second stream: "done" (Solver::comm_leave)
-    hipEvent_t xev[DS_XEV] = {nullptr};   // ordering of cross-slab copies (Solver::xcopy), used round-robin
-    hipEvent_t ev_tri = nullptr;          // "this slab's interface message is written" (Solver::tri_exchange, slabs of one process)
-    hipEvent_t ev_msg = nullptr, ev_got = nullptr;   // batched neighbour exchanges: "my messages are written" / "I have pulled mine"
+    // the slab's events (created by alloc_slabs, destroyed by free_slabs): fork / join / halo of the second stream; CJOIN:
+    // synchronous communication on it is done (Solver::comm_leave); TRI: this slab's interface message is written
+    // (Solver::tri_exchange); MSG / GOT: batched exchanges, "my messages are written" / "I have pulled mine"; X0 ..: ordering
+    // of cross-slab copies (Solver::xcopy), used round-robin
+    hipEvent_t ev[EV_X0 + DS_XEV] = {nullptr};
     int xev_next = 0;
     DevRes *res = nullptr;      // plans / tables of `dev`
     double *h_sums = nullptr;   // pinned host copy of this slab's KKT partial sums [S_COUNT]
     Grid g;
+    // Every device buffer of the slab is allocated through alloc() / zalloc() and owned by this list, whichever file asks
+    // (alloc_slabs, tri_alloc, palm_begin, acc_alloc); the named pointers below are views that kernels read, loops swap
+    // and nobody frees.  Solver::free_slabs() releases the list.
+    std::vector<void *> owned;
+    template <class T> int alloc(T **p, i64 n) {
+        DS_CHECK(dmalloc(p, n));
+        owned.push_back(*p);
+        return 0;
+    }
+    int zalloc(double **p, i64 n) {     // ... zeroed on the slab's main stream
+        DS_CHECK(alloc(p, n));
+        DS_HIP(hipMemsetAsync(*p, 0, sizeof(double) * (size_t)(n > 0 ? n : 1), st));
+        return 0;
+    }
     double *phi = nullptr;      // NphiAlloc (owned nodes + halo layer)
     double *q = nullptr;        // NqAlloc
     double *alpha = nullptr;    // NqAlloc
@@ -109,6 +118,10 @@ struct Slab {
 // every slab this process holds, with the slab's device made current first (member functions returning int)
 #define FOR_SLABS(s) for (auto &s : slabs) if (int rc_use__ = use(s)) return rc_use__; else
 
+// nodes [t0, t1) of slab `rank`; pencil j of `world`: columns [l0, l1) of the plane's (y, x) columns (solver_slabs.hip)
+int dotsocp_slab_range_impl(i64 nt, int world, int rank, i64 *t0, i64 *t1);
+void pencil_range(i64 plane, int world, int j, i64 *l0, i64 *l1);
+
 bool if_adjust_sigma(double iter, double last_iter);   // IfAdjustSigma (solver_socp_inPALM.m:361-379)
 
 enum Phase { PH_RHS = 0, PH_POISSON, PH_PROJ, PH_QSTEP, PH_BETA, PH_KKT, PH_FUSED_A, PH_FUSED_B, PH_MATERIALISE,
@@ -125,6 +138,7 @@ bool cone_writes_beta(i64 it, double lastSigmaIt, i64 maxit, bool checkStepBySte
                       double maxFeas, double relGap);
 
 struct Solver {
+    // ================ devices, streams, slabs: solver_slabs.hip ================
     dotsocp_problem prob{};
     int device = 0;
     i64 ny = 0, nx = 0, nt = 0;     // internal dims (1-D problems: ny = nx1d, nx = 1)
@@ -132,24 +146,46 @@ struct Solver {
     // carries everything but the overlapped cone pass, and all RCCL communication
     hipStream_t stream = nullptr;
     hipStream_t stream_z = nullptr;    // cone pass when it overlaps the phi step
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_halo = nullptr;
     bool multi_device = false;         // dotsocp_create_multi: slab r on device (device + r) mod #devices
     int ndev_visible = 1;
     std::vector<DevRes *> devres;      // one per device in use
     int cur_dev = -1;                  // device made current by use() (-1: unknown)
+    std::vector<Slab> slabs;        // the slabs held by THIS process
+    // one host thread per slab issues that slab's launches while run() is active (defer.h); null: the caller's thread
+    // issues everything (one slab, one process per GPU, DOTSOCP_HOST_THREADS=0)
+    std::unique_ptr<DeferCtx> defer;
+    int world = 1;                  // total number of slabs
+    int rank = 0;                   // RCCL mode: this process's slab
+    void *nccl = nullptr;           // ncclComm_t when a communicator is attached
+    double *h_sums = nullptr;       // pinned host buffer [S_COUNT + 1] (RCCL mode: reduced sums + clock)
+    double *d_red = nullptr;        // device buffer for the cross-rank reduction [S_COUNT + 1]
+    bool fused = true;       // DOTSOCP_FUSED=0 selects the unfused reference dataflow (z stored, 3 cone passes)
+    bool overlap = false;    // DOTSOCP_OVERLAP=0/1 overrides (default: on in time-slab mode)
+    bool tri_tsolve = true;  // time-slab Poisson solve by partitioned tridiagonal systems (tri.hip); DOTSOCP_TSOLVE=dct:
+                             // slab <-> pencil transposes around the t-axis DCT instead
+    bool peer_ok = true;         // every pair of devices in use can address each other's memory (alloc_slabs)
+    bool cross_device = false;   // some pair of this process's slabs lives on different devices (alloc_slabs)
+    ~Solver();
+    int init(const dotsocp_problem *p, int device, int nslabs, bool multi_dev = false);
+    int attach_rccl(const unsigned char *id, int rank, int world);
     int use(const Slab &s);            // hipSetDevice(s.dev) unless it already is the current one
     int use_dev(int d);
+    int sync_all();                    // host waits for every stream of every slab
     DevRes *res_for(int dev);          // plans + tables on `dev` (created on first request)
+    i64 column_pad() const;
+    i64 row_pitch() const;             // row pitch of this context's device arrays (ny unless the single slab is pitched)
+    int alloc_slabs(int first, int count);
+    int ensure_alloc();
+    void free_slabs();
+    bool multi() const { return world > 1; }
+    bool remote() const { return nccl != nullptr; }
+
+    // ================ messages between slabs: solver_comm.hip ================
     // in-process slabs: dst (on `to`) <- src (on `from`), ordered after everything enqueued so far on both slabs'
     // main streams and before everything enqueued later on either (what one shared stream used to give for free)
     int xcopy(Slab &from, const double *src, Slab &to, double *dst, i64 count);
     int xcopy2d(Slab &from, const double *src, size_t spitch, Slab &to, double *dst, size_t dpitch, size_t width,
                 size_t height);
-    i64 column_pad() const;
-    i64 row_pitch() const;             // row pitch of this context's device arrays (ny unless the single slab is pitched)
-    int sync_all();                    // host waits for every stream of every slab
-    // rows of `rowlen` doubles between a device array with rows `pitch` apart and a host array in the reference layout
-    int copy_rows(double *dev, double *host, i64 rowlen, i64 pitch, i64 nrows, bool up, hipStream_t st);
     // Time slabs: every message between slabs travels on the slab's SECOND stream (RCCL calls, pull launches, peer copies),
     // kernels stay on the main stream.  A communication step is bracketed by comm_enter() / comm_leave(): the second
     // stream first waits for what the main stream holds (fork), and the main stream then waits for the messages (join) --
@@ -165,20 +201,60 @@ struct Solver {
     int comm_enter();
     int comm_leave();
     int comm_fork();                               // second streams wait for the main streams
-    int comm_mark(hipEvent_t Slab::*ev);           // record on the second streams
-    int comm_wait(hipEvent_t Slab::*ev);           // main streams wait
-    bool overlap = false;              // DOTSOCP_OVERLAP=0/1 overrides (default: on in time-slab mode)
-    std::vector<Slab> slabs;        // the slabs held by THIS process
-    // one host thread per slab issues that slab's launches while run() is active (defer.h); null: the caller's thread
-    // issues everything (one slab, one process per GPU, DOTSOCP_HOST_THREADS=0)
-    std::unique_ptr<DeferCtx> defer;
-    int world = 1;                  // total number of slabs
-    int rank = 0;                   // RCCL mode: this process's slab
-    void *nccl = nullptr;           // ncclComm_t when a communicator is attached
+    int comm_mark(SlabEvent ev);                   // record on the second streams
+    int comm_wait(SlabEvent ev);                   // main streams wait
     int open_groups = 0;            // ncclGroupStart calls not yet matched by ncclGroupEnd (comm.h: DS_NCCL_G)
-    double *h_sums = nullptr;       // pinned host buffer [S_COUNT + 1] (RCCL mode: reduced sums + clock)
-    double *d_red = nullptr;        // device buffer for the cross-rank reduction [S_COUNT + 1]
+    // every slab with a neighbour in direction `dir` (+1 right, -1 left) sends `count` doubles
+    // from src(slab) to dst(neighbour)
+    typedef std::function<double *(Slab &)> Sel;
+    int shift(int dir, const Sel &src, const Sel &dst, i64 count);
+    int shift_edge_halo(const Sel &base);      // first owned bx / by layers of base(s) -> halo layer of the left slab
+    int group_begin();
+    int group_end();
+    // slabs of one process: the copies of the shift() calls between group_begin() and group_end() (a lone shift() is a
+    // group of one) are collected and pulled by ONE launch per receiving slab (flush_msgs)
+    struct Msg { int from, to; const double *src; double *dst; i64 count; };
+    std::vector<Msg> msgs;
+    int msg_depth = 0;
+    bool pull_default(const char *env_var) const;
+    bool msg_batching() const;
+    int flush_msgs();
+    // the q halo / u0 tail of the newest iterate have not been exchanged yet: step() issues the exchange behind the
+    // fork so that the cone chunks that do not read the halo overlap it; every other reader calls ensure_halo()
+    bool halo_pending = false;
+    bool u0_fresh = false;   // u0_prev holds w.*q0 - alpha0 of the CURRENT iterate of the left neighbour
+    bool u0_made = false;    // send_plane holds the u0 tail of the current iterate (written by the q-step itself)
+    int make_u0_tail();
+    int exchange_u0_tail();
+    int exchange_q_halo(bool with_u0);
+    int ensure_halo();       // run the q-halo exchange the last q-step left pending (halo_pending)
+    int make_tails();        // time slabs: finalise the adjoint sums of the last owned cell for the right neighbour
+    int send_tails();        // ... adjoint tails -> right
+    int send_phi_head();     // ... first phi layer -> left
+    int ship_tails();        // all three, one group (nothing without time slabs)
+    int transpose(bool forward);
+    // hooks of the asynchronous schedule inside the partitioned t-solve: `fill` runs on the main streams while the first
+    // interface exchange travels, `behind` right after the second one has been issued
+    struct PhiHooks { std::function<int()> fill, behind; };
+    int tri_alloc();
+    int tri_exchange(bool back);
+    int poisson_t_tridiag(const PhiHooks *hooks);
 
+    // ================ host <-> device fields, driver steps on the device: solver_io.hip ================
+    i64 field_len(int field) const;
+    // rows of `rowlen` doubles between a device array with rows `pitch` apart and a host array in the reference layout
+    int copy_rows(double *dev, double *host, i64 rowlen, i64 pitch, i64 nrows, bool up, hipStream_t st);
+    int upload(int field, const double *host);
+    int upload_layers(int field, const double *host, i64 t0, i64 n);
+    int download(int field, double *host);
+    // c is zero off its two end layers (model.c of initialize.m:42-50): the q-step, k_rhs and the sigma fix skip the rest
+    bool c_ends_on = true;       // DOTSOCP_C_ENDS=0: load all of c
+    int detect_c_ends();
+    int recover_outputs(const double *rho0, const double *rho1, double *rho, double *Ex, double *Ey, double *q0,
+                        double *bx, double *by);
+    int jump_from(Solver &coarse);
+
+    // ================ the inPALM loop and its profiling: solver.hip ================
     // ---- loop state (mirrors solver_socp_inPALM.m:11-135) ----
     bool begun = false, finished = false, stopped = false;
     dotsocp_opts opts{};
@@ -197,14 +273,11 @@ struct Solver {
     std::chrono::steady_clock::time_point t_begin;
     double elapsed_prev = 0.0;
     double elapsed_agreed = 0.0;    // multi-process: max over ranks at the last KKT check
-
-    // ---- profiling (HIP events on the launch stream) ----
-    bool profiling = false;
-    bool fused = true;       // DOTSOCP_FUSED=0 selects the unfused reference dataflow (z stored, 3 cone passes)
+    // ---- the fused dataflow: what is pending, what is valid ----
     bool deferred = false;   // fused path: beta still holds beta^{k-1}; z is not materialised
     bool z_valid = true;     // s.z holds the z of the last completed iteration
     bool z_prev_ok = false;  // s.beta2 / s.q_old still hold (beta^k, q^k): z can be regenerated (MODE_Z)
-    int ensure_z();
+    bool rhs_valid = false;  // w0 holds A'(w.*q - alpha) + c of the current iterate (left there by the q-step)
     // The gamma form.  Between two plain iterations the cone pass stores gamma^k = beta^k + tau z^{k+1} where it would
     // store beta^k; the next pass forms beta^{k+1} = gamma^k - tau (BF q^{k+1} + d) from the q it reads anyway -- no q_old,
     // no second projection.  Every other reader of beta or z needs the beta form: an iteration known (at its start) to be
@@ -216,72 +289,41 @@ struct Solver {
     i64 timeout_at = -1;         // DOTSOCP_TEST_TIMEOUT_AT (test hook): the time limit counts as passed from this iteration on
     bool timeout_pending = false;   // the time limit passed in an iteration that wrote gamma: the next one checks and stops
     int need_beta_form(const char *who) const;
-    // c is zero off its two end layers (model.c of initialize.m:42-50): the q-step, k_rhs and the sigma fix skip the rest
-    bool c_ends_on = true;       // DOTSOCP_C_ENDS=0: load all of c
-    int detect_c_ends();
-    // fused path: a scaling of beta that the next pass over beta applies on load (saves a 20 Nz pass)
-    int bpend = 0;           // pending operations on beta: 0, 1 or 2 (x * bmul / bdiv, then x * bmul2 / bdiv2)
-    double bmul = 1.0, bdiv = 1.0, bmul2 = 1.0, bdiv2 = 1.0;
+    // fused path: scalings of beta that the next pass over beta applies on load (saves a 20 Nz pass); at most two wait
+    ScaleOps bops{0, 1.0, 1.0, 1.0, 1.0};
+    ScaleOps zp_ops{0, 1.0, 1.0, 1.0, 1.0};    // the ops that were pending on the kept beta^k (beta2) when it was read
     int push_beta_op(double mul, double div);
-    int zp_pend = 0;                 // the ops that were pending on the kept beta^k (beta2) when it was read
-    double zp_mul = 1.0, zp_div = 1.0, zp_mul2 = 1.0, zp_div2 = 1.0;
+    int flush_beta();
+    // same for alpha after a sigma update on the folded KKT path: the next q-step divides on load (one slot in use)
+    ScaleOps aops{0, 1.0, 1.0, 1.0, 1.0};
+    int flush_alpha();
+    int sigma_scale_folded(double factor);
+    // the multiplier step is still pending: (q^{k-1}, q^k, beta^{k-1}) and the pending ops of beta; callers add outputs
+    FusedArgs pending_step_args(const Slab &s) const;
     // KKT sums of the last check (Solver::kkt_block) and the sigma they were taken with: the rescale block of the
     // NEXT iteration finds its five norms there instead of making its own passes over the state
     double last_S[S_COUNT] = {0};
     double last_S_sigma = 1.0;
     i64 last_S_it = -1;
-    int flush_beta();
-    // same for alpha after a sigma update on the folded KKT path: the next q-step divides on load
-    bool apend = false;
-    double amul = 1.0, adiv = 1.0;
-    int flush_alpha();
-    int sigma_scale_folded(double factor);
     bool norm_cache = true;  // DOTSOCP_NORM_CACHE=0: the rescale block always makes its own passes for its norms
     bool kkt_fold = true;    // DOTSOCP_KKT_FOLD=0: KKT sums by the separate node / edge launches on every path
     KktCoef kkt_coef() const;
-    void set_pending(FusedArgs &a) const {
-        a.bpend = bpend; a.bmul = bmul; a.bdiv = bdiv; a.bmul2 = bmul2; a.bdiv2 = bdiv2;
-    }
-    struct Pending { hipEvent_t a, b; int phase; };
-    std::vector<Pending> pending;
-    std::vector<hipEvent_t> event_pool;
-    double phase_ms[PH_COUNT] = {0};
-    i64 phase_launches[PH_COUNT] = {0};
-
-    ~Solver();
-    int init(const dotsocp_problem *p, int device, int nslabs, bool multi_dev = false);
-    int attach_rccl(const unsigned char *id, int rank, int world);
-    int upload(int field, const double *host);
-    int upload_layers(int field, const double *host, i64 t0, i64 n);
-    int download(int field, double *host);
+    int clear_partials(Slab &s);     // zero every region of the slab's KKT partial sums (on its main stream)
     int begin(const dotsocp_opts *o);
     int begin_method(const dotsocp_opts *o, int method, const dotsocp_acc_opts *acc);
     int run(i64 n_iters, i64 *done);
     int finish(dotsocp_result *res);
-
-    // internals
-    int alloc_slabs(int first, int count);
-    int ensure_alloc();
-    void free_slabs();
-    bool multi() const { return world > 1; }
-    bool remote() const { return nccl != nullptr; }
     int step(bool *brk);
     int rescale_block();
-    // hooks of the asynchronous schedule inside the partitioned t-solve: `fill` runs on the main streams while the first
-    // interface exchange travels, `behind` right after the second one has been issued
-    struct PhiHooks { std::function<int()> fill, behind; };
+    int poisson_all(const PhiHooks *hooks = nullptr);
     int phase_phi(const PhiHooks *hooks = nullptr);
     // part 0: all chunks; 1: all but the last chunk; 2: the last chunk (the only one that reads the q halo)
     int phase_z(int part = 0);
-    int phase_z_tails();
-    int make_tails();        // time slabs: finalise the adjoint sums of the last owned cell for the right neighbour
-    int send_tails();        // ... adjoint tails -> right
-    int send_phi_head();     // ... first phi layer -> left
-    int ship_tails();        // all three, one group
     // part 0: whole q-step; 1: all chunks but the last; 2: the last chunk (the one that reads the phi halo), then finish
     int phase_q(int part = 0, bool kkt = false);
     int phase_mult();
     int materialise();
+    int ensure_z();
     int kkt_sums(double *S, bool folded = false);
     int reduce_sums(double *S);
     int norms_light(double *S);
@@ -289,48 +331,18 @@ struct Solver {
     int scale_state(double a_mul, double a_div, double q_div, bool with_c);
     void update_coef();
     double elapsed() const;
-    // HIP events on slab 0's main stream (on_z: its second stream); slab 0 stands for all (slabs run in lockstep)
+    // ---- profiling (HIP events on slab 0's main stream; on_z: its second stream); slab 0 stands for all (lockstep) ----
+    bool profiling = false;
+    struct Pending { hipEvent_t a, b; int phase; };
+    std::vector<Pending> pending;
+    std::vector<hipEvent_t> event_pool;
+    double phase_ms[PH_COUNT] = {0};
+    i64 phase_launches[PH_COUNT] = {0};
     void prof_begin(int phase, bool on_z = false);
     void prof_end(int phase, bool on_z = false);
     int prof_flush();
-    int poisson_all(const PhiHooks *hooks = nullptr);
-    int transpose(bool forward);
-    int exchange_q_halo(bool with_u0);
-    int ensure_halo();       // run the q-halo exchange the last q-step left pending (halo_pending)
-    int exchange_u0_tail();
-    int make_u0_tail();
-    int group_begin();
-    int group_end();
-    bool tri_tsolve = true;  // time-slab Poisson solve by partitioned tridiagonal systems (tri.hip); DOTSOCP_TSOLVE=dct:
-                             // slab <-> pencil transposes around the t-axis DCT instead
-    int tri_alloc();
-    int tri_exchange(bool back);
-    int poisson_t_tridiag(const PhiHooks *hooks);
-    const bool qrhs = true;  // the fused dataflow's q-step also forms the next right-hand side (k_qstep_rhs)
-    bool rhs_valid = false;  // w0 holds A'(w.*q - alpha) + c of the current iterate (left there by the q-step)
-    // the q halo / u0 tail of the newest iterate have not been exchanged yet: step() issues the exchange behind the
-    // fork so that the cone chunks that do not read the halo overlap it; every other reader calls ensure_halo()
-    bool halo_pending = false;
-    bool u0_fresh = false;   // u0_prev holds w.*q0 - alpha0 of the CURRENT iterate of the left neighbour
-    bool u0_made = false;    // send_plane holds the u0 tail of the current iterate (written by the q-step itself)
-    // every slab with a neighbour in direction `dir` (+1 right, -1 left) sends `count` doubles
-    // from src(slab) to dst(neighbour)
-    typedef std::function<double *(Slab &)> Sel;
-    int shift(int dir, const Sel &src, const Sel &dst, i64 count);
-    // slabs of one process: the copies of the shift() calls between group_begin() and group_end() (a lone shift() is a
-    // group of one) are collected and pulled by ONE launch per receiving slab (flush_msgs)
-    struct Msg { int from, to; const double *src; double *dst; i64 count; };
-    std::vector<Msg> msgs;
-    int msg_depth = 0;
-    bool peer_ok = true;      // every pair of devices in use can address each other's memory (alloc_slabs)
-    bool cross_device = false;   // some pair of this process's slabs lives on different devices (alloc_slabs)
-    bool pull_default(const char *env_var) const;
-    bool msg_batching() const;
-    int flush_msgs();
-    int shift_edge_halo(const Sel &base);      // first owned bx / by layers of base(s) -> halo layer of the left slab
-    i64 field_len(int field) const;
 
-    // ---- loop variants (include/dotsocp.h: DOTSOCP_METHOD_*) ----
+    // ================ loop variants (include/dotsocp.h: DOTSOCP_METHOD_*): solver_acc.hip, solver_palm.hip ================
     int method = DOTSOCP_METHOD_INPALM;
     // acc-ADMM (solver_socp_accADMM.m:12-34,157-163)
     i64 acc_restart = 100, acc_k = 0;
@@ -350,10 +362,6 @@ struct Solver {
     void acc_swap_state();
     int acc_on_sigma_factor(double factor);
     AccCoef acc_coef() const;
-    // driver steps on the device (solver_io.hip)
-    int recover_outputs(const double *rho0, const double *rho1, double *rho, double *Ex, double *Ey, double *q0,
-                        double *bx, double *by);
-    int jump_from(Solver &coarse);
     // PALM (solver_palm.hip)
     bool palm_fast = true;     // one pass over beta per iteration (DOTSOCP_PALM_FAST=0: the two-pass dataflow)
     bool palm_p_valid = false; // p2 / sxp / syp hold the second gather of the last cone pass

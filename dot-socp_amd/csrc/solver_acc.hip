@@ -28,22 +28,22 @@ int Solver::acc_alloc() {
         const Grid &g = s.g;
         if (!s.q2) {                              // DOTSOCP_FUSED=0 contexts come without the tile buffers
             fused_geometry(g, s.fg);
-            DS_CHECK(dzalloc(&s.q_old, g.NqAlloc, s.st));
-            DS_CHECK(dzalloc(&s.q2, g.NqAlloc, s.st));
-            DS_CHECK(dzalloc(&s.beta2, 10 * g.Nc, s.st));       // pads of rows and columns stay zero (common.h)
-            DS_CHECK(dzalloc(&s.sx, s.fg.sx_len, s.st));
-            DS_CHECK(dzalloc(&s.sy, s.fg.sy_len, s.st));
-            DS_CHECK(dzalloc(&s.alpha2, g.NqAlloc, s.st));
+            DS_CHECK(s.zalloc(&s.q_old, g.NqAlloc));
+            DS_CHECK(s.zalloc(&s.q2, g.NqAlloc));
+            DS_CHECK(s.zalloc(&s.beta2, 10 * g.Nc));       // pads of rows and columns stay zero (common.h)
+            DS_CHECK(s.zalloc(&s.sx, s.fg.sx_len));
+            DS_CHECK(s.zalloc(&s.sy, s.fg.sy_len));
+            DS_CHECK(s.zalloc(&s.alpha2, g.NqAlloc));
         }
         if (s.phi_p) continue;
-        DS_CHECK(dzalloc(&s.phi_p, g.NphiAlloc, s.st));
-        DS_CHECK(dzalloc(&s.alpha_p, g.NqAlloc, s.st));
-        DS_CHECK(dzalloc(&s.z_p, 10 * g.Nc, s.st));
-        DS_CHECK(dzalloc(&s.phi_a, g.NphiAlloc, s.st));
-        DS_CHECK(dzalloc(&s.q_a, g.NqAlloc, s.st));
-        DS_CHECK(dzalloc(&s.alpha_a, g.NqAlloc, s.st));
-        DS_CHECK(dzalloc(&s.z_a, 10 * g.Nc, s.st));
-        DS_CHECK(dzalloc(&s.beta_a, 10 * g.Nc, s.st));
+        DS_CHECK(s.zalloc(&s.phi_p, g.NphiAlloc));
+        DS_CHECK(s.zalloc(&s.alpha_p, g.NqAlloc));
+        DS_CHECK(s.zalloc(&s.z_p, 10 * g.Nc));
+        DS_CHECK(s.zalloc(&s.phi_a, g.NphiAlloc));
+        DS_CHECK(s.zalloc(&s.q_a, g.NqAlloc));
+        DS_CHECK(s.zalloc(&s.alpha_a, g.NqAlloc));
+        DS_CHECK(s.zalloc(&s.z_a, 10 * g.Nc));
+        DS_CHECK(s.zalloc(&s.beta_a, 10 * g.Nc));
     }
     return 0;
 }
@@ -233,7 +233,7 @@ int Solver::acc_step(bool *brk) {
     auto cone_pass = [&]() -> int {
     prof_begin(kfold ? PH_FUSED_A : PH_ACC_CONE);      // the KKT flavour is timed apart (bench.py prices acc_cone as mode 1)
     if (kfold) {
-        FOR_SLABS(s) DS_HIP(ds_memset_async(s.kw.partials, 0, sizeof(double) * s.kw.maxBlocks * S_COUNT, s.st));
+        FOR_SLABS(s) DS_CHECK(clear_partials(s));
     }
     FOR_SLABS(s) {
         AccArgs a{};

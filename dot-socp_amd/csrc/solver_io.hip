@@ -1,6 +1,7 @@
 // Device-side driver steps around the loop: the multilevel transfer
 // jump_nextLevel (+ recoverOrgVar of the coarse level, InitialScaling of the fine one) and the outputs
 // recover_RhoE / recover_q.  Kernels: transfer.hip.  Both work on in-process time slabs (dotsocp_create_multi).
+// Below them: the fields between host and device (upload, upload_layers, download, the zero test of c at begin()).
 #include <algorithm>
 #include <cstring>
 
@@ -152,6 +153,158 @@ int Solver::jump_from(Solver &coarse) {
         DS_HIP(ds_memset_async(f.z, 0, sizeof(double) * 10 * f.g.Nc, f.st));       // var.z of initialize.m
     }
     DS_CHECK(sync_all());
+    return 0;
+}
+
+// --------------------------------------------------------------------------------------
+// upload / download.  Host pointers hold the GLOBAL field in the reference layout; with an RCCL
+// communicator attached they hold this process's slab of it (same layout restricted to the owned
+// layers: q = [q0 cells | bx layers | by layers]).
+// --------------------------------------------------------------------------------------
+static const int k1dCols[6] = {0, 5, 6, 7, 8, 9};   // 1-D cone columns inside the 10-plane layout
+
+i64 Solver::field_len(int field) const {
+    i64 ntn = nt, ntc = nt - 1;
+    if (remote()) { ntn = slabs[0].g.ntl; ntc = slabs[0].g.ncl; }
+    const i64 Nz = ny * nx * ntc, Nphi = ny * nx * ntn;
+    const i64 Nq = Nz + ny * (nx - 1) * ntn + (ny - 1) * nx * ntn;
+    switch (field) {
+        case DOTSOCP_F_PHI: case DOTSOCP_F_C: return Nphi;
+        case DOTSOCP_F_Q: case DOTSOCP_F_ALPHA: case DOTSOCP_F_WEIGHT: return Nq;
+        case DOTSOCP_F_Z: case DOTSOCP_F_BETA: return Nz * (prob.dim == 1 ? 6 : 10);
+        default: return -1;
+    }
+}
+
+// rows of `rowlen` doubles: device rows `pitch` apart, host rows contiguous (reference layout)
+int Solver::copy_rows(double *dev, double *host, i64 rowlen, i64 pitch, i64 nrows, bool up, hipStream_t st) {
+    if (rowlen <= 0 || nrows <= 0) return 0;
+    if (pitch == rowlen) {
+        if (up) DS_HIP(ds_memcpy_async(dev, host, sizeof(double) * rowlen * nrows, hipMemcpyHostToDevice, st));
+        else DS_HIP(ds_memcpy_async(host, dev, sizeof(double) * rowlen * nrows, hipMemcpyDeviceToHost, st));
+        return 0;
+    }
+    if (up) DS_HIP(ds_memcpy2d_async(dev, sizeof(double) * pitch, host, sizeof(double) * rowlen, sizeof(double) * rowlen,
+                                    (size_t)nrows, hipMemcpyHostToDevice, st));
+    else DS_HIP(ds_memcpy2d_async(host, sizeof(double) * rowlen, dev, sizeof(double) * pitch, sizeof(double) * rowlen,
+                                 (size_t)nrows, hipMemcpyDeviceToHost, st));
+    return 0;
+}
+
+static int copy_field(Solver &S, int field, double *host, bool up) {
+    const i64 ny = S.ny, nx = S.nx;
+    i64 ntn = S.nt, ntc = S.nt - 1;
+    if (S.remote()) { ntn = S.slabs[0].g.ntl; ntc = S.slabs[0].g.ncl; }
+    // host side: the reference layout q = [q0 (ny, nx, nt-1) ; bx (ny, nx-1, nt) ; by (ny-1, nx, nt)]; device side: rows
+    // py (by: pyb) doubles apart (common.h)
+    const i64 hplane = ny * nx, hbx = ny * (nx - 1), hby = (ny - 1) * nx;
+    const i64 NzG = hplane * ntc;
+    const i64 bxG = NzG, byG = NzG + hbx * ntn;
+    for (auto &s : S.slabs) {
+        DS_CHECK(S.use(s));
+        hipStream_t cur = s.st;
+        const Grid &g = s.g;
+        const i64 t0 = S.remote() ? 0 : g.t0;
+        auto nodes = [&](double *dev, double *h, i64 layers) { return S.copy_rows(dev, h, ny, g.py, nx * layers, up, cur); };
+        switch (field) {
+            case DOTSOCP_F_PHI: DS_CHECK(nodes(s.phi, host + hplane * t0, g.ntl)); break;
+            case DOTSOCP_F_C: DS_CHECK(nodes(s.c, host + hplane * t0, g.ntl)); break;
+            case DOTSOCP_F_Q: case DOTSOCP_F_ALPHA: case DOTSOCP_F_WEIGHT: {
+                double *d = field == DOTSOCP_F_Q ? s.q : (field == DOTSOCP_F_ALPHA ? s.alpha : s.weight);
+                DS_CHECK(nodes(d, host + hplane * t0, g.ncl));
+                DS_CHECK(S.copy_rows(d + g.offBx, host + bxG + hbx * t0, ny, g.py, (nx - 1) * g.ntl, up, cur));
+                DS_CHECK(S.copy_rows(d + g.offBy, host + byG + hby * t0, ny - 1, g.pyb, nx * g.ntl, up, cur));
+                break;
+            }
+            case DOTSOCP_F_Z: case DOTSOCP_F_BETA: {
+                double *d = field == DOTSOCP_F_Z ? s.z : s.beta;
+                const int K = S.prob.dim == 1 ? 6 : 10;
+                if (up && S.prob.dim == 1) DS_HIP(ds_memset_async(d, 0, sizeof(double) * 10 * g.Nc, cur));
+                for (int j = 0; j < K; ++j) {
+                    const int pj = S.prob.dim == 1 ? k1dCols[j] : j;
+                    DS_CHECK(nodes(d + pj * g.Nc, host + j * NzG + hplane * t0, g.ncl));
+                }
+                break;
+            }
+        }
+    }
+    DS_CHECK(S.sync_all());
+    return 0;
+}
+
+int Solver::upload(int field, const double *host) {
+    DS_ARG(host != nullptr, "host pointer is NULL");
+    DS_ARG(field_len(field) >= 0, "unknown field");
+    DS_ARG(field != DOTSOCP_F_WEIGHT || prob.weighted, "weight uploaded to an unweighted problem");
+    if (begun) { set_error("upload() after begin()"); return DOTSOCP_ESTATE; }
+    cur_dev = -1;
+    DS_CHECK(use_dev(device));
+    DS_CHECK(ensure_alloc());
+    return copy_field(*this, field, const_cast<double *>(host), true);
+}
+
+// model.c of initialize.m:42-50 is zero except on its first and last time layer, and every operation of the loop on c
+// (x * mul / div with positive factors) keeps a +0.0 what it is.  One reduction per slab at begin(), when every upload
+// of c is over (upload() after begin() is refused); a c that was never uploaded is the zeros of its allocation and passes.
+int Solver::detect_c_ends() {
+    FOR_SLABS(s) {
+        int *flag = nullptr, h = 1;
+        DS_CHECK(dmalloc(&flag, 1));
+        int rc = 0;
+        if (ds_memset_async(flag, 0, sizeof(int), s.st) != hipSuccess) rc = DOTSOCP_EHIP;
+        if (!rc) rc = launch_c_interior_test(s.g, s.c, flag, s.st);
+        if (!rc && ds_memcpy_async(&h, flag, sizeof(int), hipMemcpyDeviceToHost, s.st) != hipSuccess) rc = DOTSOCP_EHIP;
+        if (!rc && ds_stream_synchronize(s.st) != hipSuccess) rc = DOTSOCP_EHIP;
+        dfree(flag);
+        if (rc) { if (rc == DOTSOCP_EHIP) set_error("the zero test of c failed"); return rc; }
+        s.c_ends = (h == 0);
+    }
+    return 0;
+}
+
+// time layers [t0, t0 + n) of a node field (phi, c) from a host buffer that holds only those layers; the other layers
+// keep what they have (zeros after create).  model.c of initialize.m:42-50 is zero except for its first and last layer:
+// a driver uploads those two instead of a vector as long as the grid (1 GB at 1025 x 1025 x 129).
+int Solver::upload_layers(int field, const double *host, i64 t0, i64 n) {
+    DS_ARG(host != nullptr, "host pointer is NULL");
+    DS_ARG(field == DOTSOCP_F_PHI || field == DOTSOCP_F_C, "layer uploads serve the node fields (phi, c)");
+    const i64 ntn = remote() ? slabs[0].g.ntl : nt;
+    DS_ARG(t0 >= 0 && n >= 0 && t0 + n <= ntn, "layer range outside the field");
+    if (begun) { set_error("upload() after begin()"); return DOTSOCP_ESTATE; }
+    cur_dev = -1;
+    DS_CHECK(use_dev(device));
+    DS_CHECK(ensure_alloc());
+    const i64 hplane = ny * nx;
+    for (auto &s : slabs) {
+        DS_CHECK(use(s));
+        const Grid &g = s.g;
+        const i64 base = remote() ? 0 : g.t0;
+        const i64 lo = std::max(t0, base), hi = std::min(t0 + n, base + g.ntl);
+        if (lo >= hi) continue;
+        double *dev = (field == DOTSOCP_F_PHI ? s.phi : s.c) + g.plane * (lo - base);
+        DS_CHECK(copy_rows(dev, const_cast<double *>(host) + hplane * (lo - t0), ny, g.py, nx * (hi - lo), true, s.st));
+    }
+    DS_CHECK(sync_all());
+    return 0;
+}
+
+int Solver::download(int field, double *host) {
+    DS_ARG(host != nullptr, "host pointer is NULL");
+    DS_ARG(field_len(field) >= 0, "unknown field");
+    DS_ARG(field != DOTSOCP_F_WEIGHT || prob.weighted, "no weight in an unweighted problem");
+    cur_dev = -1;
+    DS_CHECK(use_dev(device));
+    DS_CHECK(ensure_alloc());
+    if (field == DOTSOCP_F_Z || field == DOTSOCP_F_BETA) {
+        DS_CHECK(need_beta_form("download"));
+        DS_CHECK(ensure_z());
+        DS_CHECK(flush_beta());
+    }
+    if (field == DOTSOCP_F_ALPHA) DS_CHECK(flush_alpha());
+    host_first_touch(host, sizeof(double) * (size_t)field_len(field));
+    DS_CHECK(copy_field(*this, field, host, false));
+    // after finish(): var.alpha = sigma * alpha, var.beta = sigma * beta  (solver_socp_inPALM.m:335-336)
+    if (finished && (field == DOTSOCP_F_ALPHA || field == DOTSOCP_F_BETA)) host_scale(host, field_len(field), sigma);
     return 0;
 }
 

@@ -62,17 +62,17 @@ int Solver::palm_begin() {
     if (palm_fast) {
         FOR_SLABS(s) {
             if (s.q3) continue;
-            DS_CHECK(dzalloc(&s.q3, s.g.NqAlloc, s.st));
-            DS_CHECK(dzalloc(&s.p2, s.g.NqAlloc, s.st));
-            DS_CHECK(dzalloc(&s.sxp, s.fg.sx_len, s.st));
-            DS_CHECK(dzalloc(&s.syp, s.fg.sy_len, s.st));
+            DS_CHECK(s.zalloc(&s.q3, s.g.NqAlloc));
+            DS_CHECK(s.zalloc(&s.p2, s.g.NqAlloc));
+            DS_CHECK(s.zalloc(&s.sxp, s.fg.sx_len));
+            DS_CHECK(s.zalloc(&s.syp, s.fg.sy_len));
             if (multi() && !s.g.first) {
-                DS_CHECK(dzalloc(&s.ptail_bx, s.g.bxLayer, s.st));
-                DS_CHECK(dzalloc(&s.ptail_by, s.g.byLayer, s.st));
+                DS_CHECK(s.zalloc(&s.ptail_bx, s.g.bxLayer));
+                DS_CHECK(s.zalloc(&s.ptail_by, s.g.byLayer));
             }
             if (multi() && !s.g.last) {
-                DS_CHECK(dzalloc(&s.send_pbx, s.g.bxLayer, s.st));
-                DS_CHECK(dzalloc(&s.send_pby, s.g.byLayer, s.st));
+                DS_CHECK(s.zalloc(&s.send_pbx, s.g.bxLayer));
+                DS_CHECK(s.zalloc(&s.send_pby, s.g.byLayer));
             }
         }
     }
@@ -94,15 +94,13 @@ int Solver::palm_step(bool *brk) {
                                              s.ptail_by, s.q));      // (time slabs: the tails came with the last cone pass's)
     } else if (deferred) {
         FOR_SLABS(s) {
-            FusedArgs a{};
-            a.q_old = s.q_old; a.q = s.q;
-            a.beta_in = s.beta; a.beta_out = s.beta2;
+            FusedArgs a = pending_step_args(s);
+            a.beta_out = s.beta2;
             a.q2 = s.q2; a.sx = s.sx; a.sy = s.sy;
-            set_pending(a);
             DS_CHECK(launch_cone_fused(4, s.g, lc, s.fg, a, s.st));
             std::swap(s.beta, s.beta2);
         }
-        bpend = 0;
+        bops.clear();
         deferred = false;
     } else {
         DS_CHECK(ensure_z());             // first iteration, or right after a KKT / rescale block
@@ -115,7 +113,7 @@ int Solver::palm_step(bool *brk) {
         }
     }
     if (!three) {
-        DS_CHECK(phase_z_tails());        // time slabs: adjoint tails -> right (the phi head travelled in the last iteration)
+        DS_CHECK(ship_tails());           // time slabs: adjoint tails -> right (the phi head travelled in the last iteration)
         FOR_SLABS(s)
             DS_CHECK(launch_qstep_palm_first(s.g, lc, s.fg, s.phi, s.q2, s.sx, s.sy, s.c, s.q_old, s.alpha, s.w0, s.st,
                                              s.tail_bx, s.tail_by));
@@ -150,7 +148,7 @@ int Solver::palm_step(bool *brk) {
             a.q = s.q;                    // q^k: the multiplier step
             a.q3 = s.q3;                  // q~^k: the projection
             a.beta_in = s.beta; a.beta_out = s.beta2;
-            set_pending(a);
+            a.bops = bops;
             DS_CHECK(launch_cone_fused(5, s.g, lc, s.fg, a, s.st));
             std::swap(s.beta, s.beta2);
             std::swap(s.q_old, s.q3);     // q_old = q~^k again, as the KKT / rescale blocks and the next pass expect
@@ -160,7 +158,7 @@ int Solver::palm_step(bool *brk) {
             DS_CHECK(launch_cone_fused(fast ? 6 : 0, s.g, lc, s.fg, a, s.st));
         }
     }
-    if (three) bpend = 0;
+    if (three) bops.clear();
     palm_p_valid = fast;
     prof_end(three ? PH_FUSED_B : PH_FUSED_A);
     z_valid = false;
@@ -189,14 +187,14 @@ int Solver::palm_step(bool *brk) {
     // cell pass of the block then carries the pending multiplier step, the cell sums and F*B*beta (Solver::kkt_sums).
     const bool adjustSigmaYes = if_adjust_sigma((double)it, lastSigmaIt);                 // :231
     const bool kkt_due = opts.ifCheckStepByStep || adjustSigmaYes || it == opts.maxit;
-    const bool fold = kkt_due && kkt_fold && qrhs;
+    const bool fold = kkt_due && kkt_fold;
     prof_begin(PH_QSTEP);
     if (fold) {
         const KktCoef k = kkt_coef();
         FOR_SLABS(s) {
-            DS_HIP(ds_memset_async(s.kw.partials, 0, sizeof(double) * s.kw.maxBlocks * S_COUNT, s.st));
+            DS_CHECK(clear_partials(s));
             QStepExtra ex{};
-            ex.apend = 0; ex.amul = 1.0; ex.adiv = 1.0;
+            ex.aops = aops;                        // (empty: no scaling of alpha is ever pending in this loop)
             ex.partials = kkt_qstep_partials(s.g, s.kw);
             ex.resid = s.w1;                       // free between the Poisson solves
             ex.kappa = k.kappa; ex.dsD = k.dsD;

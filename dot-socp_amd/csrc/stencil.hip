@@ -767,7 +767,7 @@ int launch_qstep_rhs(const Grid &g, const LoopCoef &c, const FusedGeom &fg, cons
     a.cvec = cvec; a.alpha_in = alpha_in; a.q_out = q_out; a.alpha_out = alpha_out; a.rhs = rhs;
     a.ap = APend{0, 1.0, 1.0};
     if (ex) {
-        a.ap = APend{ex->apend, ex->amul, ex->adiv};
+        a.ap = APend{ex->aops.n, ex->aops.mul, ex->aops.div};
         a.partials = ex->partials;
         a.resid = ex->resid;
         a.u0_tail = ex->u0_tail;

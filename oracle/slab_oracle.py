@@ -7,8 +7,9 @@ decomposition on the CPU -- which layers are owned, which halo layers travel in 
 at which point of the iteration, the slab<->pencil transposes of the Poisson solve, and which
 sums are all-reduced -- with matrix-free numpy operators, so that the plan can be checked
 against the single-process oracle (oracle/inpalm.py) under the gloo backend
-(tests/test_slabs_gloo.py).  The HIP implementation (dot-socp_amd/csrc/solver.hip) follows the
-same plan; its neighbour exchanges are validated on the GPU with all slabs in one process.
+(tests/test_slabs_gloo.py).  The HIP implementation (dot-socp_amd/csrc/solver.hip, the messages between
+slabs in solver_comm.hip) follows the same plan; its neighbour exchanges are validated on the GPU with all
+slabs in one process.
 
 Statement references are to socp/dot2d/algorithms/solver_socp_inPALM.m.
 """

@@ -1,6 +1,6 @@
 /* TEST INFRASTRUCTURE ONLY -- a stand-in for librccl that moves messages between PROCESSES THAT SHARE
  * ONE GPU through POSIX shared memory, so that the one-process-per-GPU code path of libdotsocp
- * (dot-socp_amd/csrc/solver.hip: shift(), transpose(), the KKT all-reduce) can be executed with a real
+ * (dot-socp_amd/csrc/solver_comm.hip: shift(), transpose(); solver.hip: the KKT all-reduce) can be executed with a real
  * world size > 1 on a single-GPU test box (RCCL itself refuses several ranks on one device).
  * Selected with DOTSOCP_RCCL_LIB=<this .so>; never used by the product.
  *

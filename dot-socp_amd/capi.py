@@ -75,6 +75,7 @@ SYMBOLS = {
     "dotsocp_dct_algorithm": (ctypes.c_int, [i64]),
     "dotsocp_cone_writes_beta": (ctypes.c_int, [i64, dbl, i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, dbl, dbl]),
     "dotsocp_rescale_due": (ctypes.c_int, [i64, ctypes.c_int, dbl, dbl]),
+    "dotsocp_qcone_form": (ctypes.c_int, [i64, dbl, i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, dbl, dbl]),
     "dotsocp_release_cache": (i64, []),
     "dotsocp_upload": (ctypes.c_int, [vp, ctypes.c_int, vp]),
     "dotsocp_upload_layers": (ctypes.c_int, [vp, ctypes.c_int, vp, i64, i64]),

@@ -296,6 +296,11 @@ int dotsocp_cone_writes_beta(dotsocp_i64 it, double last_sigma_it, dotsocp_i64 m
 int dotsocp_rescale_due(dotsocp_i64 it, int rescale, double maxFeas, double relGap) {
     return rescale_due(it, rescale, maxFeas, relGap) ? 1 : 0;
 }
+int dotsocp_qcone_form(dotsocp_i64 it, double last_sigma_it, dotsocp_i64 maxit, int check_step_by_step, int last_of_run,
+                       int next_last_of_run, int rescale, double maxFeas, double relGap) {
+    return qcone_form(it, last_sigma_it, maxit, check_step_by_step != 0, last_of_run != 0, next_last_of_run != 0, rescale,
+                      maxFeas, relGap);
+}
 
 dotsocp_i64 dotsocp_field_len(const dotsocp_problem *p, int field) {
     if (!p || (p->dim != 1 && p->dim != 2) || p->nt < 2 || p->nx < 1 || (p->dim == 2 && p->ny < 1)) return -1;
@@ -363,7 +368,7 @@ int dotsocp_kernel_time(dotsocp_ctx *ctx, const char *name, double *avg_ms, dots
     DS_ARG(name != nullptr, "name is NULL");
     static const char *names[PH_COUNT] = {"rhs", "poisson", "cone_proj", "qstep", "beta", "kkt",
                                           "cone_fused_a", "cone_fused_b", "materialise", "comm",
-                                          "interp", "acc_cone", "acc_gather", "qstep_first", "transpose", "cone_carry"};
+                                          "interp", "acc_cone", "acc_gather", "qstep_first", "transpose", "cone_carry", "qcone"};
     for (int i = 0; i < PH_COUNT; ++i)
         if (strcmp(name, names[i]) == 0) {
             const i64 n = ctx->s.phase_launches[i];

@@ -185,6 +185,21 @@ int launch_qstep_rhs(const Grid &g, const LoopCoef &c, const FusedGeom &fg, cons
                      double *rhs, hipStream_t st, i64 z0 = 0, i64 zcount = -1, i64 zstride = 1,
                      const QStepExtra *ex = nullptr);
 i64 qstep_rhs_blocks(const Grid &g, const FusedGeom &fg);
+// The q-step (plain inPALM instance of launch_qstep_rhs: one slab, no weight) and, one march step behind it, the
+// gamma-reading cone pass of the NEXT iteration on the q it has just formed (stencil.hip: k_qcone).  gout: that pass
+// writes gamma (the steady form: q is not stored, q_out is not touched) or beta (the exit form: q goes to q_out).
+// q2v / sx / sy are the sums the q-step reads, q2_out / sx_out / sy_out (other buffers) receive the new ones.
+struct QConeArgs {
+    const double *phi, *q2v, *sx, *sy, *cvec, *alpha_in, *gamma_in;
+    double *alpha_out, *rhs, *q_out, *beta_out, *q2_out, *sx_out, *sy_out;
+    i64 TC;                    // node layers per chunk (set by the launcher)
+    int ap_on;                 // pending scaling of alpha_in, applied on load (QStepExtra::aops)
+    double ap_mul, ap_div;
+    int c_ends;                // c is zero off the two global end layers
+};
+int launch_qcone(const Grid &g, const LoopCoef &c, const FusedGeom &fg, QConeArgs a, bool gout, hipStream_t st);
+// node layers per chunk of that launch: one chunk per tile, or DOTSOCP_QCONE_TC=n (results do not depend on it)
+i64 qcone_chunk_len(const Grid &g);
 // rhs <- (rhs + r) - r / factor, c <- c / factor  (sigma update without a new pass over q and alpha)
 // (c_ends: c is zero off the two global end layers, which alone are divided)
 int launch_rhs_sigma_fix(const Grid &g, double *rhs, const double *r, double *cvec, double factor, hipStream_t st,

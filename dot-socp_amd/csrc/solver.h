@@ -105,6 +105,7 @@ struct Slab {
     // ... on time slabs: the second gather's share of the neighbour's first edge layer (sent to the right / received from the left)
     double *send_pbx = nullptr, *send_pby = nullptr, *ptail_bx = nullptr, *ptail_by = nullptr;
     double *alpha2 = nullptr;   // ping-pong partner of alpha (q-step that also forms the next rhs)
+    double *sx2 = nullptr, *sy2 = nullptr;   // ping-pong partners of sx / sy (the early cone pass; allocated at its first use)
     // partitioned tridiagonal t-solve (tri.hip): messages to / from the owners of the modes, zero-mode work line
     double *tri_send = nullptr, *tri_recv = nullptr, *tri_bsend = nullptr, *tri_brecv = nullptr, *tri_zero = nullptr;
     double *carry = nullptr;    // 4 layer planes: hand-off between the chunk launches of a cone pass (FusedArgs::carry_in / _out)
@@ -125,7 +126,7 @@ void pencil_range(i64 plane, int world, int j, i64 *l0, i64 *l1);
 bool if_adjust_sigma(double iter, double last_iter);   // IfAdjustSigma (solver_socp_inPALM.m:361-379)
 
 enum Phase { PH_RHS = 0, PH_POISSON, PH_PROJ, PH_QSTEP, PH_BETA, PH_KKT, PH_FUSED_A, PH_FUSED_B, PH_MATERIALISE,
-             PH_COMM, PH_INTERP, PH_ACC_CONE, PH_ACC_GATHER, PH_QSTEP0, PH_TRANSPOSE, PH_CONE_CARRY, PH_COUNT };
+             PH_COMM, PH_INTERP, PH_ACC_CONE, PH_ACC_GATHER, PH_QSTEP0, PH_TRANSPOSE, PH_CONE_CARRY, PH_QCONE, PH_COUNT };
 
 // The schedule of the gamma form (fused.hip, Solver::step): pure host arithmetic, also behind the C ABI.
 // rescale_due: the rescale block of iteration `it` takes its norms or rescales (solver_socp_inPALM.m:138-151), given the
@@ -136,6 +137,14 @@ bool rescale_due(i64 it, int rescale, double maxFeas, double relGap);
 // values are the ones iteration it + 1 will see whenever this iteration has no check.)
 bool cone_writes_beta(i64 it, double lastSigmaIt, i64 maxit, bool checkStepByStep, bool last_of_run, int rescale,
                       double maxFeas, double relGap);
+
+// The early cone pass (solver.h: Solver::qcone): the q-step of iteration `it` also runs the cone pass of iteration it + 1.
+// QCONE_NONE: the pass of `it` writes beta (cone_writes_beta), so a reader of beta or q follows it; else the form of the
+// early pass is the schedule of it + 1: QCONE_EXIT if that pass must leave beta (and q in memory), QCONE_STEADY if it
+// leaves gamma.  All inputs change at KKT checks only, and `it` has none.  next_last_of_run: it + 1 ends its run() call.
+enum { QCONE_NONE = 0, QCONE_STEADY = 1, QCONE_EXIT = 2 };
+int qcone_form(i64 it, double lastSigmaIt, i64 maxit, bool checkStepByStep, bool last_of_run, bool next_last_of_run,
+               int rescale, double maxFeas, double relGap);
 
 struct Solver {
     // ================ devices, streams, slabs: solver_slabs.hip ================
@@ -286,6 +295,20 @@ struct Solver {
     bool beta_gamma = false;     // s.beta holds gamma (deferred only)
     bool cone_gout = false;      // this iteration's pass writes gamma (set by step())
     bool last_of_run = false;    // this iteration is the last of its run() call (set by run())
+    // The early cone pass.  A gamma-reading pass needs q^{k+1} and gamma^k only -- not phi -- so the q-step of an iteration
+    // whose own pass left gamma runs the NEXT iteration's pass in the same kernel, on the q it holds in registers
+    // (stencil.hip: k_qcone; one slab, inPALM / ALG2, unweighted).  The bookkeeping of that pass is done where the launch is
+    // issued (phase_q); phase_z of the next iteration launches nothing and checks that step() schedules what was predicted.
+    // After the steady form q^{k+1} is not in memory (q_valid): by the schedule every reader of q follows an exit form.
+    int qcone = -1;              // DOTSOCP_QCONE: 0 never, 1 wherever eligible, 2 as 1 with the two kernels back to back
+                                 // (the schedule alone); unset (-1): on grids of at least 2048 tiles
+    bool q_valid = true;         // s.q holds q of the last q-step
+    bool early_pass = false;     // the cone pass of the NEXT iteration has run ...
+    bool early_gout = false;     // ... and has written gamma
+    bool next_last_of_run = false;   // the next iteration is the last of this run() call (set by run())
+    int need_q(const char *who) const;
+    int qcone_decide() const;    // QCONE_* for this iteration's q-step, after its phase_z
+    bool time_limit_passed() const;
     i64 timeout_at = -1;         // DOTSOCP_TEST_TIMEOUT_AT (test hook): the time limit counts as passed from this iteration on
     bool timeout_pending = false;   // the time limit passed in an iteration that wrote gamma: the next one checks and stops
     int need_beta_form(const char *who) const;
@@ -320,7 +343,7 @@ struct Solver {
     // part 0: all chunks; 1: all but the last chunk; 2: the last chunk (the only one that reads the q halo)
     int phase_z(int part = 0);
     // part 0: whole q-step; 1: all chunks but the last; 2: the last chunk (the one that reads the phi halo), then finish
-    int phase_q(int part = 0, bool kkt = false);
+    int phase_q(int part = 0, bool kkt = false, int early = QCONE_NONE);
     int phase_mult();
     int materialise();
     int ensure_z();

@@ -44,6 +44,13 @@ int Solver::need_beta_form(const char *who) const {
     return DOTSOCP_ESTATE;
 }
 
+// Every reader of q outside k_qcone: by the schedule each follows a q-step that stored q (solver.h: the early cone pass)
+int Solver::need_q(const char *who) const {
+    if (q_valid) return 0;
+    set_error("internal: %s met a q that was never stored", who);
+    return DOTSOCP_ESTATE;
+}
+
 int Solver::flush_beta() {
     DS_CHECK(need_beta_form("flush_beta"));
     if (bops.empty()) return 0;
@@ -106,6 +113,7 @@ int Solver::sigma_scale_folded(double factor) {
 
 int Solver::scale_state(double a_mul, double a_div, double q_div, bool with_c) {
     DS_CHECK(need_beta_form("scale_state"));
+    DS_CHECK(need_q("scale_state"));
     DS_CHECK(flush_alpha());
     if (begun) DS_CHECK(ensure_halo());
     u0_made = false;
@@ -166,6 +174,13 @@ int Solver::begin(const dotsocp_opts *o) {
     // "time limit in a gamma iteration" branch of step() at a chosen iteration instead of at a wall-clock moment)
     timeout_at = -1;
     if (const char *e = getenv("DOTSOCP_TEST_TIMEOUT_AT")) timeout_at = atoll(e);
+    qcone = -1;
+    if (const char *e = getenv("DOTSOCP_QCONE")) qcone = atoi(e);
+    if (qcone < -1 || qcone > 2) qcone = -1;
+    q_valid = true;
+    early_pass = false;
+    early_gout = false;
+    next_last_of_run = false;
     beta_gamma = false;
     cone_gout = false;
     last_of_run = false;
@@ -277,6 +292,7 @@ int Solver::phase_phi(const PhiHooks *hooks) {
     }
     prof_begin(PH_RHS);
     if (!rhs_valid) {
+        DS_CHECK(need_q("phase_phi"));
         DS_CHECK(flush_alpha());
         FOR_SLABS(s) DS_CHECK(launch_rhs(s.g, lc, s.q, s.alpha, s.c, s.weight, s.u0_prev, s.w0, s.st, c_ends_on && s.c_ends));
     } else if (multi()) {
@@ -297,6 +313,17 @@ int Solver::phase_phi(const PhiHooks *hooks) {
 // and only the last chunk reads the q halo -- step() puts the others in front of the halo's arrival (part 1) and the
 // last one beside the first interface exchange of the Poisson solve (part 2).
 int Solver::phase_z(int part) {
+    if (early_pass) {
+        // this iteration's pass ran inside the last q-step (phase_q), which also did its bookkeeping
+        early_pass = false;
+        if (part != 0 || !fused || !deferred || cone_gout != early_gout) {
+            set_error("internal: the early cone pass wrote %s, the schedule asks for %s", early_gout ? "gamma" : "beta",
+                      cone_gout ? "gamma" : "beta");
+            return DOTSOCP_ESTATE;
+        }
+        return 0;
+    }
+    DS_CHECK(need_q("phase_z"));
     if (part != 1) DS_CHECK(ensure_halo());     // the last chunk reads the q halo (part 1 never does)
     if (!fused) {
         prof_begin(PH_PROJ);
@@ -363,12 +390,39 @@ KktCoef Solver::kkt_coef() const {
 }
 
 // kkt: the iteration ends with a KKT check and the q-step runs in its KKT variant (one slab: part == 0)
-int Solver::phase_q(int part, bool kkt) {
+int Solver::phase_q(int part, bool kkt, int early) {
     if (!fused) DS_CHECK(flush_alpha());
-    prof_begin(PH_QSTEP);
+    if (early != QCONE_NONE && (part != 0 || kkt || multi() || !fused || !deferred || !beta_gamma || !bops.empty())) {
+        set_error("internal: early cone pass in a state it does not serve");
+        return DOTSOCP_ESTATE;
+    }
+    const bool egout = (early == QCONE_STEADY);
+    const int ph = (early != QCONE_NONE) ? PH_QCONE : PH_QSTEP;
+    prof_begin(ph);
     FOR_SLABS(s) {
         hipStream_t st = s.st;
-        if (!fused) {
+        if (early != QCONE_NONE && qcone != 2) {
+            // reads the sums in q2 / sx / sy and gamma; q^{k+1} goes to the buffer that held q^{k-1} (exit form only), the new
+            // sums to the buffer that holds q^k -- dead: the pass of this iteration has run, a gamma-reading pass reads no
+            // q_old and the q-step never reads q -- and to the partners of sx / sy
+            if (!s.sx2) {
+                DS_CHECK(s.zalloc(&s.sx2, s.fg.sx_len));
+                DS_CHECK(s.zalloc(&s.sy2, s.fg.sy_len));
+            }
+            QConeArgs a{};
+            a.phi = s.phi; a.q2v = s.q2; a.sx = s.sx; a.sy = s.sy; a.cvec = s.c; a.alpha_in = s.alpha; a.gamma_in = s.beta;
+            a.alpha_out = s.alpha2; a.rhs = s.w0; a.q_out = s.q_old; a.beta_out = s.beta2;
+            a.q2_out = s.q; a.sx_out = s.sx2; a.sy_out = s.sy2;
+            a.ap_on = aops.n; a.ap_mul = aops.mul; a.ap_div = aops.div;
+            a.c_ends = (c_ends_on && s.c_ends) ? 1 : 0;
+            DS_CHECK(launch_qcone(s.g, lc, s.fg, a, egout, st));
+            std::swap(s.alpha, s.alpha2);
+            std::swap(s.q, s.q_old);          // s.q: q^{k+1} (steady form: not stored), s.q_old: the new sums
+            std::swap(s.q2, s.q_old);         // s.q2: the new sums, s.q_old: a dead buffer, as the next q-step expects
+            std::swap(s.sx, s.sx2);
+            std::swap(s.sy, s.sy2);
+            std::swap(s.beta, s.beta2);
+        } else if (!fused) {
             DS_CHECK(launch_qstep(s.g, lc, s.phi, s.z, s.beta, s.weight, s.tail_bx, s.tail_by, s.q, s.alpha, s.st));
         } else {
             // q^{k+1} goes to the buffer that held q^{k-1}; q^k is kept for the deferred beta update
@@ -391,10 +445,29 @@ int Solver::phase_q(int part, bool kkt) {
                                       s.q_old, s.alpha, s.alpha2, s.w0, st, z0, zc, zs, &ex));
             if (part != 1) std::swap(s.alpha, s.alpha2);
             if (part != 1) std::swap(s.q, s.q_old);
+            if (early != QCONE_NONE) {
+                // DOTSOCP_QCONE=2: the same schedule with the two kernels back to back
+                FusedArgs a{};
+                a.q = s.q; a.q2 = s.q2; a.sx = s.sx; a.sy = s.sy;
+                a.beta_in = s.beta; a.beta_out = s.beta2;
+                a.bops = bops;
+                DS_CHECK(launch_cone_fused(1, s.g, lc, s.fg, a, s.st, 0, s.fg.chunks, CONE_GIN | (egout ? CONE_GOUT : 0)));
+                std::swap(s.beta, s.beta2);
+            }
         }
     }
-    prof_end(PH_QSTEP);
+    prof_end(ph);
     if (part == 1) return 0;
+    q_valid = true;
+    if (early != QCONE_NONE) {
+        // the bookkeeping of the next iteration's cone pass (phase_z)
+        q_valid = !egout || qcone == 2;
+        beta_gamma = egout;
+        z_valid = false;
+        z_prev_ok = false;
+        early_pass = true;
+        early_gout = egout;
+    }
     u0_made = multi() && fused;
     if (fused) aops.clear();                 // the q-step wrote the scaled alpha into the ping-pong partner
     rhs_valid = fused;
@@ -420,6 +493,7 @@ int Solver::phase_mult() {
 int Solver::materialise() {
     if (!fused || !deferred) return 0;
     DS_CHECK(need_beta_form("materialise"));
+    DS_CHECK(need_q("materialise"));
     DS_CHECK(ensure_halo());
     prof_begin(PH_MATERIALISE);
     FOR_SLABS(s) {
@@ -439,6 +513,7 @@ int Solver::materialise() {
 int Solver::ensure_z() {
     if (!fused || z_valid) return 0;
     DS_CHECK(need_beta_form("ensure_z"));
+    DS_CHECK(need_q("ensure_z"));
     if (deferred) return materialise();
     if (!z_prev_ok) {
         set_error("internal: z cannot be regenerated");
@@ -464,6 +539,7 @@ int Solver::ensure_z() {
 // share, the cell pass adds the F*B*beta terms of the edges, and no node / edge launch follows
 int Solver::kkt_sums(double *S, bool folded) {
     DS_CHECK(need_beta_form("kkt_sums"));
+    DS_CHECK(need_q("kkt_sums"));
     DS_CHECK(ensure_halo());
     const KktCoef k = kkt_coef();
     if (method == DOTSOCP_METHOD_ACCADMM && folded) {
@@ -566,6 +642,7 @@ int Solver::reduce_sums(double *S) {
 // two iterations of the fused loop): one pass over beta that stores nothing, three sums of squares.  S as from kkt_sums().
 int Solver::norms_light(double *S) {
     DS_CHECK(need_beta_form("norms_light"));
+    DS_CHECK(need_q("norms_light"));
     DS_CHECK(ensure_halo());
     DS_CHECK(flush_alpha());
     const KktCoef k = kkt_coef();
@@ -647,6 +724,33 @@ bool cone_writes_beta(i64 it, double lastSigmaIt, i64 maxit, bool checkStepBySte
     if (checkStepByStep || if_adjust_sigma((double)it, lastSigmaIt) || it >= maxit) return true;   // ends in a KKT check
     if (last_of_run) return true;                                                                  // the caller may read anything
     return rescale_due(it + 1, rescale, maxFeas, relGap);
+}
+
+int qcone_form(i64 it, double lastSigmaIt, i64 maxit, bool checkStepByStep, bool last_of_run, bool next_last_of_run,
+               int rescale, double maxFeas, double relGap) {
+    if (cone_writes_beta(it, lastSigmaIt, maxit, checkStepByStep, last_of_run, rescale, maxFeas, relGap)) return QCONE_NONE;
+    // `it` has no check: lastSigmaIt, rescale, maxFeas and relGap are what iteration it + 1 will find
+    return cone_writes_beta(it + 1, lastSigmaIt, maxit, checkStepByStep, next_last_of_run, rescale, maxFeas, relGap)
+               ? QCONE_EXIT : QCONE_STEADY;
+}
+
+// the time-out predicate of step(): the same expression in front of the q-step (qcone_decide) and behind the body
+bool Solver::time_limit_passed() const {
+    // with one slab per process a per-rank clock could split the ranks: see kkt_block()
+    return timeout_pending || (remote() ? false : (elapsed() > time_limit || (timeout_at > 0 && it >= timeout_at)));
+}
+
+// Does this iteration's q-step also run the cone pass of the next one?  Called after phase_z: beta_gamma says what this
+// iteration's own pass left.
+int Solver::qcone_decide() const {
+    if (qcone == 0 || !fused || multi() || prob.weighted || method != DOTSOCP_METHOD_INPALM) return QCONE_NONE;
+    if (!deferred || !beta_gamma || !bops.empty()) return QCONE_NONE;
+    const Slab &s = slabs[0];
+    if (s.g.ncl < 1 || s.fg.XB != 4) return QCONE_NONE;
+    if (qcone < 0 && s.fg.nyblk * s.fg.nxblk < 2048) return QCONE_NONE;      // grids whose cone pass runs as one chunk
+    if (time_limit_passed()) return QCONE_NONE;       // the check this asks for needs the state between two iterations
+    return qcone_form(it, lastSigmaIt, opts.maxit, opts.ifCheckStepByStep != 0, last_of_run, next_last_of_run, rescale,
+                      maxFeas, relGap);
 }
 
 bool if_adjust_sigma(double iter, double last_iter) {   // :361-379
@@ -765,7 +869,10 @@ int Solver::step(bool *brk) {
     const bool adjustSigmaYes = if_adjust_sigma((double)it, lastSigmaIt);                  // :220
     // known before the q-step (the time limit is the one trigger that is not: such a check takes the unfolded path)
     // ... and a time limit that passed in an iteration which left gamma behind: this one checks (folded) and stops
-    const bool kkt_due = opts.ifCheckStepByStep || adjustSigmaYes || it == opts.maxit || timeout_pending;
+    // (a steady early pass has already run this iteration's pass and left gamma and no q: the pending check waits for the
+    // next iteration that writes beta -- the one after this, since no further early pass is issued past the limit)
+    const bool early_steady = early_pass && early_gout;
+    const bool kkt_due = opts.ifCheckStepByStep || adjustSigmaYes || it == opts.maxit || (timeout_pending && !early_steady);
     // what this iteration's cone pass leaves in s.beta (solver.h: the gamma form)
     // (cone_writes_beta covers every term of kkt_due but timeout_pending, which only step() knows: hence !kkt_due)
     cone_gout = cone_carry && fused && deferred && !kkt_due &&
@@ -828,14 +935,14 @@ int Solver::step(bool *brk) {
         DS_CHECK(phase_q(split_q ? 2 : 0, fold));
     } else {
         DS_CHECK(ship_tails());      // time slabs: phi head -> left, adjoint tails -> right
-        DS_CHECK(phase_q(0, fold));
+        DS_CHECK(phase_q(0, fold, fold ? QCONE_NONE : qcone_decide()));
     }
     DS_CHECK(phase_mult());
-    // with one slab per process a per-rank clock could split the ranks: see kkt_block()
-    const bool timed_out = timeout_pending || (remote() ? false : (elapsed() > time_limit || (timeout_at > 0 && it >= timeout_at)));
+    const bool timed_out = time_limit_passed();
     timeout_pending = false;
-    if (timed_out && beta_gamma) {
+    if (timed_out && (beta_gamma || early_pass)) {
         // the unscheduled check would read beta: it is taken at the end of the next iteration, which writes beta
+        // (early_pass: the state is already that of the middle of the next iteration, whatever its pass wrote)
         timeout_pending = true;
         return 0;
     }
@@ -861,11 +968,14 @@ int Solver::run(i64 n_iters, i64 *done) {
         if (n_iters >= 0 && n >= n_iters) break;
         bool brk = false;
         last_of_run = (n_iters >= 0 && n + 1 >= n_iters);
+        next_last_of_run = (n_iters >= 0 && n + 2 >= n_iters);
         DS_CHECK(step(&brk));
         if (brk) stopped = true;
         ++n;
     }
     DS_CHECK(need_beta_form("the end of run()"));
+    DS_CHECK(need_q("the end of run()"));
+    if (early_pass) { set_error("internal: an early cone pass is pending at the end of run()"); return DOTSOCP_ESTATE; }
     DS_CHECK(ensure_halo());          // callers between run() calls see exchanged halos
     DS_CHECK(sync_all());
     DS_CHECK(prof_flush());

@@ -16,6 +16,7 @@ int Solver::recover_outputs(const double *rho0, const double *rho1, double *rho,
                             double *bx, double *by) {
     if (!finished) { set_error("recover_outputs() needs finish()"); return DOTSOCP_ESTATE; }
     DS_CHECK(need_beta_form("recover_outputs"));
+    DS_CHECK(need_q("recover_outputs"));
     DS_ARG(rho == nullptr || (rho0 != nullptr && rho1 != nullptr), "rho needs rho0 and rho1");
     cur_dev = -1;
     DS_CHECK(use_dev(device));
@@ -301,6 +302,7 @@ int Solver::download(int field, double *host) {
         DS_CHECK(flush_beta());
     }
     if (field == DOTSOCP_F_ALPHA) DS_CHECK(flush_alpha());
+    if (field == DOTSOCP_F_Q) DS_CHECK(need_q("download"));
     host_first_touch(host, sizeof(double) * (size_t)field_len(field));
     DS_CHECK(copy_field(*this, field, host, false));
     // after finish(): var.alpha = sigma * alpha, var.beta = sigma * beta  (solver_socp_inPALM.m:335-336)

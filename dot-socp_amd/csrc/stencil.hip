@@ -4,6 +4,7 @@
 // summation orders follow the column/row order of the reference's sparse products
 //  so that results agree with the oracle to the last bit.
 #include "device_utils.h"
+#include "gather_tile.h"
 #include "kernels.h"
 
 #include <cstdlib>
@@ -906,6 +907,279 @@ static int launch_qstep_rhs_var(int var, const Grid &g, const LoopCoef &c, const
         else if (var == 2) QRHS_LAUNCH(false, 2); else QRHS_LAUNCH(false, 3);
     }
 #undef QRHS_LAUNCH
+    DS_HIP(hipGetLastError());
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------
+// The q-step of iteration k with the gamma-reading cone pass of iteration k + 1 behind it (single slab, inPALM / ALG2,
+// unweighted; scheduled by Solver::step, solver.h: "The early cone pass").  That pass needs q^{k+1} and gamma^k only, and
+// the thread of node (y, x, tl) of k_qstep_rhs computes exactly the entries cone cell (y, x, tl) reads: q0 of the cell that
+// starts there, its bx / by edges and -- on the tile's first column / row -- the neighbour tile's edge.  So the march takes,
+// at step tl, the q-step of node layer tl (k_qstep_rhs<false, 0>: same loads, same arithmetic, same order) and then cone
+// cell tl - 1 (k_cone_fused<1, 4, NT, true, GOUT>: the same helpers in the same order), whose EdgeQuad of layer tl - 1 and
+// q0 were kept in registers; the x - 1 edge comes through the LDS slot that carries the edge's u, the y - 1 edge by a lane
+// shuffle.  q^{k+1} makes no round trip through memory: the steady form (GOUT: gamma out) does not store it at all, the
+// exit form (beta out) stores it for the readers behind it.  The gather writes its sums into buffers other than the ones
+// the q-step part reads.  A chunk of node layers [t0, t1) stores the q-step of these layers and the cone cells / edge
+// layers [t0 - 1, t1 - 1) (the last chunk: also the final edge layer); it starts two layers early without storing, which
+// gives it u0 of cell t0 - 1, the quad of layer t0 - 1 and the gather's carried entries of cell t0 - 2 -- reads of
+// ping-ponged or read-only arrays only.
+// ---------------------------------------------------------------------------------------
+template <bool NT, bool GOUT>
+__global__ void __launch_bounds__(TILE_Y *TILE_X, 3) k_qcone(Grid g, LoopCoef c, FusedGeom fg, QConeArgs a) {
+    constexpr int XB = TILE_X;
+    __shared__ double2 xch[2][XB][TILE_Y];         // (u, q^{k+1}) of the bx edge
+    __shared__ double ph[2][XB + 2][TILE_Y + 2];   // phi of the layer the march stands on (k_qstep_rhs)
+    __shared__ double2 gch[2][XB][64];             // the gather's hand-off (gather_tile.h)
+    const APend ap{a.ap_on, a.ap_mul, a.ap_div};
+    const int lane = threadIdx.x, xl = threadIdx.y;
+    const BlockId blk = block_id(true);
+    const i64 y = (i64)blk.x * TILE_Y + lane;
+    const i64 x = (i64)blk.y * XB + xl;
+    const bool inb = (y < g.ny) && (x < g.nx);
+    const i64 t0 = (i64)blk.z * a.TC;
+    const i64 t1 = (t0 + a.TC < g.ntl) ? t0 + a.TC : g.ntl;
+    const i64 tstart = (t0 >= 2) ? t0 - 2 : 0;
+    const i64 tstop = (t1 == g.ntl) ? t1 + 1 : t1;      // one virtual step on the last chunk emits the final edge layer
+    const i64 nxblk = gridDim.y, nyblk = gridDim.x;
+    const bool hasBx = inb && (x < g.nx - 1), hasBy = inb && (y < g.ny - 1);
+    const bool rightCol = hasBx && (xl == XB - 1), topRow = hasBy && (lane == TILE_Y - 1);
+    const bool leftTile = inb && (xl == 0) && (x >= 1);          // the bx edge on the left belongs to the tile there
+    const bool belowTile = inb && (lane == 0) && (y >= 1);       // the by edge below belongs to the tile there
+    const bool sxOwn = hasBx && ((x % fg.XB) == fg.XB - 1), syOwn = hasBy && ((y & 63) == 63);
+    const i64 yc = inb ? y : 0, xc = inb ? x : 0;
+    double p0 = 0.0;
+    if (inb) {
+        const i64 node0 = y + g.py * (x + g.nx * tstart);
+        p0 = a.phi[node0];
+        double hx = 0.0, hl = 0.0, hy = 0.0, hb = 0.0;
+        if (rightCol) hx = a.phi[node0 + g.py];
+        if (leftTile) hl = a.phi[node0 - g.py];
+        if (topRow) hy = a.phi[node0 + 1];
+        if (belowTile) hb = a.phi[node0 - 1];
+        ph[0][xl + 1][lane + 1] = p0;
+        if (xl == XB - 1) ph[0][XB + 1][lane + 1] = hx;
+        if (xl == 0) ph[0][0][lane + 1] = hl;
+        if (lane == TILE_Y - 1) ph[0][xl + 1][TILE_Y + 1] = hy;
+        if (lane == 0) ph[0][xl + 1][0] = hb;
+    }
+    double u0prev = 0.0;                   // u of the q0 entry of cell tl - 1 (a chunk's unstored first step: unused)
+    double q0c = 0.0;                      // q0^{k+1} of cell tl - 1
+    EdgeQuad eprev{0.0, 0.0, 0.0, 0.0};    // the cell's edges of layer tl - 1, times sf
+    GatherCarry gc;
+    int par = 0;
+    __syncthreads();                                              // ph[0] is complete
+    for (i64 tl = tstart; tl < tstop; ++tl) {
+        const bool own = tl >= t0;                                // false on the two steps in front of the chunk
+        const bool hasC = (tl > tstart) && (tl - 1 < g.ncl);      // cone cell tl - 1 exists and its first quad is in eprev
+        // ---------------- loads of the cone cell ----------------
+        const i64 ci = yc + g.py * (xc + g.nx * (hasC ? tl - 1 : 0));
+        double b[10];
+        if (hasC) {
+#pragma unroll
+            for (int j = 0; j < 10; ++j) b[j] = ld_stream<NT>(a.gamma_in + j * g.Nc + ci);
+        }
+        EdgeQuad ecur{0.0, 0.0, 0.0, 0.0};
+        double q0n = 0.0;
+        if (tl < g.ntl) {
+            // ======== the q-step of node layer tl: k_qstep_rhs<false, 0>, phase by phase ========
+            const i64 node = yc + g.py * (xc + g.nx * tl);
+            const bool tbnd = (g.t0 + tl == 0) || (g.t0 + tl == g.nt - 1);
+            const double dc = tbnd ? c.c2 : c.c1;
+            const double di = tbnd ? c.dinv2 : c.dinv1;
+            const bool hasCell = inb && (tl < g.ncl);
+            // ---------------- loads ----------------
+            const i64 eX = hasBx ? g.offBx + g.bxLayer * tl + yc + g.py * xc : node;
+            const i64 eY = hasBy ? g.offBy + g.byLayer * tl + yc + g.pyb * xc : node;
+            const i64 k0 = hasCell ? node : 0;
+            const i64 nodeT = hasCell ? node + g.plane : node;
+            const double pTl = a.phi[nodeT];
+            double hx = 0.0, hl = 0.0, hy = 0.0, hb = 0.0;
+            if (rightCol) hx = a.phi[nodeT + g.py];
+            if (leftTile) hl = a.phi[nodeT - g.py];
+            if (topRow) hy = a.phi[nodeT + 1];
+            if (belowTile) hb = a.phi[nodeT - 1];
+            const double pXl = ph[par][xl + 2][lane + 1];
+            const double pYl = ph[par][xl + 1][lane + 2];
+            const double al0 = a.alpha_in[k0], alX = a.alpha_in[eX], alY = a.alpha_in[eY];
+            const double g0 = a.q2v[k0];
+            double gX = a.q2v[eX], gY = a.q2v[eY];
+            double cv = 0.0;
+            if (!a.c_ends || tbnd) cv = a.cvec[node];
+            const double sxv = a.sx[sxOwn ? (tl * fg.nxblk + (x / fg.XB + 1)) * g.ny + y : 0];
+            const double syv = a.sy[syOwn ? (tl * g.nx + x) * fg.nyblk + (y / 64 + 1) : 0];
+            double pLl = 0.0, alL = 0.0, gL = 0.0, sxL = 0.0;
+            if (leftTile) {
+                const i64 eL = g.offBx + g.bxLayer * tl + y + g.py * (x - 1);
+                pLl = ph[par][0][lane + 1];
+                alL = a.alpha_in[eL];
+                gL = a.q2v[eL];
+                if (((x - 1) % fg.XB) == fg.XB - 1) sxL = a.sx[(tl * fg.nxblk + ((x - 1) / fg.XB + 1)) * g.ny + y];
+            }
+            double pBl = 0.0, alB = 0.0, gB = 0.0, syB = 0.0;
+            if (belowTile) {
+                const i64 eB = g.offBy + g.byLayer * tl + (y - 1) + g.pyb * x;
+                pBl = ph[par][xl + 1][0];
+                alB = a.alpha_in[eB];
+                gB = a.q2v[eB];
+                if (((y - 1) & 63) == 63) syB = a.sy[(tl * g.nx + x) * fg.nyblk + ((y - 1) / 64 + 1)];
+            }
+            // ---------------- arithmetic ----------------
+            if (sxOwn) gX = c.sf * (gX + sxv);
+            if (syOwn) gY = c.sf * (gY + syv);
+            double pT = 0.0, u0 = 0.0, ubx = 0.0, uby = 0.0;
+            double a0n = 0.0, qXn = 0.0, aXn = 0.0, qYn = 0.0, aYn = 0.0;
+            if (hasCell) {
+                pT = pTl;
+                double tmp = (-c.at) * p0;
+                tmp += c.at * pT;
+                q_calc<false, 0>(c, tmp, g0, c.c1, c.dinv1, 1.0, al0, ap, q0n, a0n, u0);
+            }
+            if (hasBx) {
+                double tmp = (-c.ax) * p0;
+                tmp += c.ax * pXl;
+                q_calc<false, 0>(c, tmp, gX, dc, di, 1.0, alX, ap, qXn, aXn, ubx);
+            }
+            if (hasBy) {
+                double tmp = (-c.ay) * p0;
+                tmp += c.ay * pYl;
+                q_calc<false, 0>(c, tmp, gY, dc, di, 1.0, alY, ap, qYn, aYn, uby);
+            }
+            double ubx_l = 0.0, qL = 0.0, uby_b = 0.0, qB = 0.0;
+            if (leftTile) {
+                double q2 = gL;
+                if (((x - 1) % fg.XB) == fg.XB - 1) q2 = c.sf * (q2 + sxL);
+                double tmp = (-c.ax) * pLl;
+                tmp += c.ax * p0;
+                double an;
+                q_calc<false, 0>(c, tmp, q2, dc, di, 1.0, alL, ap, qL, an, ubx_l);
+            }
+            if (belowTile) {
+                double q2 = gB;
+                if (((y - 1) & 63) == 63) q2 = c.sf * (q2 + syB);
+                double tmp = (-c.ay) * pBl;
+                tmp += c.ay * p0;
+                double an;
+                q_calc<false, 0>(c, tmp, q2, dc, di, 1.0, alB, ap, qB, an, uby_b);
+            }
+            // ---------------- stores ----------------
+            if (own) {
+                if (hasCell) {
+                    a.alpha_out[node] = a0n;
+                    if (!GOUT) a.q_out[node] = q0n;
+                }
+                if (hasBx) {
+                    a.alpha_out[eX] = aXn;
+                    if (!GOUT) a.q_out[eX] = qXn;
+                }
+                if (hasBy) {
+                    a.alpha_out[eY] = aYn;
+                    if (!GOUT) a.q_out[eY] = qYn;
+                }
+            }
+            xch[par][xl][lane] = make_double2(ubx, qXn);
+            ph[par ^ 1][xl + 1][lane + 1] = pTl;
+            if (xl == XB - 1) ph[par ^ 1][XB + 1][lane + 1] = hx;
+            if (xl == 0) ph[par ^ 1][0][lane + 1] = hl;
+            if (lane == TILE_Y - 1) ph[par ^ 1][xl + 1][TILE_Y + 1] = hy;
+            if (lane == 0) ph[par ^ 1][xl + 1][0] = hb;
+            __syncthreads();
+            double uby_m = __shfl_up(uby, 1, 64);
+            double qY_m = __shfl_up(qYn, 1, 64);
+            if (inb) {
+                double ubx_m = 0.0, qX_m = 0.0;
+                if (x >= 1) {
+                    if (xl > 0) {
+                        const double2 r = xch[par][xl - 1][lane];
+                        ubx_m = r.x;
+                        qX_m = r.y;
+                    } else {            // edge owned by the tile to the left
+                        ubx_m = ubx_l;
+                        qX_m = qL;
+                    }
+                }
+                if (belowTile) {        // edge owned by the tile below
+                    uby_m = uby_b;
+                    qY_m = qB;
+                }
+                if (own) {
+                    double r = 0.0;
+                    if (tl >= 1) r += c.at * u0prev;
+                    if (tl < g.ncl) r += (-c.at) * u0;
+                    if (x >= 1) r += c.ax * ubx_m;
+                    if (x <= g.nx - 2) r += (-c.ax) * ubx;
+                    if (y >= 1) r += c.ay * uby_m;
+                    if (y <= g.ny - 2) r += (-c.ay) * uby;
+                    a.rhs[node] = r + cv;
+                }
+                // the four edges around cell column (y, x) at layer tl, as load_edges() returns them
+                ecur.xm = (x >= 1) ? c.sf * qX_m : 0.0;
+                ecur.xp = (x <= g.nx - 2) ? c.sf * qXn : 0.0;
+                ecur.ym = (y >= 1) ? c.sf * qY_m : 0.0;
+                ecur.yp = (y <= g.ny - 2) ? c.sf * qYn : 0.0;
+            }
+            u0prev = u0;
+            p0 = pT;
+            par ^= 1;
+        }
+        if (tl > tstart) {
+            // ======== cone cell tl - 1: k_cone_fused<1, 4, NT, true, GOUT>, then edge layer tl - 1 of the gather ========
+            double w[10];
+            if (hasC) {
+                double v[10];
+                build_z2(v, q0c, eprev, ecur, c.s, c.dF);
+#pragma unroll
+                for (int j = 0; j < 10; ++j) b[j] = mult_finish(b[j], v[j], c.tau);
+                if (!GOUT && own && inb) {
+#pragma unroll
+                    for (int j = 0; j < 10; ++j) st_stream<NT>(a.beta_out + j * g.Nc + ci, b[j]);
+                }
+#pragma unroll
+                for (int j = 0; j < 10; ++j) v[j] = v[j] - b[j];
+                proj_row<10>(v);
+                if (GOUT && own && inb) {
+#pragma unroll
+                    for (int j = 0; j < 10; ++j) st_stream<NT>(a.beta_out + j * g.Nc + ci, mult_carry(b[j], v[j], c.tau));
+                }
+#pragma unroll
+                for (int j = 0; j < 10; ++j) w[j] = v[j] + b[j];
+                if (own && inb) a.q2_out[ci] = c.s * (w[9] - w[0]);
+            } else {
+#pragma unroll
+                for (int j = 0; j < 10; ++j) w[j] = 0.0;
+            }
+            gather_emit<XB>(g, c.sf, gch, gc, w, tl - 1, own && inb, x, y, xl, lane, nxblk, nyblk, blk.y, blk.x, a.q2_out,
+                            a.sx_out, a.sy_out);
+        }
+        eprev = ecur;
+        q0c = q0n;
+    }
+}
+
+i64 qcone_chunk_len(const Grid &g) {
+    i64 TC = g.ntl;                                       // one chunk per tile (measured)
+    if (const char *e = getenv("DOTSOCP_QCONE_TC")) {     // read per launch: the tests switch it inside one process
+        const i64 n = atoll(e);
+        if (n >= 1) TC = n;
+    }
+    return TC < g.ntl ? TC : g.ntl;
+}
+
+int launch_qcone(const Grid &g, const LoopCoef &c, const FusedGeom &fg, QConeArgs a, bool gout, hipStream_t st) {
+    if (fg.XB != TILE_X || !(g.first && g.last) || g.ncl < 1) { set_error("internal: k_qcone on a grid it does not serve"); return DOTSOCP_ESTATE; }
+    a.TC = qcone_chunk_len(g);
+    const i64 chunks = (g.ntl + a.TC - 1) / a.TC;
+    dim3 grid((unsigned)fg.nyblk, (unsigned)fg.nxblk, (unsigned)chunks);
+    dim3 blk(TILE_Y, TILE_X);
+    const bool nt = stream_nt_enabled();
+    if (gout) {
+        if (nt) DS_KLAUNCH((k_qcone<true, true>), grid, blk, 0, st, g, c, fg, a);
+        else DS_KLAUNCH((k_qcone<false, true>), grid, blk, 0, st, g, c, fg, a);
+    } else {
+        if (nt) DS_KLAUNCH((k_qcone<true, false>), grid, blk, 0, st, g, c, fg, a);
+        else DS_KLAUNCH((k_qcone<false, false>), grid, blk, 0, st, g, c, fg, a);
+    }
     DS_HIP(hipGetLastError());
     return 0;
 }

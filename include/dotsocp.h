@@ -224,6 +224,14 @@ int dotsocp_dct_algorithm(dotsocp_i64 n);
 int dotsocp_cone_writes_beta(dotsocp_i64 it, double last_sigma_it, dotsocp_i64 maxit, int check_step_by_step,
                              int last_of_run, int rescale, double maxFeas, double relGap);
 int dotsocp_rescale_due(dotsocp_i64 it, int rescale, double maxFeas, double relGap);
+/* The early cone pass (pure host arithmetic, no device): may the q-step of iteration `it` also run the cone pass of
+ * iteration it + 1, and in which form?  0: no -- the pass of `it` writes beta (dotsocp_cone_writes_beta), a reader of beta
+ * or q follows it.  Otherwise the pass of `it` left gamma, so `it` has no check and every argument is what iteration
+ * it + 1 will find: 1 (steady) the early pass writes gamma and q is not stored, 2 (exit) it writes beta and q, because
+ * dotsocp_cone_writes_beta(it + 1, ..., next_last_of_run, ...) holds.  The solver adds what only it knows: one slab,
+ * inPALM / ALG2 without a weight, no time limit passed, the switch DOTSOCP_QCONE. */
+int dotsocp_qcone_form(dotsocp_i64 it, double last_sigma_it, dotsocp_i64 maxit, int check_step_by_step, int last_of_run,
+                       int next_last_of_run, int rescale, double maxFeas, double relGap);
 
 int dotsocp_upload(dotsocp_ctx *ctx, int field, const double *host);
 int dotsocp_download(dotsocp_ctx *ctx, int field, double *host);
@@ -277,7 +285,8 @@ int dotsocp_get_history(dotsocp_ctx *ctx, double *kkt, double *time, double *ite
  * dotsocp_kernel_time: average device time in ms of the named kernel family over the profiled launches since
  * begin(), and their count; names: "rhs", "poisson", "cone_proj", "qstep", "beta", "kkt", "cone_fused_a",
  * "cone_fused_b", "materialise", "comm", "interp", "acc_cone", "acc_gather", "qstep_first", "transpose", "cone_carry"
- * (the cone passes that read gamma and no q^{k-1}; "cone_fused_b" keeps the passes that move 8 (20 Nz + 3 Nq) bytes). */
+ * (the cone passes that read gamma and no q^{k-1}; "cone_fused_b" keeps the passes that move 8 (20 Nz + 3 Nq) bytes),
+ * "qcone" (a q-step with the next iteration's gamma-reading cone pass in the same kernel: counted here alone). */
 int dotsocp_set_profiling(dotsocp_ctx *ctx, int on);
 int dotsocp_kernel_time(dotsocp_ctx *ctx, const char *name, double *avg_ms, dotsocp_i64 *launches);
 

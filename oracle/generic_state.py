@@ -1,0 +1,184 @@
+"""One generic start for the loops: phi, q, z, alpha, beta with no vanishing term and all three
+branches of the cone projection populated.
+
+TEST INFRASTRUCTURE (see oracle/__init__.py).  The all-zero state of initialize.m is special: on an
+`example1` trajectory started from it the polar branch of mexProjSoc (||x_bar|| <= -x_1, result 0) is
+never taken and KKT column 5 stays at rounding noise.  The recipe here is the one of the random-state
+tests (tests/test_gpu_solver.py::test_iterations_from_a_random_state) with one addition: each cone row
+is drawn into one of three classes, and its first multiplier entry is pushed by +SHIFT (the row's
+argument z2 - beta then lies in the polar cone), by -SHIFT (inside the cone) or left alone (mostly on
+the surface branch).  tests/test_generic_state_conditions.py asserts, with the oracle alone, that the
+free-running loops started here do visit every branch and keep every KKT column away from zero.
+"""
+import numpy as np
+
+from . import mexops
+
+FIELDS = ("phi", "q", "z", "alpha", "beta")
+AMPLITUDES = {"phi": 1.0, "q": 0.3, "z": 0.6, "alpha": 0.5, "beta": 0.4}
+SHIFT = 3.0
+DEFAULT_SEED = 2357
+
+
+def cone_holes(var, dims):
+    """Boolean mask of the slots of z / beta that mexBFd (2-D: dims = (ny, nx, nt)) or mexBFd1d
+    (dims = (nx, nt)) leaves unwritten: cone rows at the domain boundary have no edge there."""
+    probe = np.full(np.shape(var.beta), np.nan, order="F")
+    q = np.zeros(np.size(var.q))
+    if len(dims) == 2:
+        nx, nt = dims
+        mexops.mexBFd1d(probe, q, nt, nx)
+    else:
+        ny, nx, nt = dims
+        mexops.mexBFd(probe, q, nt, nx, ny)
+    hole = np.isnan(probe)
+    assert 0 < hole.sum() < probe.size // 4
+    return hole
+
+
+def generic_state(var, dims, seed=DEFAULT_SEED, amplitudes=None, shift=SHIFT):
+    """The start as a dict of new arrays shaped like the fields of `var` (a level after InitialScaling).
+
+    N(0,1) times the amplitude of each field; the row classes 0 / 1 / 2 with equal probability
+    (1: beta[row, 0] += shift, 2: beta[row, 0] -= shift); z and beta zero in the slots mexBFd leaves
+    unwritten -- the reference never makes them non-zero, and its KKT block reads what an earlier
+    projection left in such slots of a shared temporary (tests/test_gpu_solver.py gives the lines)."""
+    amp = dict(AMPLITUDES, **(amplitudes or {}))
+    rng = np.random.default_rng(seed)
+    start = {}
+    for f in ("phi", "q", "alpha", "z", "beta"):
+        shape = np.shape(getattr(var, f))
+        start[f] = np.asfortranarray(amp[f] * rng.standard_normal(shape))
+    rows = start["beta"].shape[0]
+    cls = rng.integers(0, 3, size=rows)
+    start["beta"][cls == 1, 0] += shift
+    start["beta"][cls == 2, 0] -= shift
+    hole = cone_holes(var, dims)
+    start["z"][hole] = 0.0
+    start["beta"][hole] = 0.0
+    return start
+
+
+def perturbed(start, seed=1, eps=2.0 ** -52):
+    """Every entry times (1 + eps N(0,1)): the one-ulp perturbation the sensitivity check uses (zeros stay zero)."""
+    rng = np.random.default_rng(seed)
+    return {f: np.asfortranarray(a * (1.0 + eps * rng.standard_normal(a.shape))) for f, a in start.items()}
+
+
+def set_state(var, start):
+    """Copies of the start into the fields of `var` (an oracle level or a device-side one alike)."""
+    for f in FIELDS:
+        setattr(var, f, start[f].copy(order="F"))
+
+
+# --------------------------------------------------------------------------------------------------
+# The cases the generic-start tests run (tests/test_generic_state_conditions.py on the CPU asserts for each that the
+# start does its job; tests/test_gpu_generic_state.py compares the device loops with the same oracle runs).
+# shape: (ny, nx, nt), or (nx, nt) for the 1-D problem.  Every entry may carry seed / amplitudes / shift of its own.
+# --------------------------------------------------------------------------------------------------
+CASES = {
+    "inPALM-130x9x7": dict(method="inPALM", shape=(130, 9, 7), K=12),
+    "inPALM-66x10x6": dict(method="inPALM", shape=(66, 10, 6), K=25),
+    "inPALM-100x70x20": dict(method="inPALM", shape=(100, 70, 20), K=25),
+    "inPALM-1d-150x7": dict(method="inPALM", shape=(150, 7), K=12),
+    # The cases below miss a condition with the plain recipe (the polar rows die out within three iterations), so each
+    # has amplitudes of its own; the thresholds of tests/test_generic_state_conditions.py are the same for all.
+    # 13 layers: a wider class offset and a larger alpha keep polar rows alive through iterations 3..7
+    "inPALM-40x12x13": dict(method="inPALM", shape=(40, 12, 13), K=12, shift=20.0, amplitudes=dict(alpha=2.5)),        # the time-slab grid
+    # 1e6 weights: with q of the plain size KKT column 5 moves by 3e-12 relative under one-ulp perturbations (w q
+    # cancels against A phi in the alpha update); a smaller q brings that to 1e-13.  Past iteration 12 column 4 falls
+    # to 1e-3.
+    "inPALM-weighted-66x10x6": dict(method="inPALM", shape=(66, 10, 6), K=12, weighted=True, shift=20.0,
+                                    amplitudes=dict(alpha=2.5, q=0.03)),
+    # tau = 1: -beta lands in the cone after every multiplier step, so polar rows survive only behind a wide offset
+    "ALG2-66x10x6": dict(method="ALG2", shape=(66, 10, 6), K=12, shift=20.0),
+    # PALM and acc-ADMM recompute q from A phi before their first projection: a phi of size 1 makes q of size 30 and
+    # every row a surface row; PALM's polar rows are gone after iteration 7
+    "PALM-66x10x6": dict(method="PALM", shape=(66, 10, 6), K=7, shift=20.0, amplitudes=dict(phi=0.02, beta=0.1)),
+    "acc-ADMM-66x10x6": dict(method="acc-ADMM", shape=(66, 10, 6), K=12, shift=20.0, amplitudes=dict(phi=0.02)),
+}
+
+# KKT column 5 (index 4), sigma ||F*B*beta + D_w alpha||, is zero in exact arithmetic for the loops whose multiplier step
+# has length 1 (ALG2: tau = 1, acc-ADMM): there the q-step's optimality condition diagQ q = A phi + alpha + F*B*(z + beta)
+# and diagQ = I + F*B*BF give F*B*beta^+ + alpha^+ = 0 identically, whatever the data.  No start makes it generic; it is
+# rounding noise (1e-16) that moves by O(1) relative under a one-ulp perturbation, and is held to an absolute bound instead.
+CANCELLING_COLUMNS = {"ALG2": (4,), "acc-ADMM": (4,)}
+
+
+def problem(case):
+    """(rho0, rho1, nt, weight) of a case: `example1` / the 1-D Gaussians, the circle-pillar barrier when weighted."""
+    from .examples import (ensure_barrier_validity, gene_barrier_of_circle_pillar, get_example_1d, get_example_2d,
+                           get_weight_by_barrier)
+    spec = CASES[case]
+    shape = spec["shape"]
+    if len(shape) == 2:
+        rho0, rho1 = get_example_1d("gaussian", shape[0])
+        return rho0, rho1, shape[1], None
+    ny, nx, nt = shape
+    rho0, rho1 = get_example_2d("example1", ny, nx)          # arrays of shape (ny, nx)
+    weight = None
+    if spec.get("weighted"):
+        barrier = gene_barrier_of_circle_pillar()
+        weight = get_weight_by_barrier(nx, ny, nt, barrier)
+        rho0, rho1, _ = ensure_barrier_validity(rho0, rho1, barrier)
+    return rho0, rho1, nt, weight
+
+
+def case_opts(case):
+    return dict(tol=0.0, maxit=CASES[case]["K"])
+
+
+def case_start(case, var):
+    spec = CASES[case]
+    return generic_state(var, spec["shape"], seed=spec.get("seed", DEFAULT_SEED), amplitudes=spec.get("amplitudes"),
+                         shift=spec.get("shift", SHIFT))
+
+
+def branch_shares(inp):
+    """Share of the rows of a mexProjSoc argument in each branch (oracle/mex_kernels.c: oracle_proj_soc):
+    (polar: result 0, inside: the row itself, surface: the scaled row)."""
+    n = np.sqrt(np.sum(inp[:, 1:] ** 2, axis=1))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        c = (inp[:, 0] / n + 1.0) * 0.5
+    polar, inside = np.mean(c <= 0.0), np.mean(c >= 1.0)
+    return polar, inside, 1.0 - polar - inside
+
+
+_runs = {}
+
+
+def oracle_run(case, perturb=False):
+    """The oracle's free-running loop of a case from its generic start, computed once per process and shared (treat
+    the result as read-only).  Returns a dict: var (the finished level), start, hist, sigma, shares (one
+    (polar, inside, surface) triple per z-step projection, the projection inside the KKT block not counted),
+    weight, and the level's opts."""
+    key = (case, bool(perturb))
+    if key in _runs:
+        return _runs[key]
+    from . import driver as OD
+    spec = CASES[case]
+    rho0, rho1, nt, weight = problem(case)
+    var, model, o = OD.make_level(rho0, rho1, nt, case_opts(case), spec["method"], weight)
+    start = case_start(case, var)
+    if perturb:
+        start = perturbed(start)
+    set_state(var, start)
+    st = OD.make_state(var, o, model, spec["method"], weighted=weight is not None)
+    shares = []
+    plain = mexops.mexProjSoc
+
+    def counting(out, inp):
+        if out is st.z:                      # the z-step; the KKT block projects into the temporary z2
+            shares.append(branch_shares(inp))
+        plain(out, inp)
+
+    mexops.mexProjSoc = counting
+    try:
+        st.run()
+    finally:
+        mexops.mexProjSoc = plain
+    hist, sigma = st.finish()
+    for f in FIELDS:
+        getattr(var, f).flags.writeable = False
+    _runs[key] = dict(var=var, start=start, hist=hist, sigma=sigma, shares=np.array(shares), weight=weight, opts=o)
+    return _runs[key]

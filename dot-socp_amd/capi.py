@@ -73,6 +73,7 @@ SYMBOLS = {
     "dotsocp_slab_range": (ctypes.c_int, [i64, ctypes.c_int, ctypes.c_int, ctypes.POINTER(i64), ctypes.POINTER(i64)]),
     "dotsocp_field_len": (i64, [ctypes.POINTER(Problem), ctypes.c_int]),
     "dotsocp_dct_algorithm": (ctypes.c_int, [i64]),
+    "dotsocp_tsolve_tri_safe": (ctypes.c_int, [i64, i64, i64]),
     "dotsocp_cone_writes_beta": (ctypes.c_int, [i64, dbl, i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, dbl, dbl]),
     "dotsocp_rescale_due": (ctypes.c_int, [i64, ctypes.c_int, dbl, dbl]),
     "dotsocp_qcone_form": (ctypes.c_int, [i64, dbl, i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, dbl, dbl]),
@@ -90,6 +91,7 @@ SYMBOLS = {
     "dotsocp_set_profiling": (ctypes.c_int, [vp, ctypes.c_int]),
     "dotsocp_kernel_time": (ctypes.c_int, [vp, ctypes.c_char_p, ctypes.POINTER(dbl), ctypes.POINTER(i64)]),
     "dotsocp_canary_check": (ctypes.c_int, []),
+    "dotsocp_poisson_phi": (ctypes.c_int, [vp]),
     "dotsocp_synchronize": (ctypes.c_int, [vp]),
 }
 

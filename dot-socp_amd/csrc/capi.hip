@@ -288,6 +288,7 @@ int dotsocp_attach_rccl(dotsocp_ctx *ctx, const unsigned char id[128], int rank,
     } while (0)
 
 int dotsocp_dct_algorithm(dotsocp_i64 n) { return dct_choose_algorithm(n); }
+int dotsocp_tsolve_tri_safe(dotsocp_i64 ny, dotsocp_i64 nx, dotsocp_i64 nt) { return tsolve_tri_safe(ny, nx, nt) ? 1 : 0; }
 
 int dotsocp_cone_writes_beta(dotsocp_i64 it, double last_sigma_it, dotsocp_i64 maxit, int check_step_by_step,
                              int last_of_run, int rescale, double maxFeas, double relGap) {
@@ -386,6 +387,8 @@ int dotsocp_canary_check(void) {
     if (bad) set_error("canary: %d device buffer(s) written out of bounds: %s", bad, rep.c_str());
     return bad;
 }
+
+int dotsocp_poisson_phi(dotsocp_ctx *ctx) { CTX_OR_FAIL(); return ctx->s.poisson_phi(); }
 
 int dotsocp_synchronize(dotsocp_ctx *ctx) {
     CTX_OR_FAIL();

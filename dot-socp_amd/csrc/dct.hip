@@ -213,7 +213,7 @@ bool tsolve_tri_allowed() {
 int launch_poisson_t_single(const DctPlan *pt, const Grid &g, double kscale, const double *cy, const double *cx,
                             const double *ct, double *p, double *p2, i64 pitch0, hipStream_t st, bool allow_tri) {
     const i64 ny = g.ny, nx = g.nx, nt = g.nt;
-    if (allow_tri && tsolve_tri_preferred(nt, dct_plan_is_pow2(pt), g.plane))
+    if (allow_tri && tsolve_tri_preferred(nt, dct_plan_is_pow2(pt), g.plane) && tsolve_tri_safe(ny, nx, nt))
         // no transform along t: the (ky, kx) modes are tridiagonal systems in t (tri.hip: k_tsolve_single / _pipe)
         return launch_tsolve_tri(g, nt, kscale, cy, cx, p, st);
     if (dct_plan_has_tsolve(pt))

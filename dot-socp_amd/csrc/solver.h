@@ -339,6 +339,7 @@ struct Solver {
     int step(bool *brk);
     int rescale_block();
     int poisson_all(const PhiHooks *hooks = nullptr);
+    int poisson_phi();               // test support: poisson_all() on the phi field, before begin()
     int phase_phi(const PhiHooks *hooks = nullptr);
     // part 0: all chunks; 1: all but the last chunk; 2: the last chunk (the only one that reads the q halo)
     int phase_z(int part = 0);

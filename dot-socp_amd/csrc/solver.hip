@@ -282,6 +282,19 @@ int Solver::poisson_all(const PhiHooks *hooks) {
     return 0;
 }
 
+// Test support (dotsocp_poisson_phi): phi <- the loop's own Poisson solve of phi, on whatever slabs this context holds.
+// Between create and begin only: the loop's state is not touched, w0 / w1 and the solve's messages are free then.
+int Solver::poisson_phi() {
+    if (begun) { set_error("poisson_phi() must precede begin()"); return DOTSOCP_ESTATE; }
+    cur_dev = -1;
+    DS_CHECK(use_dev(device));
+    DS_CHECK(ensure_alloc());
+    D = prob.D;                      // what begin() sets; poisson_all() divides by D^2 * kernel
+    FOR_SLABS(s) DS_HIP(ds_memcpy_async(s.w0, s.phi, sizeof(double) * (size_t)s.g.Nphi, hipMemcpyDeviceToDevice, s.st));
+    DS_CHECK(poisson_all(nullptr));
+    return sync_all();
+}
+
 int Solver::phase_phi(const PhiHooks *hooks) {
     DS_CHECK(ensure_halo());
     if (multi() && !u0_fresh) {      // normally shipped with the q halo at the end of the previous iteration

@@ -485,6 +485,14 @@ int Solver::tri_exchange(bool back) {
 // once both have been joined (more messages for the second streams).
 int Solver::poisson_t_tridiag(const PhiHooks *hooks) {
     const i64 plane = slabs[0].g.plane;
+    // the (0, 0) line of a slab travels whole in the TRI_EXTRA doubles behind a message (poisson_all asks before it calls)
+    for (i64 p = 0, a, b; p < world; ++p) {
+        dotsocp_slab_range_impl(nt, world, (int)p, &a, &b);
+        if (b - a > TRI_EXTRA) {
+            set_error("partitioned t-solve: slab %d has %lld time nodes, a message holds %d", (int)p, (long long)(b - a), TRI_EXTRA);
+            return DOTSOCP_EINVAL;
+        }
+    }
     DS_CHECK(tri_alloc());
     PencilCuts pc{};
     std::vector<i64> slab_n;

@@ -19,6 +19,7 @@
 #include "device_utils.h"
 #include "kernels.h"
 
+#include <cmath>
 #include <cstdint>
 #include <cstdlib>
 #include <mutex>
@@ -114,7 +115,21 @@ __device__ __forceinline__ double tri_last(const TriCoef &c, double D, double N1
 // Both sweeps of a column come out of two running sums, H_t = g_t + rho H_{t-1} and G_t = sum_{s <= t} rho^s g_s:
 //     D_t = sum_{s <= t} rho^(t-s) N_s g_s = H_t + s_f pe_f rho^t G_t            (front sweep, kept per row by k_tri_final)
 //     F   = sum_t rho^t N'_{n-1-t} g_t     = G_{n-1} + s_b pe_b rho^(n-1) H_{n-1}  (back sweep, as a weighted sum)
-// -- no power ever has to be walked downwards from a value that may have underflowed.
+// -- neither sum needs a power walked back up from a value that may have underflowed.  The BACKWARD sweep of k_tri_final
+// does: it forms N_t = 1 + s pe rho^(2t) from rho^t walked up from rho^(n-1) (pw *= r), and rho^(n-1) leaves the normal
+// range once (n - 1) log10(r) > 308 -- slabs of more than 64 nodes with a' = (CY + CX) / (nt-1)^2 in the hundreds, e.g.
+// 2048 x 2048 x 256 on two GPUs.  From a zero the walk stays zero and every N_t, t >= 1, came out as 1 (errors of 1e-7 of
+// a high mode); from a denormal it carries that value's few bits.  So the forward sweep remembers the last row t* whose
+// power was still >= TRI_PW_SAFE, and its value: behind t* N_t IS 1 in double (rho^(2t) < 2^-1000), at t* the walk resumes
+// from the remembered value.  Where rho^(n-1) >= TRI_PW_SAFE, t* = n - 1 and the arithmetic is what it always was.
+// (k_tsolve_single / k_tsolve_pipe walk the same way -- and put the left interface in as xl N_0 rho^t, so a lost power costs
+// them that whole term -- over pieces of n = ceil(nt / NSUB) <= 64 rows.  rho^(n-1) < 2^-1022 needs
+// r > 2^(1022 / (n-1)): 7.6e4 on 64 rows (nt >= 505), 2e9 on 34 (nt = 136 or 272), and r ~ a' <= 4 ((ny-1)^2 + (nx-1)^2) / (nt-1)^2:
+// no 2-D grid that fits a device, but a 1-D grid from 70 000 space points at nt = 505 .. 511.  Those kernels keep their
+// arithmetic -- they are the flagship's t solve -- and are not launched there: tsolve_tri_safe(), asked by
+// launch_poisson_t_single, sends every grid whose largest a' could take rho^(n-1) below TRI_PW_SAFE to the transform passes
+// along t, which exist for every length.)
+#define TRI_PW_SAFE 0x1p-500
 // first / last entries of A_p^-1 e_first (vf, vl) and A_p^-1 e_last (wf, wl) of a block of n rows:
 // prod_{s < n-1} 1 / piv_s = rho^(n-1) N_0 / N_{n-1}, 1 / piv_{n-1} = rho N_{n-1} / N_n (boundary end: N_{n-1} / (r N_n - N_{n-1}))
 struct TriSpike {
@@ -268,7 +283,8 @@ __global__ void __launch_bounds__(128) k_tri_reduced(TriGeom g, TriReduced q, co
 }
 
 // A_p x = g + e_first x_left + e_last x_right: forward D_t from the two running sums (no division), backward
-// x_t = rho (D_t + N_t x_{t+1}) / N_{t+1} (one fast division per row), N_t = 1 + s pe rho^(2t) from rho^t walked back up.
+// x_t = rho (D_t + N_t x_{t+1}) / N_{t+1} (one fast division per row), N_t = 1 + s pe rho^(2t) from rho^t walked back up
+// from the last row at which it was still >= TRI_PW_SAFE (see above).
 // Generic slab length: D_t is parked in x between the sweeps (two reads and two writes of the slab).
 __global__ void __launch_bounds__(256) k_tri_final(TriGeom g, const double *__restrict__ back, double *__restrict__ x) {
     const i64 m = (i64)blockIdx.x * 256 + threadIdx.x;
@@ -286,6 +302,8 @@ __global__ void __launch_bounds__(256) k_tri_final(TriGeom g, const double *__re
     const double xl = back[off + (m - g.pc.cut[j])], xr = back[off + w + (m - g.pc.cut[j])];
     const double spe = first ? c.rho : -c.rho2;                     // s pe of the front sequence
     double H = 0.0, G = 0.0, pw = 1.0, D = 0.0;
+    int ts = 0;                                                     // last row with rho^t >= TRI_PW_SAFE, and that power
+    double pws = 1.0;
     for (int t = 0; t < n; ++t) {
         double gt = x[m + g.plane * t] * sc;
         if (t == 0) gt += xl;
@@ -294,15 +312,17 @@ __global__ void __launch_bounds__(256) k_tri_final(TriGeom g, const double *__re
         G += pw * gt;
         D = H + (spe * pw) * G;
         x[m + g.plane * t] = D;
+        if (pw >= TRI_PW_SAFE) { ts = t; pws = pw; }
         if (t + 1 < n) pw *= c.rho;
     }
     const TriEnds f = tri_ends(c, first, n, pw);
     double xn = tri_last(c, D, f.N1, f.Nn, last);
     x[m + g.plane * (n - 1)] = xn;
     double Nt1 = f.N1;
+    pw = pws;                                                       // (= rho^(n-1) unless that fell below TRI_PW_SAFE)
     for (int t = n - 2; t >= 0; --t) {
-        pw *= c.r;
-        const double Nt = (t == 0) ? f.N0 : 1.0 + spe * (pw * pw);
+        if (t < ts) pw *= c.r;
+        const double Nt = (t == 0) ? f.N0 : ((t > ts) ? 1.0 : 1.0 + spe * (pw * pw));
         xn = tri_div(c.rho * (x[m + g.plane * t] + Nt * xn), Nt1);
         x[m + g.plane * t] = xn;
         Nt1 = Nt;
@@ -331,6 +351,8 @@ __global__ void __launch_bounds__(256) k_tri_final_reg(TriGeom g, const double *
     for (int t = 0; t < NTL; ++t) X[t] = (t < n) ? x[m + g.plane * t] : 0.0;
     const double spe = first ? c.rho : -c.rho2;
     double H = 0.0, G = 0.0, pw = 1.0, D = 0.0;
+    int ts = 0;                                                     // as in k_tri_final
+    double pws = 1.0;
 #pragma unroll
     for (int t = 0; t < NTL; ++t) {
         if (t < n) {
@@ -341,19 +363,21 @@ __global__ void __launch_bounds__(256) k_tri_final_reg(TriGeom g, const double *
             G += pw * gt;
             D = H + (spe * pw) * G;
             X[t] = D;
+            if (pw >= TRI_PW_SAFE) { ts = t; pws = pw; }
             if (t + 1 < n) pw *= c.rho;
         }
     }
     const TriEnds f = tri_ends(c, first, n, pw);
     double xn = tri_last(c, D, f.N1, f.Nn, last);
     double Nt1 = f.N1;
+    pw = pws;
 #pragma unroll
     for (int t = NTL - 1; t >= 0; --t) {
         if (t == n - 1) {
             X[t] = xn;
         } else if (t < n - 1) {
-            pw *= c.r;
-            const double Nt = (t == 0) ? f.N0 : 1.0 + spe * (pw * pw);
+            if (t < ts) pw *= c.r;
+            const double Nt = (t == 0) ? f.N0 : ((t > ts) ? 1.0 : 1.0 + spe * (pw * pw));
             xn = tri_div(c.rho * (X[t] + Nt * xn), Nt1);
             X[t] = xn;
             Nt1 = Nt;
@@ -767,6 +791,22 @@ static int tri_device_cus() {
 }
 
 bool tsolve_tri_supported(i64 nt) { return nt >= 2 && nt <= 512; }
+
+// wavefronts (= pieces of a column) of the kernel launch_tsolve_tri picks for nt: the table of TSOLVE() below; k_tsolve_pipe: 4
+static int tsolve_nsub(i64 nt) { return nt <= 8 ? 1 : (nt <= 32 ? 2 : (nt <= 136 ? 4 : 8)); }
+
+// Do the powers rho^t of every mode stay >= TRI_PW_SAFE over a piece (n = ceil(nt / NSUB) rows)?  The backward sweeps of
+// k_tsolve_single / k_tsolve_pipe walk rho^t back up from rho^(n-1) and are wrong once that has left the normal range (see
+// TRI_PW_SAFE).  Largest a': CY, CX <= 4 (n-1)^2.  Pure host arithmetic (dotsocp_tsolve_tri_safe).
+bool tsolve_tri_safe(i64 ny, i64 nx, i64 nt) {
+    if (!tsolve_tri_supported(nt)) return false;
+    const int nsub = tsolve_nsub(nt);
+    const double n = (double)((nt + nsub - 1) / nsub);
+    const double ap = 4.0 * ((double)(ny - 1) * (double)(ny - 1) + (double)(nx - 1) * (double)(nx - 1)) /
+                      ((double)(nt - 1) * (double)(nt - 1));
+    const double r = 1.0 + 0.5 * ap + sqrt(ap * (1.0 + 0.25 * ap));     // tri_coef
+    return (n - 1.0) * log2(r) <= 500.0;
+}
 
 static bool tsolve_pipe_on() {
     const char *pe = getenv("DOTSOCP_TS_PIPE");        // read per call: the tests switch it inside one process

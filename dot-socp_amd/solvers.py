@@ -405,3 +405,42 @@ def solver_wdotsocp2d(rho0, rho1, nt, levelN, opts, method="inPALM", barrier=Non
     if not check_massConservation(output["rho"], 1e-2):
         print("Warning: The tolerance of mass conservation constraint is under 0.01")
     return output, timeML, runHistML, runHist
+
+
+def poisson_on_slabs(rhs, D, nslabs=1, ngpu=None, dim=2, device=0, repeat=None):
+    """Test support: idctn(dctn(rhs) ./ (D^2 * initialize_FFTkernel)) by the loop's own Poisson solve
+    (dotsocp_poisson_phi: Solver::poisson_all) on a context cut into `nslabs` time slabs on one device, or `ngpu` slabs
+    with their own streams (dotsocp_create_multi).  rhs: (ny, nx, nt) Fortran array; dim=1: the 1-D grid nx1d x nt as
+    (nx1d, 1, nt).  The context is built from the shape and D alone -- no densities.
+    Two arguments beyond that: `device`, the HIP device (ngpu: the first one); and `repeat`, a list of further
+    right-hand sides of the same shape solved one after the other on the SAME context (the mode probes solve several
+    bands per layout and would otherwise create the slabs once per band).  Without `repeat` the result is the solved
+    array; WITH it the return type changes: a list, [solution of rhs] + [solutions of repeat], in that order."""
+    L = capi.lib()
+    rhs = np.asfortranarray(rhs, dtype=np.float64)
+    if rhs.ndim != 3 or (dim == 1 and rhs.shape[1] != 1) or dim not in (1, 2):
+        raise ValueError("rhs must be an (ny, nx, nt) array (dim=1: (nx1d, 1, nt))")
+    ny, nx, nt = rhs.shape
+    p = capi.Problem()
+    p.dim, p.weighted = int(dim), 0
+    p.ny, p.nx, p.nt = (1, ny, nt) if dim == 1 else (ny, nx, nt)
+    p.D, p.E, p.cScale, p.dScale, p.normc, p.normd = float(D), 1.0, 1.0, 1.0, 1.0, 1.0
+    if ngpu is not None and int(ngpu) > 1:
+        ctx = L.dotsocp_create_multi(ctypes.byref(p), int(device), int(ngpu))
+    else:
+        ctx = L.dotsocp_create(ctypes.byref(p), int(device), int(nslabs))
+    if not ctx:
+        raise capi.DotsocpError(-1, L.dotsocp_last_error().decode())
+    try:
+        out = []
+        for r in [rhs] + [np.asfortranarray(a, dtype=np.float64) for a in (repeat or [])]:
+            if r.shape != rhs.shape:
+                raise ValueError("every right-hand side must have the shape of the first")
+            res = np.empty(rhs.shape, dtype=np.float64, order="F")
+            capi.check(L.dotsocp_upload(ctx, capi.F_PHI, capi.fptr(r)))
+            capi.check(L.dotsocp_poisson_phi(ctx))
+            capi.check(L.dotsocp_download(ctx, capi.F_PHI, capi.fptr(res)))
+            out.append(res)
+    finally:
+        L.dotsocp_destroy(ctx)
+    return out[0] if repeat is None else out

@@ -214,6 +214,13 @@ dotsocp_i64 dotsocp_field_len(const dotsocp_problem *prob, int field);
  * 4 Bluestein (other lengths up to 1024), 5 dense DCT-matrix product. */
 int dotsocp_dct_algorithm(dotsocp_i64 n);
 
+/* May the single slab solve the t axis of its Poisson step as tridiagonal systems (tri.hip: k_tsolve_single / k_tsolve_pipe)
+ * on an ny x nx x nt grid (1-D: ny = nx1d, nx = 1)?  1 if the powers rho^t of the mode with the largest
+ * a' = 4 ((ny-1)^2 + (nx-1)^2) / (nt-1)^2 stay >= 2^-500 over a piece of ceil(nt / NSUB) <= 64 rows; 0 if not (1-D grids
+ * whose space step is far finer than the time step, or nt > 512): the solve then takes the transform passes along t,
+ * as with DOTSOCP_TSOLVE=dct.  Pure host arithmetic, no device. */
+int dotsocp_tsolve_tri_safe(dotsocp_i64 ny, dotsocp_i64 nx, dotsocp_i64 nt);
+
 /* The schedule of the cone pass's gamma form (pure host arithmetic, no device).  Between two plain inPALM iterations
  * the cone pass leaves gamma = beta + tau z in the multiplier array instead of beta; only the next cone pass can read
  * that.  dotsocp_cone_writes_beta: 1 if the pass of iteration `it` must leave beta -- the iteration ends in a KKT check
@@ -296,6 +303,13 @@ int dotsocp_kernel_time(dotsocp_ctx *ctx, const char *name, double *avg_ms, dots
  * call checks all live buffers of the process at any time: returns the number of damaged buffers (0 = clean, also
  * when the canaries are off) and sets dotsocp_last_error() accordingly.  An out-of-bounds READ shows up as NaNs. */
 int dotsocp_canary_check(void);
+
+/* Test support: phi <- idctn(dctn(phi) ./ (D^2 * initialize_FFTkernel)) by the loop's own Poisson solve
+ * (Solver::poisson_all, the function every iteration calls), on the slabs of the context as created: one slab, `nslabs`
+ * on one device, dotsocp_create_multi, or an attached RCCL rank -- so the partitioned tridiagonal solve along t and the
+ * slab <-> pencil transposes can be probed as operators.  Upload DOTSOCP_F_PHI, call, download DOTSOCP_F_PHI; blocks
+ * until the solve is complete.  Valid between create and begin (DOTSOCP_ESTATE afterwards); may be repeated. */
+int dotsocp_poisson_phi(dotsocp_ctx *ctx);
 
 /* Blocks until all work enqueued by this context has completed. */
 int dotsocp_synchronize(dotsocp_ctx *ctx);

@@ -1,0 +1,217 @@
+"""The Poisson solve of the loop on time slabs (Solver::poisson_all through dotsocp_poisson_phi), probed mode by mode.
+
+A Poisson solution is dominated by its low modes -- the highest (ky, kx) modes are about 1e-6 of it -- so a comparison of
+whole fields at 1e-10 of their max-abs cannot see an error of 1e-6 of a high mode.  Here the right-hand side is a handful
+of (ky, kx) modes, rhs = sum_j amp_j u_ky (x) v_kx (x) g_j(t) with seeded normal columns g_j, scaled so that every component
+of the SOLUTION is O(1); the device result is projected back onto u_ky (x) v_kx (long-double dot products over y and x; the
+other modes are orthogonal and drop out) and compared, per mode, with the literal definition of the operation along t,
+    x_j = C' diag(1 / (D^2 (CY[ky] + CX[kx] + CT))) C g_j       (C: the nt x nt orthonormal DCT-II matrix, long double,
+                                                                  the zero eigenvalue replaced by 1: initialize_FFTkernel)
+which shares nothing with the tridiagonal algebra of tri.hip.  Modes whose amplitudes differ by more than a factor of 16
+go into separate solves: otherwise the rounding of the y / x transforms of the large components leaks into the small ones,
+which is the conditioning of the problem and not the kernel's doing.
+
+Bound per mode: 1e-12 max(1, 1e-2 / a'), a' = (CY[ky] + CX[kx]) / (nt-1)^2; 1e-12 for the singular (0, 0) mode.  It comes
+from the CPU model of the partitioned solve (tests/test_tri_closed_form.py) against the same long-double reference: <= 3e-14
+where a' >= 1e-2 and rho^(n-1) stays normal, growing like 1 / a' below (1e-13 .. 1e-12 at a' = 1e-4), <= 1.4e-13 for the
+zero-mode recurrence at nt = 512.  The shapes are the smallest grids that reach every kernel instance and regime:
+
+  1 (130, 9, 40)    pitched rows; nslabs 1: k_tsolve_single; 2: k_tri_final_reg<32>; 3: slabs of 14 / 13 / 13 nodes,
+                    k_tri_final_reg<16>, k_tri_reduced<4>; 12: k_tri_reduced<16>; 20: two-node slabs, the scratch-array
+                    instance k_tri_reduced<DS_MAX_WORLD>; ngpu 2: a pair of streams per slab
+  2 (66, 10, 80)    40 nodes per slab: k_tri_final_reg<64>
+  3 (66, 10, 140)   70 nodes per slab: the generic k_tri_final
+  4 (34, 6, 512)    2 slabs of 256 = TRI_EXTRA nodes (tiny a': no underflow); the same grid on 1 and 4 slabs
+  5 (34, 6, 514)    257 nodes per slab: the solve must fall back to the slab <-> pencil transposes
+  6 (2048, 1, 512)  1-D; 2 slabs: n = 256, a' up to 64, rho^255 underflows; 4 slabs: n = 128, it does not
+  7 (2048, 4, 340)  n = 170, a' up to 146: underflow
+  8 (2048, 4, 262)  2048^2 x 256 on two GPUs in miniature: n = 131, r = 248, rho^130 = 1e-311 (denormal)
+  9 (3, 4096, 505)  ONE slab (the 4096-point axis along x: the y transform stops at 2048): pieces of 64 rows, a' up to 264, rho^63 < TRI_PW_SAFE: k_tsolve_single, which walks its
+                    powers up from rho^(n-1), must not be launched (tsolve_tri_safe) -- the transform passes along t run
+
+Before the backward sweeps of k_tri_final / k_tri_final_reg resumed rho^t from the last row at which it was still safely
+normal (TRI_PW_SAFE), rows 6 (two slabs: 3.0e-6 at ky = 1024) and 7 (9.6e-8 at ky = 2046) missed the bound by five to six
+orders of magnitude."""
+import functools
+
+import numpy as np
+import pytest
+
+import dotsocp_amd as D
+from dotsocp_amd import capi
+
+gpu = pytest.mark.gpu
+
+LD = np.longdouble
+PI = 4 * np.arctan(LD(1))           # np.pi would leave the reference itself good to 1e-14 only at nt = 512
+DSC = 0.37
+
+SHAPES = {1: ((130, 9, 40), 2), 2: ((66, 10, 80), 2), 3: ((66, 10, 140), 2), 4: ((34, 6, 512), 2), 5: ((34, 6, 514), 2),
+          6: ((2048, 1, 512), 1), 7: ((2048, 4, 340), 2), 8: ((2048, 4, 262), 2), 9: ((3, 4096, 505), 2)}
+LAYOUTS = [(1, dict(nslabs=1)), (1, dict(nslabs=2)), (1, dict(nslabs=3)), (1, dict(nslabs=12)), (1, dict(nslabs=20)),
+           (1, dict(ngpu=2)), (2, dict(nslabs=2)), (3, dict(nslabs=2)), (4, dict(nslabs=1)), (4, dict(nslabs=2)),
+           (4, dict(nslabs=4)), (5, dict(nslabs=2)), (6, dict(nslabs=2)), (6, dict(nslabs=4)), (7, dict(nslabs=2)),
+           (8, dict(nslabs=2)), (9, dict(nslabs=1))]
+
+
+def _id(case):
+    shape, kw = case
+    return "shape%d-%s" % (shape, "-".join("%s%d" % kv for kv in kw.items()))
+
+
+def _basis(n, k):
+    """the k-th orthonormal DCT-II basis vector of length n"""
+    i = np.arange(n, dtype=LD)
+    return np.sqrt(LD(1 if k == 0 else 2) / n) * np.cos(PI * k * (2 * i + 1) / (2 * n))
+
+
+def _eig(n):
+    """initialize_FFTkernel.m:6-8"""
+    return 2 * LD(n - 1) ** 2 * (1 - np.cos(PI * np.arange(n, dtype=LD) / n))
+
+
+def _modes(ny, nx):
+    kys = sorted({0, 1, 2, ny // 8, ny // 2, ny - 2, ny - 1} & set(range(ny)))
+    kxs = sorted({0, 1, nx - 1} & set(range(nx)))
+    return [(ky, kx) for ky in kys for kx in kxs]
+
+
+@functools.lru_cache(maxsize=2)
+def _probe(shape_no):
+    """Per shape, computed once and read-only: the modes with their long-double solutions, amplitudes and bounds, and the
+    right-hand sides of the bands (float64, Fortran (ny, nx, nt))."""
+    (ny, nx, nt), _ = SHAPES[shape_no]
+    rng = np.random.default_rng(1000 + shape_no)
+    C = np.stack([_basis(nt, k) for k in range(nt)])            # C[k, t]
+    cy, cx, ct = _eig(ny), _eig(nx), _eig(nt)
+    modes = []
+    for ky, kx in _modes(ny, nx):
+        g = rng.standard_normal(nt).astype(LD)
+        lam = cy[ky] + cx[kx] + ct
+        if ky == 0 and kx == 0:
+            lam[0] = 1                                           # kernel(kernel == 0) = 1 (initialize_FFTkernel.m:15)
+        x = C.T @ ((C @ g) / (LD(DSC) ** 2 * lam))
+        amp = 1 / np.max(np.abs(x))
+        ap = float((cy[ky] + cx[kx]) / LD(nt - 1) ** 2)
+        bound = 1e-12 if (ky, kx) == (0, 0) else 1e-12 * max(1.0, 1e-2 / ap)
+        modes.append(dict(k=(ky, kx), g=g, x=amp * x, amp=amp, ap=ap, bound=bound,
+                          b=np.outer(_basis(nx, kx), _basis(ny, ky)).ravel()))     # b[y + ny x] = u(y) v(x)
+    # bands: (0, 0) alone -- the singular column travels whole and is solved by recurrence -- then by amplitude
+    bands = [[m for m in modes if m["k"] == (0, 0)]]
+    for m in sorted((m for m in modes if m["k"] != (0, 0)), key=lambda m: float(m["amp"])):
+        if len(bands) == 1 or m["amp"] > 16 * bands[-1][0]["amp"]:
+            bands.append([])
+        bands[-1].append(m)
+    rhs = []
+    for band in bands:
+        r = np.zeros((ny * nx, nt), dtype=LD)
+        for m in band:
+            r += np.outer(m["b"], m["amp"] * m["g"])
+        r = np.asfortranarray(r.astype(np.float64)).reshape((ny, nx, nt), order="F")
+        r.setflags(write=False)
+        rhs.append(r)
+    return bands, rhs
+
+
+def _errors(shape_no, kw):
+    """[(mode, e_j, bound_j)] over all bands of the shape, one context, one solve per band"""
+    (ny, nx, nt), dim = SHAPES[shape_no]
+    bands, rhs = _probe(shape_no)
+    sols = D.poisson_on_slabs(rhs[0], DSC, dim=dim, repeat=rhs[1:], **kw)
+    out = []
+    for band, sol in zip(bands, sols):
+        assert np.all(np.isfinite(sol))
+        W = sol.reshape((ny * nx, nt), order="F").astype(LD)
+        P = np.stack([m["b"] for m in band]) @ W
+        for m, p in zip(band, P):
+            out.append((m, float(np.max(np.abs(p - m["x"]))), m["bound"]))
+    return out
+
+
+def _report(tag, errs):
+    m, e, b = max(errs, key=lambda r: r[1])
+    mr, er, br = max(errs, key=lambda r: r[1] / r[2])
+    print("\n%s: worst e_j %.2e at (ky, kx) = %s, a' = %.3g; worst e_j / bound %.2e at %s, a' = %.3g"
+          % (tag, e, m["k"], m["ap"], er / br, mr["k"], mr["ap"]))
+
+
+def _check(tag, errs):
+    _report(tag, errs)
+    bad = ["(ky, kx) = %s, a' = %.3g: e = %.2e > %.2e" % (m["k"], m["ap"], e, b) for m, e, b in errs if not e <= b]
+    assert not bad, tag + ": " + "; ".join(bad)
+
+
+def test_bands_of_the_probes():
+    """(No device needed.)  What the probes rest on: three or more bands per shape besides (0, 0), amplitudes within a
+    factor of 16 inside a band, every component of the solution of unit size."""
+    for shape_no in (1, 6):
+        bands, rhs = _probe(shape_no)
+        assert [m["k"] for m in bands[0]] == [(0, 0)] and len(bands) >= 4 and len(rhs) == len(bands)
+        for band in bands:
+            amps = [float(m["amp"]) for m in band]
+            assert max(amps) <= 16 * min(amps)
+            for m in band:
+                assert abs(float(np.max(np.abs(m["x"]))) - 1) < 1e-15
+
+
+@gpu
+@pytest.mark.parametrize("case", LAYOUTS, ids=_id)
+def test_modes_on_slabs(case):
+    shape_no, kw = case
+    _check(_id(case), _errors(shape_no, kw))
+
+
+@gpu
+@pytest.mark.parametrize("case", [(1, dict(nslabs=2)), (1, dict(nslabs=3)), (3, dict(nslabs=2))], ids=_id)
+def test_modes_through_the_transposes(case, monkeypatch):
+    """DOTSOCP_TSOLVE=dct: the slab <-> pencil transposes around the t-axis transform, same probes, same bounds"""
+    monkeypatch.setenv("DOTSOCP_TSOLVE", "dct")
+    shape_no, kw = case
+    _check(_id(case) + "-dct", _errors(shape_no, kw))
+
+
+def _slab_nodes(nt, nslabs):
+    return [b - a for a, b in (capi.slab_range(nt, nslabs, r) for r in range(nslabs))]
+
+
+@gpu
+@pytest.mark.parametrize("shape_no,nslabs,tri", [(1, 2, True), (3, 2, True), (4, 2, True), (5, 2, False)])
+def test_which_t_solve_ran(shape_no, nslabs, tri, monkeypatch):
+    """The slab runs above took the tridiagonal path, shape 5 (257 nodes per slab > TRI_EXTRA) the transposes: with
+    DOTSOCP_TSOLVE=dct every context transposes, so the bits of the default run differ from that run's exactly where the
+    default is another algorithm for the same systems, and are the same bits where it is the same launches."""
+    (ny, nx, nt), dim = SHAPES[shape_no]
+    assert (max(_slab_nodes(nt, nslabs)) <= 256) == tri
+    rhs = np.asfortranarray(np.random.default_rng(shape_no).standard_normal((ny, nx, nt)))
+    a = D.poisson_on_slabs(rhs, DSC, nslabs=nslabs, dim=dim)
+    monkeypatch.setenv("DOTSOCP_TSOLVE", "dct")
+    b = D.poisson_on_slabs(rhs, DSC, nslabs=nslabs, dim=dim)
+    # the same operation: each run within the bound of its worst-conditioned mode (the smallest a') of the field
+    ap = min(float(v) for v in (_eig(ny)[1:2].tolist() + _eig(nx)[1:2].tolist())) / (nt - 1) ** 2
+    np.testing.assert_allclose(a, b, rtol=0, atol=2e-12 * max(1.0, 1e-2 / ap) * np.abs(b).max())
+    assert np.array_equal(a, b) == (not tri)
+
+
+@gpu
+@pytest.mark.parametrize("nx,safe", [(2048, True), (4096, False)])
+def test_single_slab_t_solve_and_the_guard(nx, safe, monkeypatch):
+    """3 x nx x 505 on one slab: at nx = 2048 the tridiagonal kernel runs (other bits than the transform passes), at
+    nx = 4096 the powers of its 64-row pieces could fall below TRI_PW_SAFE and the transform passes run: the same bits."""
+    assert capi.lib().dotsocp_tsolve_tri_safe(3, nx, 505) == int(safe)
+    rhs = np.asfortranarray(np.random.default_rng(nx).standard_normal((3, nx, 505)))
+    a = D.poisson_on_slabs(rhs, DSC)
+    monkeypatch.setenv("DOTSOCP_TSOLVE", "dct")
+    b = D.poisson_on_slabs(rhs, DSC)
+    assert np.array_equal(a, b) == (not safe)
+
+
+@gpu
+def test_poisson_phi_only_before_begin():
+    rho0, rho1 = D.get_example_2d("example1", 16, 16)
+    var, model = D.initialize(rho0, rho1, 8)
+    D.InitialScaling(var, model, True)
+    ctx = D.InPALMContext(var, dict(tau=1.9, sigma=1.0, tol=0.0, maxit=1), model)
+    try:
+        assert capi.lib().dotsocp_poisson_phi(ctx._ctx) == -4          # DOTSOCP_ESTATE
+    finally:
+        ctx.close()

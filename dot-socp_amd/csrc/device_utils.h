@@ -1,4 +1,4 @@
-// Device-side helpers shared by cone.hip, stencil.hip and kkt.hip.
+// Device-side helpers shared by cone.hip, stencil.hip, qstep_march.hip and kkt.hip.
 #pragma once
 #include "common.h"
 #include "kernels.h"
@@ -149,6 +149,28 @@ __device__ __forceinline__ void build_z2(double (&v)[10], double q0, const EdgeQ
     v[1] = a.xm; v[2] = a.xp; v[3] = b.xm; v[4] = b.xp;
     v[5] = a.ym; v[6] = a.yp; v[7] = b.ym; v[8] = b.yp;
     v[9] = dF + s * q0;
+}
+
+// q layout: index of the bx edge that leaves node (y, x) in +x resp. of the by edge that leaves it in +y, edge layer tl
+__device__ __forceinline__ i64 bx_index(const Grid &g, i64 y, i64 x, i64 tl) { return g.offBx + g.bxLayer * tl + y + g.py * x; }
+__device__ __forceinline__ i64 by_index(const Grid &g, i64 y, i64 x, i64 tl) { return g.offBy + g.byLayer * tl + y + g.pyb * x; }
+
+// Edges on a tile border of the fused cone kernel (x the last column of a tile of width fg.XB / y the last row of a tile of
+// height 64): q2 holds the own tile's raw partial sum, the side buffer slot sx_index / sy_index the neighbour tile's
+__device__ __forceinline__ bool sx_split(const FusedGeom &fg, i64 x) { return (x % fg.XB) == fg.XB - 1; }
+__device__ __forceinline__ bool sy_split(i64 y) { return (y & 63) == 63; }
+__device__ __forceinline__ i64 sx_index(const Grid &g, const FusedGeom &fg, i64 y, i64 x, i64 tl) {
+    return (tl * fg.nxblk + (x / fg.XB + 1)) * g.ny + y;
+}
+__device__ __forceinline__ i64 sy_index(const Grid &g, const FusedGeom &fg, i64 y, i64 x, i64 tl) {
+    return (tl * g.nx + x) * fg.nyblk + (y / 64 + 1);
+}
+
+// One entry of A phi: a * (p1 - p0) as the reference's sparse product forms it, two rounded products and one sum
+__device__ __forceinline__ double fwd_diff(double a, double p0, double p1) {
+    double tmp = (-a) * p0;
+    tmp += a * p1;
+    return tmp;
 }
 
 // Adjoint gather for one staggered edge.  `w(j, cell)` is supplied by a functor so the same

@@ -161,13 +161,7 @@ int launch_outputs(const Grid &g, const double *q, const double *alpha, const do
 int launch_out_tail(const Grid &g, const double *alpha, const double *weight, double sig, double cD, double *out,
                     hipStream_t st);
 
-// ---------------- stencil.hip ----------------
-// q-step + alpha update reading the precomputed adjoint sums q2 (+ side buffers) of the fused kernel;
-// writes q^{k+1} into q_out (q^k stays intact for the deferred beta update).
-int launch_qstep_fused(const Grid &g, const LoopCoef &c, const FusedGeom &fg, const double *phi,
-                       const double *q2, const double *sx, const double *sy, const double *weight,
-                       const double *tail_bx, const double *tail_by, double *q_out, double *alpha,
-                       hipStream_t st);
+// ---------------- qstep_march.hip: the q-step as one march through the time layers (march step: qstep_tile.h) ----------------
 // q-step + alpha update (alpha_in -> alpha_out, distinct buffers) + rhs of the next iteration's phi-step
 // ex (optional): a scaling of alpha_in that is still pending in memory (applied on load), and -- partials != nullptr, one
 // slab only -- the KKT variant: the sums of the KKT block that need only phi, q^+, alpha^+, A phi and c are accumulated in
@@ -186,7 +180,7 @@ int launch_qstep_rhs(const Grid &g, const LoopCoef &c, const FusedGeom &fg, cons
                      const QStepExtra *ex = nullptr);
 i64 qstep_rhs_blocks(const Grid &g, const FusedGeom &fg);
 // The q-step (plain inPALM instance of launch_qstep_rhs: one slab, no weight) and, one march step behind it, the
-// gamma-reading cone pass of the NEXT iteration on the q it has just formed (stencil.hip: k_qcone).  gout: that pass
+// gamma-reading cone pass of the NEXT iteration on the q it has just formed (k_qcone).  gout: that pass
 // writes gamma (the steady form: q is not stored, q_out is not touched) or beta (the exit form: q goes to q_out).
 // q2v / sx / sy are the sums the q-step reads, q2_out / sx_out / sy_out (other buffers) receive the new ones.
 struct QConeArgs {
@@ -200,13 +194,6 @@ struct QConeArgs {
 int launch_qcone(const Grid &g, const LoopCoef &c, const FusedGeom &fg, QConeArgs a, bool gout, hipStream_t st);
 // node layers per chunk of that launch: one chunk per tile, or DOTSOCP_QCONE_TC=n (results do not depend on it)
 i64 qcone_chunk_len(const Grid &g);
-// rhs <- (rhs + r) - r / factor, c <- c / factor  (sigma update without a new pass over q and alpha)
-// (c_ends: c is zero off the two global end layers, which alone are divided)
-int launch_rhs_sigma_fix(const Grid &g, double *rhs, const double *r, double *cvec, double factor, hipStream_t st,
-                         bool c_ends = false);
-// *flag (device, cleared by the caller) |= 1 unless every layer of the slab's c except global layer 0 and nt - 1 is
-// all-zero bits
-int launch_c_interior_test(const Grid &g, const double *cvec, int *flag, hipStream_t st);
 // chunks of time layers of that launch (z0 + i * zstride, i < zcount, selects chunks; chunks are independent of each other: only
 // chunk 0 reads the adjoint tails of the left neighbour slab and only the last one the phi halo of the right one -- and
 // writes the u0 tail)
@@ -218,12 +205,28 @@ int launch_qstep_rhs_acc(int var, const Grid &g, const LoopCoef &c, const FusedG
                          double *q_raw, const double *alpha_in, double *alpha_out, double *rhs, double *q_state,
                          const double *q_anchor, const double *alpha_anchor, const AccCoef &k, hipStream_t st,
                          const double *tail_bx = nullptr, const double *tail_by = nullptr, double *u0_tail = nullptr);
-int launch_rhs_fixup(const Grid &g, const LoopCoef &c, const double *u0_prev, double *rhs, hipStream_t st);
-// PALM (solver_socp_PALM.m:196-200,137): first q-step without the alpha update; tmp_q = A phi in q layout
+// PALM (solver_socp_PALM.m:196-200): first q-step without the alpha update
 int launch_qstep_palm_first(const Grid &g, const LoopCoef &c, const FusedGeom &fg, const double *phi, const double *q2,
                             const double *sx, const double *sy, const double *cvec, double *q_out, const double *alpha,
                             double *rhs, hipStream_t st, const double *tail_bx = nullptr, const double *tail_by = nullptr,
                             const double *qk = nullptr);   // qk: q2 / sx / sy hold k_cone_fused's second gather (modes 5, 6)
+
+// ---------------- stencil.hip: one-entry-per-thread stencils, halo helpers, scalings ----------------
+// q-step + alpha update reading the precomputed adjoint sums q2 (+ side buffers) of the fused kernel;
+// writes q^{k+1} into q_out (q^k stays intact for the deferred beta update).
+int launch_qstep_fused(const Grid &g, const LoopCoef &c, const FusedGeom &fg, const double *phi,
+                       const double *q2, const double *sx, const double *sy, const double *weight,
+                       const double *tail_bx, const double *tail_by, double *q_out, double *alpha,
+                       hipStream_t st);
+// rhs <- (rhs + r) - r / factor, c <- c / factor  (sigma update without a new pass over q and alpha)
+// (c_ends: c is zero off the two global end layers, which alone are divided)
+int launch_rhs_sigma_fix(const Grid &g, double *rhs, const double *r, double *cvec, double factor, hipStream_t st,
+                         bool c_ends = false);
+// *flag (device, cleared by the caller) |= 1 unless every layer of the slab's c except global layer 0 and nt - 1 is
+// all-zero bits
+int launch_c_interior_test(const Grid &g, const double *cvec, int *flag, hipStream_t st);
+int launch_rhs_fixup(const Grid &g, const LoopCoef &c, const double *u0_prev, double *rhs, hipStream_t st);
+// tmp_q = A phi in q layout (solver_socp_PALM.m:137)
 int launch_grad(const Grid &g, const LoopCoef &c, const double *phi, double *out, hipStream_t st);
 // time-slab mode: complete the adjoint sums of the last owned cell for the right neighbour (values times sf)
 int launch_tail_finalize(const Grid &g, const LoopCoef &c, const FusedGeom &fg, const double *q2, const double *sx,

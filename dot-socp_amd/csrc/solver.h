@@ -297,7 +297,7 @@ struct Solver {
     bool last_of_run = false;    // this iteration is the last of its run() call (set by run())
     // The early cone pass.  A gamma-reading pass needs q^{k+1} and gamma^k only -- not phi -- so the q-step of an iteration
     // whose own pass left gamma runs the NEXT iteration's pass in the same kernel, on the q it holds in registers
-    // (stencil.hip: k_qcone; one slab, inPALM / ALG2, unweighted).  The bookkeeping of that pass is done where the launch is
+    // (qstep_march.hip: k_qcone; one slab, inPALM / ALG2, unweighted).  The bookkeeping of that pass is done where the launch is
     // issued (phase_q); phase_z of the next iteration launches nothing and checks that step() schedules what was predicted.
     // After the steady form q^{k+1} is not in memory (q_valid): by the schedule every reader of q follows an exit form.
     int qcone = -1;              // DOTSOCP_QCONE: 0 never, 1 wherever eligible, 2 as 1 with the two kernels back to back

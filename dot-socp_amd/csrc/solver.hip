@@ -1,7 +1,7 @@
 // Host side of the device-resident inPALM / ALG2 loop.  The scalar control flow (sigma rule,
 // rescale triggers, KKT ratios, stop test) restates socp/dot2d/algorithms/solver_socp_inPALM.m
 // (and solver_wsocp_inPALM.m for the weighted variant) line by line; all array work is done by the
-// kernels of cone.hip / fused.hip / stencil.hip / dct*.hip / kkt.hip on the slab's HIP streams.
+// kernels of cone.hip / fused.hip / stencil.hip / qstep_march.hip / dct*.hip / kkt.hip on the slab's HIP streams.
 //
 // Time-slab mode (world > 1): the grid is cut along t (common.h: Grid).  Per iteration a slab
 // exchanges six ny x nx layers with its neighbours (u0 tail, phi head, adjoint tails, bx/by heads)

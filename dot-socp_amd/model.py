@@ -1,6 +1,6 @@
 """Host-side mirror of the reference's model set-up and output recovery (the O(N),
 once-per-level code either side of the hot loop).  Matrix-free: `model.grad` is not built --
-the staggered gradient lives in the HIP stencils (dot-socp_amd/csrc/stencil.hip).
+the staggered gradient lives in the HIP stencils (dot-socp_amd/csrc/stencil.hip, qstep_march.hip).
 
 Every function names the reference code it mirrors; vectors are 1-D float64 arrays in MATLAB
 column-major order, z / beta are (Nz, 10) (1-D: (Nz, 6)) Fortran-ordered matrices.

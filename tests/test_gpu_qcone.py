@@ -1,5 +1,5 @@
 """The early cone pass: the q-step of an iteration whose own cone pass left gamma also runs the NEXT iteration's
-gamma-reading pass, in one kernel, on the q it holds in registers (stencil.hip: k_qcone; Solver::step schedules it,
+gamma-reading pass, in one kernel, on the q it holds in registers (qstep_march.hip: k_qcone; Solver::step schedules it,
 solver.h).  The steady form does not store q at all, the exit form stores q and beta for the readers behind it.
 
 Every entry gets the arithmetic of the unfused pair of kernels in the same order, so DOTSOCP_QCONE=1 (fuse wherever

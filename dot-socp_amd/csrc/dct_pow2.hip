@@ -943,7 +943,7 @@ static int tile_log2_rows(int n, i64 nLines, int nbuf) {
     return lp;
 }
 
-static int device_cus() {
+int device_cus() {
     static int cus[64] = {0};
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;

@@ -267,6 +267,7 @@ bool tsolve_tri_supported(i64 nt);
 bool tsolve_tri_preferred(i64 nt, bool pow2, i64 plane);      // faster than the transform pass(es) along t?
 bool tsolve_tri_safe(i64 ny, i64 nx, i64 nt);                 // no power rho^t of a piece leaves the safe range (else: transform passes)
 int launch_tsolve_tri(const Grid &g, i64 nt, double kscale, const double *cy, const double *cx, double *x, hipStream_t st);
+int device_cus();              // compute units of the current device, cached per device (dct_pow2.hip); 256 if the query fails
 // up to DS_MAX_WORLD messages copied by ONE launch on the receiving slab's stream: message m = count[m] doubles from
 // src[m] (this or a peer device) to dst[m] -- the exchanges between the slabs of one process (one launch per receiver
 // instead of one event-ordered copy per message)

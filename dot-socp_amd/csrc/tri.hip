@@ -16,8 +16,11 @@
 // The (0, 0) mode is singular (kernel == 0 -> 1, initialize_FFTkernel.m:15): its single line of nt values
 // travels whole to the owner of column 0, which solves T x = g - mean(g) by recurrence, removes the mean and adds
 // (nt-1)^2 mean(g) -- the k = 0 coefficient divided by D^2 * 1.
+// The arithmetic of all of it -- forward step, backward step, spike values, reduced sweep, singular mode, and the tile solve
+// of the two k_tsolve_* kernels -- is in tri_sweep.h; the kernels here are loops, loads, stores and message layout.
 #include "device_utils.h"
 #include "kernels.h"
+#include "tri_sweep.h"
 
 #include <cmath>
 #include <cstdint>
@@ -47,119 +50,6 @@ __device__ __forceinline__ int tri_owner(const PencilCuts &pc, i64 m, i64 plane)
 // message to owner j starts at 2 cut[j] + TRI_EXTRA j and holds [first values | last values | TRI_EXTRA extras]
 __device__ __forceinline__ i64 tri_msg_off(const PencilCuts &pc, int j) { return 2 * pc.cut[j] + (i64)TRI_EXTRA * j; }
 
-// ---- division-free eliminations (round 4) ----
-// The pivots of a block depend on the mode and the row only, and have a closed form.  With x = 1 + a'/2 = cosh(theta),
-// r = e^theta = x + sqrt(x^2 - 1), rho = 1 / r, the elimination from a block's first row gives
-//     piv_t = r N_{t+1} / N_t ,   N_t = 1 - rho^(2t+2)  (row 0 couples to a neighbour slab: delta_0 = a' + 2)
-//                                 N_t = 1 + rho^(2t+1)  (row 0 is the global first / last row: delta_0 = a' + 1)
-// (both satisfy N_{t+1} = (1 - rho^2) + rho^2 N_t -- a recurrence of positive terms, no cancellation), and a global
-// boundary row at the END of the sweep has piv = r N_n / N_{n-1} - 1.  In the scaled variable D_t = d_t N_t the sweep
-// d_t = g_t + d_{t-1} / piv_{t-1} becomes  D_t = g_t N_t + rho D_{t-1}:  no division per row (the kernels of round 2
-// spent 2 n dependent IEEE divisions per mode here and were bound by them: 43 + 57 us on a slab of 16 layers that
-// streams in 27 + 54, 530 + 630 us on 64 layers).  The last unknown is rho D_{n-1} / N_n (boundary end:
-// D_{n-1} / (r N_n - N_{n-1})).  The sweep from the other end is the same recurrence on the reversed column; as a
-// weighted sum, sum_t rho^t N'_{n-1-t} g_t, it runs in the same ascending pass over the column.
-struct TriCoef {
-    double rho, rho2, r, r2, n0d;      // n0d = 1 - rho^2, formed without cancellation
-};
-__device__ __forceinline__ TriCoef tri_coef(double ap) {
-    TriCoef c;
-    const double s = sqrt(ap * (1.0 + 0.25 * ap));     // sqrt(x^2 - 1)
-    const double rm1 = 0.5 * ap + s;                    // r - 1
-    c.r = 1.0 + rm1;
-    c.rho = 1.0 / c.r;
-    c.rho2 = c.rho * c.rho;
-    c.r2 = c.r * c.r;
-    c.n0d = (rm1 * c.rho) * (1.0 + c.rho);              // (1 - rho) (1 + rho)
-    return c;
-}
-__device__ __forceinline__ double tri_n0(const TriCoef &c, bool bnd) { return bnd ? 1.0 + c.rho : c.n0d; }
-// x / n for n in (0, 2]: reciprocal seed, two Newton steps, one residual correction (the result of the IEEE sequence to
-// the last bit or one off it, at about half its instructions)
-__device__ __forceinline__ double tri_div(double x, double n) {
-    double r = __builtin_amdgcn_rcp(n);
-    double e = __builtin_fma(-n, r, 1.0);
-    r = __builtin_fma(r, e, r);
-    e = __builtin_fma(-n, r, 1.0);
-    r = __builtin_fma(r, e, r);
-    const double q = x * r;
-    return __builtin_fma(__builtin_fma(-n, q, x), r, q);
-}
-// N_0, N_{n-1}, N_n of the sweep over n rows that starts on a boundary row (bnd: N_j = 1 + rho^(2j+1)) or not
-// (N_j = 1 - rho^(2j+2)); rn1 = rho^(n-1).  s, pe: N_j = 1 + s pe rho^(2j).
-struct TriEnds {
-    double N0, N1, Nn, s, pe;
-};
-__device__ __forceinline__ TriEnds tri_ends(const TriCoef &c, bool bnd, int n, double rn1) {
-    TriEnds e;
-    e.s = bnd ? 1.0 : -1.0;
-    e.pe = bnd ? c.rho : c.rho2;
-    e.N0 = tri_n0(c, bnd);
-    e.N1 = (n == 1) ? e.N0 : 1.0 + e.s * ((rn1 * rn1) * e.pe);
-    e.Nn = c.n0d + c.rho2 * e.N1;
-    return e;
-}
-__device__ __forceinline__ double tri_powi(double x, int k) {
-    double r = 1.0;
-    while (k > 0) {
-        if (k & 1) r *= x;
-        x *= x;
-        k >>= 1;
-    }
-    return r;
-}
-// the last unknown of a sweep over n rows from its D_{n-1}; bnd: the sweep ENDS on a global boundary row
-__device__ __forceinline__ double tri_last(const TriCoef &c, double D, double N1, double Nn, bool bnd) {
-    return bnd ? tri_div(D, c.r * Nn - N1) : tri_div(c.rho * D, Nn);
-}
-// Both sweeps of a column come out of two running sums, H_t = g_t + rho H_{t-1} and G_t = sum_{s <= t} rho^s g_s:
-//     D_t = sum_{s <= t} rho^(t-s) N_s g_s = H_t + s_f pe_f rho^t G_t            (front sweep, kept per row by k_tri_final)
-//     F   = sum_t rho^t N'_{n-1-t} g_t     = G_{n-1} + s_b pe_b rho^(n-1) H_{n-1}  (back sweep, as a weighted sum)
-// -- neither sum needs a power walked back up from a value that may have underflowed.  The BACKWARD sweep of k_tri_final
-// does: it forms N_t = 1 + s pe rho^(2t) from rho^t walked up from rho^(n-1) (pw *= r), and rho^(n-1) leaves the normal
-// range once (n - 1) log10(r) > 308 -- slabs of more than 64 nodes with a' = (CY + CX) / (nt-1)^2 in the hundreds, e.g.
-// 2048 x 2048 x 256 on two GPUs.  From a zero the walk stays zero and every N_t, t >= 1, came out as 1 (errors of 1e-7 of
-// a high mode); from a denormal it carries that value's few bits.  So the forward sweep remembers the last row t* whose
-// power was still >= TRI_PW_SAFE, and its value: behind t* N_t IS 1 in double (rho^(2t) < 2^-1000), at t* the walk resumes
-// from the remembered value.  Where rho^(n-1) >= TRI_PW_SAFE, t* = n - 1 and the arithmetic is what it always was.
-// (k_tsolve_single / k_tsolve_pipe walk the same way -- and put the left interface in as xl N_0 rho^t, so a lost power costs
-// them that whole term -- over pieces of n = ceil(nt / NSUB) <= 64 rows.  rho^(n-1) < 2^-1022 needs
-// r > 2^(1022 / (n-1)): 7.6e4 on 64 rows (nt >= 505), 2e9 on 34 (nt = 136 or 272), and r ~ a' <= 4 ((ny-1)^2 + (nx-1)^2) / (nt-1)^2:
-// no 2-D grid that fits a device, but a 1-D grid from 70 000 space points at nt = 505 .. 511.  Those kernels keep their
-// arithmetic -- they are the flagship's t solve -- and are not launched there: tsolve_tri_safe(), asked by
-// launch_poisson_t_single, sends every grid whose largest a' could take rho^(n-1) below TRI_PW_SAFE to the transform passes
-// along t, which exist for every length.)
-#define TRI_PW_SAFE 0x1p-500
-// first / last entries of A_p^-1 e_first (vf, vl) and A_p^-1 e_last (wf, wl) of a block of n rows:
-// prod_{s < n-1} 1 / piv_s = rho^(n-1) N_0 / N_{n-1}, 1 / piv_{n-1} = rho N_{n-1} / N_n (boundary end: N_{n-1} / (r N_n - N_{n-1}))
-struct TriSpike {
-    double vf, vl, wf, wl;
-};
-__device__ __forceinline__ TriSpike tri_spike(const TriCoef &c, int n, bool first, bool last) {
-    const double rn1 = tri_powi(c.rho, n - 1);
-    const TriEnds f = tri_ends(c, first, n, rn1), b = tri_ends(c, last, n, rn1);
-    TriSpike k;
-    if (last) {
-        const double den = c.r * f.Nn - f.N1;
-        k.vl = tri_div(rn1 * f.N0, den);
-        k.wl = tri_div(f.N1, den);
-    } else {
-        k.vl = tri_div((rn1 * c.rho) * f.N0, f.Nn);
-        k.wl = tri_div(c.rho * f.N1, f.Nn);
-    }
-    if (first) {
-        const double den = c.r * b.Nn - b.N1;
-        k.wf = tri_div(rn1 * b.N0, den);
-        k.vf = tri_div(b.N1, den);
-    } else {
-        k.wf = tri_div((rn1 * c.rho) * b.N0, b.Nn);
-        k.vf = tri_div(c.rho * b.N1, b.Nn);
-    }
-    if (first) k.vf = k.vl = 0.0;                 // no left / right neighbour
-    if (last) k.wf = k.wl = 0.0;
-    return k;
-}
-
 // One ascending pass over the column of a mode: both eliminations at once, nothing kept (any slab length)
 __global__ void __launch_bounds__(256) k_tri_local(TriGeom g, const double *__restrict__ r, double *__restrict__ send) {
     const i64 m = (i64)blockIdx.x * 256 + threadIdx.x;
@@ -176,7 +66,7 @@ __global__ void __launch_bounds__(256) k_tri_local(TriGeom g, const double *__re
     }
     const TriCoef c = tri_coef(tri_aprime(g, m));
     const bool first = g.first != 0, last = g.last != 0;
-    double H = 0.0, G = 0.0, pw = 1.0;
+    TriFwd<false, false> fw;
     constexpr int U = 8;
     for (int t0 = 0; t0 < n; t0 += U) {
         double gv[U];
@@ -184,17 +74,12 @@ __global__ void __launch_bounds__(256) k_tri_local(TriGeom g, const double *__re
         for (int u = 0; u < U; ++u) gv[u] = (t0 + u < n) ? r[m + g.plane * (t0 + u)] * sc : 0.0;
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            if (t0 + u < n) {
-                H = gv[u] + c.rho * H;
-                G += pw * gv[u];
-                if (t0 + u + 1 < n) pw *= c.rho;           // ends as rho^(n-1)
-            }
+            if (t0 + u < n) fw.step(c, 0.0, gv[u], t0 + u, t0 + u + 1 < n);        // (no D per row: s pe not needed yet)
         }
     }
-    const TriEnds f = tri_ends(c, first, n, pw), b = tri_ends(c, last, n, pw);
-    const double D = H + ((f.s * f.pe) * pw) * G, F = G + ((b.s * b.pe) * pw) * H;
-    send[off + (m - g.pc.cut[j])] = tri_last(c, F, b.N1, b.Nn, first);        // first entry of A^-1 g
-    send[off + w + (m - g.pc.cut[j])] = tri_last(c, D, f.N1, f.Nn, last);     // last entry
+    const TriEnds f = tri_ends(c, first, n, fw.pw), b = tri_ends(c, last, n, fw.pw);
+    send[off + (m - g.pc.cut[j])] = tri_last(c, fw.back(tri_spe(c, last)), b, first);          // first entry of A^-1 g
+    send[off + w + (m - g.pc.cut[j])] = tri_last(c, fw.front(tri_spe(c, first)), f, last);     // last entry
 }
 
 struct TriReduced {
@@ -221,7 +106,6 @@ __global__ void __launch_bounds__(128) k_tri_reduced(TriGeom g, TriReduced q, co
     auto msg_in = [&](int p) { return (p == q.own) ? q.own_recv : recv + p * stride; };
     auto msg_out = [&](int p) { return (p == q.own) ? q.own_back : back + p * stride; };
     if (m == 0) {
-        // T x = g - mean(g) by recurrence from x_0 = 0, then zero mean, plus beta * mean(g)
         double sum = 0.0;
         i64 tg = 0;
         for (int p = 0; p < q.P; ++p)
@@ -230,17 +114,7 @@ __global__ void __launch_bounds__(128) k_tri_reduced(TriGeom g, TriReduced q, co
                 zero_work[tg] = v;
                 sum += v;
             }
-        const double gbar = sum / (double)q.nt;
-        double xm = 0.0, xc = 0.0, acc = 0.0;      // x_{t-1}, x_t
-        for (i64 t = 0; t < q.nt; ++t) {
-            const double gt = zero_work[t] - gbar;
-            zero_work[t] = xc;
-            acc += xc;
-            const double xn = (t == 0) ? xc - gt : 2.0 * xc - xm - gt;
-            xm = xc;
-            xc = xn;
-        }
-        const double shift = g.beta * gbar - acc / (double)q.nt;
+        const double shift = tri_singular(zero_work, q.nt, sum, g.beta);
         tg = 0;
         for (int p = 0; p < q.P; ++p)
             for (i64 t = 0; t < q.slab_n[p]; ++t, ++tg) msg_out(p)[2 * q.nl + t] = zero_work[tg] + shift;
@@ -253,28 +127,19 @@ __global__ void __launch_bounds__(128) k_tri_reduced(TriGeom g, TriReduced q, co
     for (int p = 0; p < PMAX; ++p) {
         if (p >= q.P) break;
         const TriSpike k = tri_spike(c, (int)q.slab_n[p], p == 0, p == q.P - 1);
-        const double vf = k.vf, vl = k.vl, wf = k.wf, wl = k.wl;
         const double *mi = msg_in(p);
         const double Gf = mi[i], Gl = mi[q.nl + i];
-        // unknowns F_p (first value of slab p), L_p (last value):  F_p = Gf + vf L_{p-1} + wf F_{p+1},  L_p = Gl + vl L_{p-1} + wl F_{p+1}
-        // sweep: L_{p-1} = al + ga F_p  ->  F_p = A + B F_{p+1},  L_p = al' + ga' F_{p+1}
-        if (p == 0) {
-            A[0] = Gf; B[0] = wf; al[0] = Gl; ga[0] = wl;
-        } else {
-            const double den = 1.0 - vf * ga[p - 1];
-            A[p] = (Gf + vf * al[p - 1]) / den;
-            B[p] = wf / den;
-            al[p] = Gl + vl * (al[p - 1] + ga[p - 1] * A[p]);
-            ga[p] = wl + vl * ga[p - 1] * B[p];
-        }
+        const int pp = p ? p - 1 : 0;              // (the head has no slab before it and reads nothing of it)
+        tri_red_fwd(p == 0, Gf, Gl, k.vf, k.vl, k.wf, k.wl, al[pp], ga[pp], A[p], B[p], al[p], ga[p]);
     }
     // back substitution; slab p needs L_{p-1} and F_{p+1}
     double Fnext = 0.0;                            // F_{p+1}
 #pragma unroll
     for (int p = PMAX - 1; p >= 0; --p) {
         if (p >= q.P) continue;
-        const double F = A[p] + B[p] * Fnext;
-        const double Lprev = (p > 0) ? al[p - 1] + ga[p - 1] * F : 0.0;
+        double Lprev;
+        const int pp = p ? p - 1 : 0;
+        const double F = tri_red_back(p == 0, A[p], B[p], al[pp], ga[pp], Fnext, Lprev);
         double *mo = msg_out(p);
         mo[i] = Lprev;
         mo[q.nl + i] = Fnext;
@@ -282,9 +147,8 @@ __global__ void __launch_bounds__(128) k_tri_reduced(TriGeom g, TriReduced q, co
     }
 }
 
-// A_p x = g + e_first x_left + e_last x_right: forward D_t from the two running sums (no division), backward
-// x_t = rho (D_t + N_t x_{t+1}) / N_{t+1} (one fast division per row), N_t = 1 + s pe rho^(2t) from rho^t walked back up
-// from the last row at which it was still >= TRI_PW_SAFE (see above).
+// A_p x = g + e_first x_left + e_last x_right: forward step per row (xl / xr added to the first / last right-hand-side
+// entry), backward step per row with the power resumed from the last safe row (tri_sweep.h).
 // Generic slab length: D_t is parked in x between the sweeps (two reads and two writes of the slab).
 __global__ void __launch_bounds__(256) k_tri_final(TriGeom g, const double *__restrict__ back, double *__restrict__ x) {
     const i64 m = (i64)blockIdx.x * 256 + threadIdx.x;
@@ -300,33 +164,19 @@ __global__ void __launch_bounds__(256) k_tri_final(TriGeom g, const double *__re
     const bool first = g.first != 0, last = g.last != 0;
     const double sc = 1.0 / (g.kscale * g.beta);
     const double xl = back[off + (m - g.pc.cut[j])], xr = back[off + w + (m - g.pc.cut[j])];
-    const double spe = first ? c.rho : -c.rho2;                     // s pe of the front sequence
-    double H = 0.0, G = 0.0, pw = 1.0, D = 0.0;
-    int ts = 0;                                                     // last row with rho^t >= TRI_PW_SAFE, and that power
-    double pws = 1.0;
+    const double spe = tri_spe(c, first);                           // s pe of the front sequence
+    TriFwd<true> fw;
     for (int t = 0; t < n; ++t) {
         double gt = x[m + g.plane * t] * sc;
         if (t == 0) gt += xl;
         if (t == n - 1) gt += xr;
-        H = gt + c.rho * H;
-        G += pw * gt;
-        D = H + (spe * pw) * G;
-        x[m + g.plane * t] = D;
-        if (pw >= TRI_PW_SAFE) { ts = t; pws = pw; }
-        if (t + 1 < n) pw *= c.rho;
+        fw.step(c, spe, gt, t, t + 1 < n);
+        x[m + g.plane * t] = fw.D;
     }
-    const TriEnds f = tri_ends(c, first, n, pw);
-    double xn = tri_last(c, D, f.N1, f.Nn, last);
-    x[m + g.plane * (n - 1)] = xn;
-    double Nt1 = f.N1;
-    pw = pws;                                                       // (= rho^(n-1) unless that fell below TRI_PW_SAFE)
-    for (int t = n - 2; t >= 0; --t) {
-        if (t < ts) pw *= c.r;
-        const double Nt = (t == 0) ? f.N0 : ((t > ts) ? 1.0 : 1.0 + spe * (pw * pw));
-        xn = tri_div(c.rho * (x[m + g.plane * t] + Nt * xn), Nt1);
-        x[m + g.plane * t] = xn;
-        Nt1 = Nt;
-    }
+    const TriEnds f = tri_ends(c, first, n, fw.pw);
+    TriBwd<false, true> bw(c, f, fw, last, 0.0, 0.0);
+    x[m + g.plane * (n - 1)] = bw.xn;
+    for (int t = n - 2; t >= 0; --t) x[m + g.plane * t] = bw.step(c, f, spe, x[m + g.plane * t], t);
 }
 
 // Register-resident flavour for short slabs (ntl <= NTL): the column of a mode is read ONCE into registers, both sweeps
@@ -349,39 +199,24 @@ __global__ void __launch_bounds__(256) k_tri_final_reg(TriGeom g, const double *
     double X[NTL];
 #pragma unroll
     for (int t = 0; t < NTL; ++t) X[t] = (t < n) ? x[m + g.plane * t] : 0.0;
-    const double spe = first ? c.rho : -c.rho2;
-    double H = 0.0, G = 0.0, pw = 1.0, D = 0.0;
-    int ts = 0;                                                     // as in k_tri_final
-    double pws = 1.0;
+    const double spe = tri_spe(c, first);
+    TriFwd<true> fw;
 #pragma unroll
     for (int t = 0; t < NTL; ++t) {
         if (t < n) {
             double gt = X[t] * sc;
             if (t == 0) gt += xl;
             if (t == n - 1) gt += xr;
-            H = gt + c.rho * H;
-            G += pw * gt;
-            D = H + (spe * pw) * G;
-            X[t] = D;
-            if (pw >= TRI_PW_SAFE) { ts = t; pws = pw; }
-            if (t + 1 < n) pw *= c.rho;
+            fw.step(c, spe, gt, t, t + 1 < n);
+            X[t] = fw.D;
         }
     }
-    const TriEnds f = tri_ends(c, first, n, pw);
-    double xn = tri_last(c, D, f.N1, f.Nn, last);
-    double Nt1 = f.N1;
-    pw = pws;
+    const TriEnds f = tri_ends(c, first, n, fw.pw);
+    TriBwd<false, true> bw(c, f, fw, last, 0.0, 0.0);
 #pragma unroll
     for (int t = NTL - 1; t >= 0; --t) {
-        if (t == n - 1) {
-            X[t] = xn;
-        } else if (t < n - 1) {
-            if (t < ts) pw *= c.r;
-            const double Nt = (t == 0) ? f.N0 : ((t > ts) ? 1.0 : 1.0 + spe * (pw * pw));
-            xn = tri_div(c.rho * (X[t] + Nt * xn), Nt1);
-            X[t] = xn;
-            Nt1 = Nt;
-        }
+        if (t == n - 1) X[t] = bw.xn;
+        else if (t < n - 1) X[t] = bw.step(c, f, spe, X[t], t);
     }
 #pragma unroll
     for (int t = 0; t < NTL; ++t)
@@ -449,156 +284,43 @@ int launch_tri_final(const Grid &g, i64 nt, double kscale, const double *cy, con
 // D^2 ((CY + CX) I + T) phi^ = r^ per (ky, kx) mode, so the t axis needs no transform at all -- for ANY nt.  A workgroup of
 // NSUB wavefronts owns 64 consecutive modes (one coalesced 512-byte segment per time layer); wavefront w holds the rows
 // [t_w, t_{w+1}) of those modes in registers (R = 32 at nt = 128 / 129: ~110 registers, four waves per SIMD) and the NSUB
-// pieces of a column are coupled exactly like time slabs: scaled sweep from the front (D_t kept in the registers) and the
-// weighted sum from the back -> first / last entry of A_p^-1 g_p, exchanged through LDS -> every wave solves the small
-// reduced system of its modes (closed-form coefficients) -> backward sweep with the neighbours' interface values
-// (D_t is linear in the right-hand side: the left value enters as xl N_0 rho^t) -> one write.  One read and one write of
+// pieces of a column are coupled exactly like time slabs (tsolve_front / tsolve_back of tri_sweep.h: the tile solve both
+// kernels below share; each kernel is only the way a tile arrives and leaves).  One read and one write of
 // the array, ~20 flops per entry: bound by HBM where the fused transform pass (two FFTs, seven barriers per tile) is
 // bound by its own LDS / VALU chain.  Measured: 0.62 ms at 1024 x 1024 x 128 against 0.56 ms for the pipelined transform pass
 // (which therefore stays for the power-of-two lengths), 0.66 ms at 1025 x 1025 x 129 against 0.86 ms for the prime-factor pass,
 // and no dense t-axis product at all for the other lengths: the default whenever nt is no power of two (Solver::poisson_all).
-// The singular (0, 0) mode: its column is parked in LDS, one thread runs k_tri_reduced's recurrence on it.
+struct TsPiece {
+    int t0, n;                // rows [t0, t0 + n) of piece w: as evenly as possible (dotsocp_slab_range_impl's rule)
+};
+template <int NSUB>
+__device__ __forceinline__ TsPiece ts_piece(i64 nt, int w) {
+    const int base = (int)(nt / NSUB), rem = (int)(nt % NSUB);
+    auto t_begin = [&](int p) { return p * base + (p < rem ? p : rem); };
+    const int t0 = t_begin(w);
+    return TsPiece{t0, t_begin(w + 1) - t0};
+}
+
+// One tile per workgroup: global loads, the tile solve, stores.
 template <int R, int NSUB>
 __global__ void __launch_bounds__(64 * NSUB) k_tsolve_single(TriGeom g, i64 nt, double *__restrict__ x) {
-    // per piece and mode: first / last entry of A_p^-1 g_p and the piece's four spike values; then the interface values
     __shared__ double ex[NSUB][6][64];
-    __shared__ double sw[NSUB][4][64];                 // the reduced sweep's A, B, al, ga (wave 0)
-    __shared__ double zcol[NSUB * R];                  // the singular mode's column (workgroup 0 only)
+    __shared__ double zcol[NSUB * R];
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const i64 m = (i64)blockIdx.x * 64 + lane;
     const bool ok = m < g.plane;
     const i64 mc = ok ? m : 0;
-    // rows of piece p: as evenly as possible (dotsocp_slab_range_impl's rule)
-    const int base = (int)(nt / NSUB), rem = (int)(nt % NSUB);
-    auto t_begin = [&](int p) { return p * base + (p < rem ? p : rem); };
-    const int t0 = t_begin(w), n = t_begin(w + 1) - t0;
-    const bool first = (w == 0), last = (w == NSUB - 1);
+    const TsPiece pc = ts_piece<NSUB>(nt, w);
+    const int t0 = pc.t0, n = pc.n;
     const double sc = 1.0 / (g.kscale * g.beta);
     double X[R];
 #pragma unroll
     for (int t = 0; t < R; ++t) X[t] = (t < n) ? x[mc + g.plane * (t0 + t)] * sc : 0.0;
-    const bool zero = (m == 0);
-    const TriCoef c = tri_coef(zero ? 1.0 : tri_aprime(g, mc));      // (the singular mode takes its own path below)
-    if (blockIdx.x == 0 && lane == 0) {
-#pragma unroll
-        for (int t = 0; t < R; ++t)
-            if (t < n) zcol[t0 + t] = X[t];
-    }
-    // ---- local eliminations (the two running sums, see above) ----
-    const double spe = first ? c.rho : -c.rho2;
-    double H = 0.0, G = 0.0, pw = 1.0, D = 0.0;
-#pragma unroll
-    for (int t = 0; t < R; ++t) {
-        if (t < n) {
-            const double gt = X[t];
-            H = gt + c.rho * H;
-            G += pw * gt;
-            D = H + (spe * pw) * G;
-            X[t] = D;
-            if (t + 1 < n) pw *= c.rho;                            // ends as rho^(n-1)
-        }
-    }
-    const TriEnds f = tri_ends(c, first, n, pw), b = tri_ends(c, last, n, pw);
-    if (NSUB > 1) {
-        ex[w][0][lane] = tri_last(c, G + ((b.s * b.pe) * pw) * H, b.N1, b.Nn, first);
-        ex[w][1][lane] = tri_last(c, D, f.N1, f.Nn, last);
-        // the piece's spike values (tri_spike, from the ends already at hand)
-        double vf, vl, wf, wl;
-        if (last) {
-            const double den = c.r * f.Nn - f.N1;
-            vl = tri_div(pw * f.N0, den);
-            wl = tri_div(f.N1, den);
-        } else {
-            vl = tri_div((pw * c.rho) * f.N0, f.Nn);
-            wl = tri_div(c.rho * f.N1, f.Nn);
-        }
-        if (first) {
-            const double den = c.r * b.Nn - b.N1;
-            wf = tri_div(pw * b.N0, den);
-            vf = tri_div(b.N1, den);
-        } else {
-            wf = tri_div((pw * c.rho) * b.N0, b.Nn);
-            vf = tri_div(c.rho * b.N1, b.Nn);
-        }
-        ex[w][2][lane] = first ? 0.0 : vf;
-        ex[w][3][lane] = first ? 0.0 : vl;
-        ex[w][4][lane] = last ? 0.0 : wf;
-        ex[w][5][lane] = last ? 0.0 : wl;
-    }
+    const bool zero = (m == 0), tile0 = (blockIdx.x == 0);
+    const TsMid k = tsolve_front<R, NSUB>(ex, zcol, X, zero ? 1.0 : tri_aprime(g, mc), w, lane, t0, n, tile0);
     __syncthreads();
-    // ---- reduced system of the NSUB pieces (k_tri_reduced's sweep), by wave 0 for the workgroup's 64 modes ----
-    double xl = 0.0, xr = 0.0;
-    if (NSUB > 1) {
-        if (w == 0) {
-#pragma unroll 1
-            for (int p = 0; p < NSUB; ++p) {
-                const double Gf = ex[p][0][lane], Gl = ex[p][1][lane];
-                const double vf = ex[p][2][lane], vl = ex[p][3][lane], wf = ex[p][4][lane], wl = ex[p][5][lane];
-                double A, B, al, ga;
-                if (p == 0) {
-                    A = Gf; B = wf; al = Gl; ga = wl;
-                } else {
-                    const double alp = sw[p - 1][2][lane], gap = sw[p - 1][3][lane];
-                    const double den = 1.0 - vf * gap;
-                    A = (Gf + vf * alp) / den;
-                    B = wf / den;
-                    al = Gl + vl * (alp + gap * A);
-                    ga = wl + vl * gap * B;
-                }
-                sw[p][0][lane] = A; sw[p][1][lane] = B; sw[p][2][lane] = al; sw[p][3][lane] = ga;
-            }
-            double Fnext = 0.0;
-#pragma unroll 1
-            for (int p = NSUB - 1; p >= 0; --p) {
-                const double Fp = sw[p][0][lane] + sw[p][1][lane] * Fnext;
-                const double Lprev = (p > 0) ? sw[p - 1][2][lane] + sw[p - 1][3][lane] * Fp : 0.0;
-                ex[p][0][lane] = Lprev;                            // the piece's left / right interface values
-                ex[p][1][lane] = Fnext;
-                Fnext = Fp;
-            }
-        }
-        __syncthreads();
-        xl = ex[w][0][lane];
-        xr = ex[w][1][lane];
-    }
-    // ---- the singular mode ----
-    if (blockIdx.x == 0) {
-        if (threadIdx.x == 0) {
-            // T x = g - mean(g) by recurrence from x_0 = 0, then zero mean, plus beta * mean(g) (k_tri_reduced)
-            double sum = 0.0;
-            for (i64 t = 0; t < nt; ++t) sum += zcol[t];
-            const double gbar = sum / (double)nt;
-            double xm = 0.0, xc = 0.0, acc = 0.0;
-            for (i64 t = 0; t < nt; ++t) {
-                const double gt = zcol[t] - gbar;
-                zcol[t] = xc;
-                acc += xc;
-                const double xn = (t == 0) ? xc - gt : 2.0 * xc - xm - gt;
-                xm = xc;
-                xc = xn;
-            }
-            const double shift = g.beta * gbar - acc / (double)nt;
-            for (i64 t = 0; t < nt; ++t) zcol[t] += shift;
-        }
-        __syncthreads();
-    }
-    // ---- backward sweep with the interface values ----
-    const double cl = xl * f.N0;                                   // D_t gains cl rho^t; D_{n-1} also xr N_{n-1}
-    double xn = tri_last(c, (D + cl * pw) + xr * f.N1, f.N1, f.Nn, last);
-    double Nt1 = f.N1;
-#pragma unroll
-    for (int t = R - 1; t >= 0; --t) {
-        if (t == n - 1) {
-            X[t] = xn;
-        } else if (t < n - 1) {
-            pw *= c.r;                                             // rho^t
-            const double Nt = (t == 0) ? f.N0 : 1.0 + spe * (pw * pw);
-            xn = tri_div(c.rho * ((X[t] + cl * pw) + Nt * xn), Nt1);
-            X[t] = xn;
-            Nt1 = Nt;
-        }
-    }
+    tsolve_back<R, NSUB, false>(ex, zcol, X, k, w, lane, n, tile0, nt, g.beta);
     if (ok) {
 #pragma unroll
         for (int t = 0; t < R; ++t)
@@ -610,20 +332,20 @@ __global__ void __launch_bounds__(64 * NSUB) k_tsolve_single(TriGeom g, i64 nt, 
 // 64 modes; the rows of the NEXT tile travel into an LDS image [row][mode] by global_load_lds_dwordx4 (no registers) while
 // the current tile is eliminated in registers and stored, so loads are in flight all the time -- the one-tile-per-workgroup
 // kernel above alternates between loading and computing (0.62 ms at nt = 128 where the traffic takes 0.4).  One LDS image:
-// the DMA of tile i + 1 is issued behind the barrier that follows the forward sweep of tile i (every wave has copied its
+// the DMA of tile i + 1 is issued behind the barrier that follows the front half of tile i (every wave has copied its
 // rows to registers by then); it has landed when only the stores issued after it are outstanding (vector-memory operations
-// of a wave complete in issue order) -- counted waits and raw barriers, a fence would drain the counter.
+// of a wave complete in issue order) -- counted waits and raw barriers, a fence would drain the counter.  The counts hold
+// because a wave issues exactly n stores per tile behind the DMA and no other vector-memory instruction: the tile solve
+// must not spill.
 template <int R, int NSUB>
 __global__ void __launch_bounds__(64 * NSUB) k_tsolve_pipe(TriGeom g, i64 nt, int nTiles, double *__restrict__ x) {
     extern __shared__ double img[];                    // [nt rounded up to even][64]
-    __shared__ double ex[NSUB][6][64];                 // per piece: Gf, Gl, vf, vl, wf, wl -> xl, xr, A, B, al, ga (in place)
+    __shared__ double ex[NSUB][6][64];
     __shared__ double zcol[NSUB * R];
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int base = (int)(nt / NSUB), rem = (int)(nt % NSUB);
-    auto t_begin = [&](int p) { return p * base + (p < rem ? p : rem); };
-    const int t0 = t_begin(w), n = t_begin(w + 1) - t0;
-    const bool first = (w == 0), last = (w == NSUB - 1);
+    const TsPiece pc = ts_piece<NSUB>(nt, w);
+    const int t0 = pc.t0, n = pc.n;
     const double sc = 1.0 / (g.kscale * g.beta);
     const unsigned ldsBase = (unsigned)(uintptr_t)img;
     const int npairs = (int)((nt + 1) / 2);            // one DMA instruction moves two rows (2 x 512 bytes)
@@ -654,123 +376,12 @@ __global__ void __launch_bounds__(64 * NSUB) k_tsolve_pipe(TriGeom g, i64 nt, in
 #pragma unroll
         for (int t = 0; t < R; ++t) X[t] = (t < n) ? img[(t0 + t) * 64 + lane] * sc : 0.0;
         const bool zero = (m == 0);
-        const TriCoef c = tri_coef(zero ? 1.0 : tri_aprime(g, mc));
-        if (tile == 0 && lane == 0) {
-#pragma unroll
-            for (int t = 0; t < R; ++t)
-                if (t < n) zcol[t0 + t] = X[t];
-        }
-        const double spe = first ? c.rho : -c.rho2;
-        double H = 0.0, G = 0.0, pw = 1.0, D = 0.0;
-#pragma unroll
-        for (int t = 0; t < R; ++t) {
-            if (t < n) {
-                const double gt = X[t];
-                H = gt + c.rho * H;
-                G += pw * gt;
-                D = H + (spe * pw) * G;
-                X[t] = D;
-                if (t + 1 < n) pw *= c.rho;
-            }
-        }
-        const TriEnds f = tri_ends(c, first, n, pw), b = tri_ends(c, last, n, pw);
-        if (NSUB > 1) {
-            ex[w][0][lane] = tri_last(c, G + ((b.s * b.pe) * pw) * H, b.N1, b.Nn, first);
-            ex[w][1][lane] = tri_last(c, D, f.N1, f.Nn, last);
-            double vf, vl, wf, wl;
-            if (last) {
-                const double den = c.r * f.Nn - f.N1;
-                vl = tri_div(pw * f.N0, den);
-                wl = tri_div(f.N1, den);
-            } else {
-                vl = tri_div((pw * c.rho) * f.N0, f.Nn);
-                wl = tri_div(c.rho * f.N1, f.Nn);
-            }
-            if (first) {
-                const double den = c.r * b.Nn - b.N1;
-                wf = tri_div(pw * b.N0, den);
-                vf = tri_div(b.N1, den);
-            } else {
-                wf = tri_div((pw * c.rho) * b.N0, b.Nn);
-                vf = tri_div(c.rho * b.N1, b.Nn);
-            }
-            ex[w][2][lane] = first ? 0.0 : vf;
-            ex[w][3][lane] = first ? 0.0 : vl;
-            ex[w][4][lane] = last ? 0.0 : wf;
-            ex[w][5][lane] = last ? 0.0 : wl;
-        }
+        const TsMid k = tsolve_front<R, NSUB>(ex, zcol, X, zero ? 1.0 : tri_aprime(g, mc), w, lane, t0, n, tile == 0);
         lds_barrier();                                 // every wave has its rows in registers: the image is free
         if (tile + stride < nTiles) dma(tile + stride);
-        double xl = 0.0, xr = 0.0;
-        if (NSUB > 1) {
-            if (w == 0) {
-#pragma unroll 1
-                for (int p = 0; p < NSUB; ++p) {
-                    const double Gf = ex[p][0][lane], Gl = ex[p][1][lane];
-                    const double vf = ex[p][2][lane], vl = ex[p][3][lane], wf = ex[p][4][lane], wl = ex[p][5][lane];
-                    double A, B, al, ga;
-                    if (p == 0) {
-                        A = Gf; B = wf; al = Gl; ga = wl;
-                    } else {
-                        const double alp = ex[p - 1][4][lane], gap = ex[p - 1][5][lane];
-                        const double den = 1.0 - vf * gap;
-                        A = (Gf + vf * alp) / den;
-                        B = wf / den;
-                        al = Gl + vl * (alp + gap * A);
-                        ga = wl + vl * gap * B;
-                    }
-                    ex[p][2][lane] = A; ex[p][3][lane] = B; ex[p][4][lane] = al; ex[p][5][lane] = ga;
-                }
-                double Fnext = 0.0;
-#pragma unroll 1
-                for (int p = NSUB - 1; p >= 0; --p) {
-                    const double Fp = ex[p][2][lane] + ex[p][3][lane] * Fnext;
-                    const double Lprev = (p > 0) ? ex[p - 1][4][lane] + ex[p - 1][5][lane] * Fp : 0.0;
-                    ex[p][0][lane] = Lprev;
-                    ex[p][1][lane] = Fnext;
-                    Fnext = Fp;
-                }
-            }
-            lds_barrier();
-            xl = ex[w][0][lane];
-            xr = ex[w][1][lane];
-        }
-        if (tile == 0) {                               // the singular mode (k_tri_reduced's recurrence)
-            if (threadIdx.x == 0) {
-                double sum = 0.0;
-                for (i64 t = 0; t < nt; ++t) sum += zcol[t];
-                const double gbar = sum / (double)nt;
-                double xm = 0.0, xc = 0.0, acc = 0.0;
-                for (i64 t = 0; t < nt; ++t) {
-                    const double gt = zcol[t] - gbar;
-                    zcol[t] = xc;
-                    acc += xc;
-                    const double xn = (t == 0) ? xc - gt : 2.0 * xc - xm - gt;
-                    xm = xc;
-                    xc = xn;
-                }
-                const double shift = g.beta * gbar - acc / (double)nt;
-                for (i64 t = 0; t < nt; ++t) zcol[t] += shift;
-            }
-            lds_barrier();
-        }
-        const double cl = xl * f.N0;
-        double xn = tri_last(c, (D + cl * pw) + xr * f.N1, f.N1, f.Nn, last);
-        double Nt1 = f.N1;
-#pragma unroll
-        for (int t = R - 1; t >= 0; --t) {
-            if (t == n - 1) {
-                X[t] = xn;
-            } else if (t < n - 1) {
-                pw *= c.r;
-                const double Nt = (t == 0) ? f.N0 : 1.0 + spe * (pw * pw);
-                xn = tri_div(c.rho * ((X[t] + cl * pw) + Nt * xn), Nt1);
-                X[t] = xn;
-                Nt1 = Nt;
-            }
-        }
-        // exactly n stores per wave and tile (the wait at the top counts them): lanes beyond the plane rewrite a valid entry
-        // of their own tile's last mode?  no -- they store nothing: the count is per wave instruction, not per lane
+        tsolve_back<R, NSUB, true>(ex, zcol, X, k, w, lane, n, tile == 0, nt, g.beta);
+        // exactly n stores per wave and tile (the wait at the top counts them; the count is per wave instruction, not per
+        // lane: lanes beyond the plane store nothing)
 #pragma unroll
         for (int t = 0; t < R; ++t)
             if (t < n) {
@@ -779,25 +390,14 @@ __global__ void __launch_bounds__(64 * NSUB) k_tsolve_pipe(TriGeom g, i64 nt, in
     }
 }
 
-static int tri_device_cus() {
-    static int cus[64] = {0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-    if (!cus[dev]) {
-        hipDeviceProp_t pr;
-        cus[dev] = (hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0) ? pr.multiProcessorCount : 256;
-    }
-    return cus[dev];
-}
-
 bool tsolve_tri_supported(i64 nt) { return nt >= 2 && nt <= 512; }
 
 // wavefronts (= pieces of a column) of the kernel launch_tsolve_tri picks for nt: the table of TSOLVE() below; k_tsolve_pipe: 4
 static int tsolve_nsub(i64 nt) { return nt <= 8 ? 1 : (nt <= 32 ? 2 : (nt <= 136 ? 4 : 8)); }
 
 // Do the powers rho^t of every mode stay >= TRI_PW_SAFE over a piece (n = ceil(nt / NSUB) rows)?  The backward sweeps of
-// k_tsolve_single / k_tsolve_pipe walk rho^t back up from rho^(n-1) and are wrong once that has left the normal range (see
-// TRI_PW_SAFE).  Largest a': CY, CX <= 4 (n-1)^2.  Pure host arithmetic (dotsocp_tsolve_tri_safe).
+// k_tsolve_single / k_tsolve_pipe walk rho^t back up from rho^(n-1) and are wrong once that has left the normal range
+// (TriBwd<., KEEP = false>, tri_sweep.h).  Largest a': CY, CX <= 4 (n-1)^2.  Pure host arithmetic (dotsocp_tsolve_tri_safe).
 bool tsolve_tri_safe(i64 ny, i64 nx, i64 nt) {
     if (!tsolve_tri_supported(nt)) return false;
     const int nsub = tsolve_nsub(nt);
@@ -815,7 +415,7 @@ static bool tsolve_pipe_on() {
 // the persistent LDS-DMA flavour: grids with enough tiles to keep two workgroups per CU busy for many rounds; its image
 // fits twice into a CU's LDS up to nt = 136
 static bool tsolve_pipe_fits(i64 nt, i64 plane) {
-    return nt > 64 && nt <= 136 && (plane + 63) / 64 >= 16 * (i64)tri_device_cus() && (plane % 2) == 0;
+    return nt > 64 && nt <= 136 && (plane + 63) / 64 >= 16 * (i64)device_cus() && (plane % 2) == 0;
 }
 // Is the tridiagonal solve the faster t-axis solve of a single slab?  Every length without a power-of-two transform pass
 // (prime-factor lengths 0.66 vs 0.86 ms at 1025 x 1025 x 129, and no dense product along t for the rest); powers of two
@@ -836,7 +436,7 @@ int launch_tsolve_tri(const Grid &g, i64 nt, double kscale, const double *cy, co
     const int nTiles = (int)((g.plane + 63) / 64);
     const size_t img = (size_t)((nt + 1) / 2) * 2 * 64 * sizeof(double);
     // persistent LDS-DMA flavour (DOTSOCP_TS_PIPE=0: the one-tile-per-workgroup kernel)
-    const int G = 2 * tri_device_cus();
+    const int G = 2 * device_cus();
     const bool pipe = tsolve_pipe_on() && tsolve_pipe_fits(nt, g.plane);
     if (pipe) {
         static std::mutex mu;

@@ -192,11 +192,14 @@ def test_oper_poisson(ny, nx, nt):
     np.testing.assert_allclose(got, ref, rtol=0, atol=1e-12 * np.abs(ref).max())
 
 
-@pytest.mark.parametrize("ny,nx,nt", [(512, 512, 72), (1024, 512, 128), (514, 520, 129)])
+@pytest.mark.parametrize("ny,nx,nt", [(512, 512, 72), (1024, 512, 128), (514, 520, 129), (512, 512, 133), (512, 512, 136)])
 def test_tridiagonal_t_solve_flavours_agree(ny, nx, nt, monkeypatch):
     """The t axis of the Poisson solve as tridiagonal systems: the persistent LDS-DMA kernel (k_tsolve_pipe), the
-    one-tile-per-workgroup kernel (DOTSOCP_TS_PIPE=0) -- the same arithmetic on the same registers, bit for bit -- and the
-    transform passes along t (DOTSOCP_TSOLVE=dct), another algorithm for the same linear systems: rounding."""
+    one-tile-per-workgroup kernel (DOTSOCP_TS_PIPE=0) -- the same tile solve (tri_sweep.h) on the same registers, bit for
+    bit -- and the transform passes along t (DOTSOCP_TSOLVE=dct), another algorithm for the same linear systems: rounding.
+    512 x 512 is the smallest plane that takes the persistent kernel on 256 compute units (4096 tiles); nt = 133: pieces of
+    34 / 33 / 33 / 33 rows, so the waves of a workgroup wait on different counts (n == R on wave 0 only); 136: n == R == 34 on
+    every wave."""
     rhs = np.asfortranarray(np.random.default_rng(5).standard_normal((ny, nx, nt)))
     a = D.oper_poisson3dim(0.37 ** 2, rhs)
     monkeypatch.setenv("DOTSOCP_TS_PIPE", "0")

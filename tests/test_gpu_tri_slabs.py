@@ -28,6 +28,14 @@ zero-mode recurrence at nt = 512.  The shapes are the smallest grids that reach 
   8 (2048, 4, 262)  2048^2 x 256 on two GPUs in miniature: n = 131, r = 248, rho^130 = 1e-311 (denormal)
   9 (3, 4096, 505)  ONE slab (the 4096-point axis along x: the y transform stops at 2048): pieces of 64 rows, a' up to 264, rho^63 < TRI_PW_SAFE: k_tsolve_single, which walks its
                     powers up from rho^(n-1), must not be launched (tsolve_tri_safe) -- the transform passes along t run
+  10 .. 18 (66, 5, nt) on ONE slab, one shape per k_tsolve_single<R, NSUB> instance (two pitched rows per tile; the tile
+                    solve is the one k_tsolve_pipe shares, tri_sweep.h): nt = 5 <8, 1> (no reduced sweep), 12 <8, 2>,
+                    23 <16, 2> (pieces of 12 / 11 rows), 49 <16, 4> (13 / 12 / 12 / 12), 100 <32, 4>, 133 <34, 4>
+                    (34 / 33 / 33 / 33: n == R on wave 0 only), 200 <32, 8>, 270 <34, 8>, 500 <64, 8>
+  19 (514, 3, 200)  ONE slab, small but legal powers: a' up to 27, rho^24 = 1e-35
+  20 (2048, 1, 505) 1-D, ONE slab: pieces of 64 / 63 rows, rho^63 = 4e-116, dotsocp_tsolve_tri_safe = 1
+The CPU model on the pieces of shapes 10 .. 20 (the left interface as xl N_0 rho^t, the power walked up from rho^(n-1)) stays
+below 1e-2 of the bound at every probed mode.
 
 Before the backward sweeps of k_tri_final / k_tri_final_reg resumed rho^t from the last row at which it was still safely
 normal (TRI_PW_SAFE), rows 6 (two slabs: 3.0e-6 at ky = 1024) and 7 (9.6e-8 at ky = 2046) missed the bound by five to six
@@ -47,11 +55,14 @@ PI = 4 * np.arctan(LD(1))           # np.pi would leave the reference itself goo
 DSC = 0.37
 
 SHAPES = {1: ((130, 9, 40), 2), 2: ((66, 10, 80), 2), 3: ((66, 10, 140), 2), 4: ((34, 6, 512), 2), 5: ((34, 6, 514), 2),
-          6: ((2048, 1, 512), 1), 7: ((2048, 4, 340), 2), 8: ((2048, 4, 262), 2), 9: ((3, 4096, 505), 2)}
+          6: ((2048, 1, 512), 1), 7: ((2048, 4, 340), 2), 8: ((2048, 4, 262), 2), 9: ((3, 4096, 505), 2),
+          10: ((66, 5, 5), 2), 11: ((66, 5, 12), 2), 12: ((66, 5, 23), 2), 13: ((66, 5, 49), 2), 14: ((66, 5, 100), 2),
+          15: ((66, 5, 133), 2), 16: ((66, 5, 200), 2), 17: ((66, 5, 270), 2), 18: ((66, 5, 500), 2),
+          19: ((514, 3, 200), 2), 20: ((2048, 1, 505), 1)}
 LAYOUTS = [(1, dict(nslabs=1)), (1, dict(nslabs=2)), (1, dict(nslabs=3)), (1, dict(nslabs=12)), (1, dict(nslabs=20)),
            (1, dict(ngpu=2)), (2, dict(nslabs=2)), (3, dict(nslabs=2)), (4, dict(nslabs=1)), (4, dict(nslabs=2)),
            (4, dict(nslabs=4)), (5, dict(nslabs=2)), (6, dict(nslabs=2)), (6, dict(nslabs=4)), (7, dict(nslabs=2)),
-           (8, dict(nslabs=2)), (9, dict(nslabs=1))]
+           (8, dict(nslabs=2)), (9, dict(nslabs=1))] + [(no, dict(nslabs=1)) for no in range(10, 21)]
 
 
 def _id(case):

@@ -1,8 +1,9 @@
-"""The algebra behind the division-free tridiagonal kernels of dot-socp_amd/csrc/tri.hip (round 4), restated in numpy
-and held against dense solves: closed-form pivots piv_t = r N_{t+1} / N_t, the two running sums H_t = g_t + rho H_{t-1},
-G_t = sum rho^s g_s from which both sweeps of a column come (tri_ends / tri_last / tri_spike / k_tri_final's backward
-sweep), for blocks that start / end on a global Neumann row or couple to a neighbour slab.  A CPU test of the device
-code's mathematics -- the kernels themselves are checked against scipy's DCT and the single slab in the GPU suite."""
+"""The algebra behind the division-free tridiagonal kernels of dot-socp_amd/csrc/tri.hip (round 4; the sweeps themselves:
+tri_sweep.h), restated in numpy and held against dense solves: closed-form pivots piv_t = r N_{t+1} / N_t, the two running
+sums H_t = g_t + rho H_{t-1}, G_t = sum rho^s g_s from which both sweeps of a column come (tri_ends / tri_last / tri_spike /
+TriFwd / TriBwd: _piece() with its flags into_rhs = !LEFT and keep_power = KEEP), for blocks that start / end on a global
+Neumann row or couple to a neighbour slab.  A CPU test of the device code's mathematics -- the kernels themselves are
+checked against scipy's DCT and the single slab in the GPU suite."""
 import numpy as np
 import pytest
 

@@ -73,6 +73,7 @@ SYMBOLS = {
     "dotsocp_slab_range": (ctypes.c_int, [i64, ctypes.c_int, ctypes.c_int, ctypes.POINTER(i64), ctypes.POINTER(i64)]),
     "dotsocp_field_len": (i64, [ctypes.POINTER(Problem), ctypes.c_int]),
     "dotsocp_dct_algorithm": (ctypes.c_int, [i64]),
+    "dotsocp_dct_levels": (ctypes.c_int, [i64, ctypes.c_int]),
     "dotsocp_tsolve_tri_safe": (ctypes.c_int, [i64, i64, i64]),
     "dotsocp_cone_writes_beta": (ctypes.c_int, [i64, dbl, i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, dbl, dbl]),
     "dotsocp_rescale_due": (ctypes.c_int, [i64, ctypes.c_int, dbl, dbl]),
@@ -174,3 +175,11 @@ def dct_algorithm(n):
     """The transform the DCT passes use for an axis of length n: "fft" (power of two), "pfa" (prime-factor lengths),
     "rader" (257), "bluestein" (other lengths up to 1024), "dense" (DCT-matrix product) or "none" (n <= 1).  No device needed."""
     return DCT_ALGORITHMS[lib().dotsocp_dct_algorithm(int(n))]
+
+
+def dct_levels(n, axis):
+    """Passes through memory that the transform of an axis of length n takes along `axis` (0: y, the contiguous one; 1: x;
+    2: t): 0 no transform (n <= 1), 1 one pass with the whole line in LDS, 2 the two-level transform for power-of-two
+    lines beyond the LDS (from 4096 along y and 16384 along x / t up to 2^20; DOTSOCP_DCT_LONG_MIN lowers the start),
+    negative: unsupported.  No device needed."""
+    return int(lib().dotsocp_dct_levels(int(n), int(axis)))

@@ -180,6 +180,7 @@ struct Plans {
     DctPlan *py = nullptr, *px = nullptr, *pt = nullptr;
     ~Plans() { dct_plan_destroy(py); dct_plan_destroy(px); dct_plan_destroy(pt); }
     int make(i64 ny, i64 nx, i64 nt) {
+        DS_CHECK(dct_length_check(ny)); DS_CHECK(dct_length_check(nx)); DS_CHECK(dct_length_check(nt));
         py = dct_plan_create(ny); px = dct_plan_create(nx); pt = dct_plan_create(nt);
         if (!py || !px || !pt) { set_error("DCT plan allocation failed"); return DOTSOCP_EHIP; }
         return 0;
@@ -188,6 +189,7 @@ struct Plans {
 
 int dotsocp_dctn(double *a, dotsocp_i64 ny, dotsocp_i64 nx, dotsocp_i64 nt, int inverse) {
     DS_ARG(a && ny >= 1 && nx >= 1 && nt >= 1, "bad array");
+    DS_CHECK(dct_length_check(ny)); DS_CHECK(dct_length_check(nx)); DS_CHECK(dct_length_check(nt));
     DS_CHECK(require_device());
     const i64 n = ny * nx * nt;
     DevBuf da, db;
@@ -205,6 +207,7 @@ int dotsocp_dctn(double *a, dotsocp_i64 ny, dotsocp_i64 nx, dotsocp_i64 nt, int 
 int dotsocp_oper_poisson(double *res, const double *rhs, dotsocp_i64 ny, dotsocp_i64 nx, dotsocp_i64 nt,
                          double kernelScale) {
     DS_ARG(res && rhs && ny >= 1 && nx >= 1 && nt >= 1, "bad array");
+    DS_CHECK(dct_length_check(ny)); DS_CHECK(dct_length_check(nx)); DS_CHECK(dct_length_check(nt));
     DS_CHECK(require_device());
     const i64 n = ny * nx * nt;
     DevBuf da, db, cy, cx, ct;
@@ -288,6 +291,7 @@ int dotsocp_attach_rccl(dotsocp_ctx *ctx, const unsigned char id[128], int rank,
     } while (0)
 
 int dotsocp_dct_algorithm(dotsocp_i64 n) { return dct_choose_algorithm(n); }
+int dotsocp_dct_levels(dotsocp_i64 n, int axis) { return dct_levels(n, axis); }
 int dotsocp_tsolve_tri_safe(dotsocp_i64 ny, dotsocp_i64 nx, dotsocp_i64 nt) { return tsolve_tri_safe(ny, nx, nt) ? 1 : 0; }
 
 int dotsocp_cone_writes_beta(dotsocp_i64 it, double last_sigma_it, dotsocp_i64 maxit, int check_step_by_step,

@@ -6,6 +6,7 @@
 // plan is made, the plan stores that choice (`alg`) beside the chosen family's own plan, and every launcher below
 // switches on it:
 //   powers of two                         Makhoul's reordering + FFT in LDS            dct_pow2.hip
+//     ... from 4096 (y) / 16384 (x, t) up to 2^20: two-level FFT through a scratch array   dct_long.hip
 //   the 2^k+1 grids of the multilevel driver   prime-factor transform                  pfa.hip
 //   257 and the other lengths up to 1024  Rader / Bluestein convolution                cdft.hip
 //   the rest                              product with the dense DCT matrix            dct_dense.hip
@@ -82,7 +83,10 @@ void dct_plan_destroy(DctPlan *p) {
 }
 
 bool dct_plan_is_pow2(const DctPlan *p) { return p->alg == DCT_ALG_FFT; }
-bool dct_plan_has_tsolve(const DctPlan *p) { return p->alg == DCT_ALG_FFT || p->alg == DCT_ALG_PFA; }
+// (a t length that takes the two-level transform has no fused pass: forward pass, division, inverse pass)
+bool dct_plan_has_tsolve(const DctPlan *p) {
+    return (p->alg == DCT_ALG_FFT && p->n < dct_long_min(2)) || p->alg == DCT_ALG_PFA;
+}
 
 __global__ void __launch_bounds__(256) k_copy(const double *__restrict__ src, double *__restrict__ dst, i64 n) {
     for (i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (i64)gridDim.x * blockDim.x) dst[i] = src[i];
@@ -92,7 +96,7 @@ int launch_dct_t_solve(const DctPlan *p, const double *src, double *dst, i64 ny,
                        i64 nt, double kscale, const double *cy, const double *cx, const double *ct, hipStream_t st,
                        i64 pitch0) {
     if (p->n != nt || !dct_plan_has_tsolve(p)) {
-        set_error("fused t-axis solve needs a power-of-two nt or one of the prime-factor lengths");
+        set_error("fused t-axis solve needs a power-of-two nt inside the LDS or one of the prime-factor lengths");
         return DOTSOCP_EINVAL;
     }
     const bool pitched = pitch0 > ny;

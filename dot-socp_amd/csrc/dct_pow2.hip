@@ -23,6 +23,7 @@ struct Pow2Plan {
     int lg;         // n = 2^lg
     double2 *tw;    // [n/2]  exp(-2 pi i k / n)
     double2 *ww;    // [n]    2 exp(-i pi k / 2n) / sqrt(2n), ww[0] /= sqrt(2)   (mirt_dctn.m:69-70)
+    LongPlan *lng;  // lines of this length leave the LDS along some axis: the two-level transform (dct_long.hip)
 };
 
 Pow2Plan *pow2_plan_create(i64 n) {
@@ -32,6 +33,17 @@ Pow2Plan *pow2_plan_create(i64 n) {
     while (((i64)1 << p->lg) < n) ++p->lg;
     p->tw = nullptr;
     p->ww = nullptr;
+    p->lng = nullptr;
+    if (n > DCT_LONG_MAX_N) {                // refused when the plan is made (dct_length_check has the message)
+        delete p;
+        return nullptr;
+    }
+    const i64 firstLong = dct_long_min(0) < dct_long_min(1) ? dct_long_min(0) : dct_long_min(1);
+    if (n >= firstLong && !(p->lng = long_plan_create(n))) {
+        delete p;
+        return nullptr;
+    }
+    if (n >= dct_long_min(0) && n >= dct_long_min(1)) return p;      // no axis keeps such lines in the LDS: no tables
     const long double PI = 3.141592653589793238462643383279502884L;
     std::vector<double2> tw(n / 2), ww(n);
     for (i64 k = 0; k < n / 2; ++k) {
@@ -58,6 +70,7 @@ void pow2_plan_destroy(Pow2Plan *p) {
     if (!p) return;
     if (p->tw) (void)hipFree(p->tw);
     if (p->ww) (void)hipFree(p->ww);
+    long_plan_destroy(p->lng);
     delete p;
 }
 
@@ -275,10 +288,11 @@ __global__ void __launch_bounds__(DCT_THREADS) k_dct_strided(const double *__res
             for (int b = lane; b < total; b += 64) {
                 const int rr = b >> lh;
                 double2 *r = rows + rr * rowStride;
+                // (an odd line count leaves the last pair with line a alone: it keeps ITS eigenvalue, line b's is unused)
                 i64 La = L0 + 2 * ((wave << lrw) + rr);
-                if (La + 1 >= map.nLines) La = (map.nLines >= 2) ? map.nLines - 2 : 0;
+                if (La >= map.nLines) La = map.nLines - 1;
                 const i64 Ga = sa.line0 + La;
-                const i64 Gb = (Ga + 1 < sa.nplane) ? Ga + 1 : Ga;
+                const i64 Gb = (La + 1 < map.nLines && Ga + 1 < sa.nplane) ? Ga + 1 : Ga;
                 const double ea = sa.cy[Ga % sa.ny] + sa.cx[Ga / sa.ny];                    // CY + CX of line a
                 const double eb = sa.cy[Gb % sa.ny] + sa.cx[Gb / sa.ny];
                 const int k = (b & ((1 << lh) - 1)) + 1;          // 1 .. n/2
@@ -310,9 +324,9 @@ __global__ void __launch_bounds__(DCT_THREADS) k_dct_strided(const double *__res
             if (lane < (1 << lrw)) {                               // k = 0: V[0] is its own partner
                 double2 *r = rows + lane * rowStride;
                 i64 La = L0 + 2 * ((wave << lrw) + lane);
-                if (La + 1 >= map.nLines) La = (map.nLines >= 2) ? map.nLines - 2 : 0;
+                if (La >= map.nLines) La = map.nLines - 1;
                 const i64 Ga = sa.line0 + La;
-                const i64 Gb = (Ga + 1 < sa.nplane) ? Ga + 1 : Ga;
+                const i64 Gb = (La + 1 < map.nLines && Ga + 1 < sa.nplane) ? Ga + 1 : Ga;
                 double la = (sa.cy[Ga % sa.ny] + sa.cx[Ga / sa.ny]) + sa.ct[0];
                 double lb2 = (sa.cy[Gb % sa.ny] + sa.cx[Gb / sa.ny]) + sa.ct[0];
                 if (la == 0.0) la = 1.0;
@@ -988,7 +1002,7 @@ static int launch_strided(int mode, const Pow2Plan *p, const double *src, double
     const int lp = tile_log2_rows(n, map.nLines, mode == 2 ? 2 : 1);
     const size_t lds = ((size_t)1 << lp) * row_stride(n) * sizeof(double2);
     if (lds > DCT_LDS_MAX) {
-        set_error("power-of-two DCT length %d does not fit the LDS (largest supported: 8192)", n);
+        set_error("power-of-two DCT length %d does not fit the LDS in one pass (largest supported there: 8192)", n);
         return DOTSOCP_EINVAL;
     }
     const i64 linesPerBlock = (i64)2 << lp;
@@ -1091,6 +1105,7 @@ static int launch_strided(int mode, const Pow2Plan *p, const double *src, double
 }
 
 int pow2_launch_strided(const Pow2Plan *p, const double *src, double *dst, const LineMap &map, int inverse, hipStream_t st) {
+    if (p->lng && p->n >= dct_long_min(1)) return long_launch(p->lng, src, dst, map, false, inverse, st);
     return launch_strided(inverse ? 1 : 0, p, src, dst, map, SolveArgs{}, st);
 }
 
@@ -1112,6 +1127,7 @@ int pow2_launch_tsolve(const Pow2Plan *p, const double *src, double *dst, i64 ny
 }
 
 int pow2_launch_axis0(const Pow2Plan *p, const double *src, double *dst, const LineMap &map, int inverse, hipStream_t st) {
+    if (p->lng && p->n >= dct_long_min(0)) return long_launch(p->lng, src, dst, map, true, inverse, st);
     // each wave owns 2^lrw rows; a workgroup of 4 waves stages 4 * 2^lrw rows
     const i64 n = p->n;
     const int lg = p->lg;

@@ -328,6 +328,11 @@ enum { DCT_ALG_NONE = 0, DCT_ALG_FFT = 1, DCT_ALG_PFA = 2, DCT_ALG_RADER = 3, DC
 // Pure host arithmetic (no HIP call); honours DOTSOCP_PFA, DOTSOCP_CDFT and DOTSOCP_CDFT_MIN, each read once per process.
 int dct_choose_algorithm(i64 n);
 struct DctPlan;   // the choice for one axis length and the chosen family's tables
+// 0 no transform (n <= 1), 1 one pass with the line in LDS (or one of the other families), 2 the two-level transform of
+// dct_long.hip, negative: unsupported (a power of two above 2^20).  dct_length_check: 0, or DOTSOCP_EINVAL with the limit
+// in the error text -- asked before plans and contexts are made, so that nothing fails at a launch.
+int dct_levels(i64 n, int axis);
+int dct_length_check(i64 n);
 DctPlan *dct_plan_create(i64 n);
 void dct_plan_destroy(DctPlan *p);
 // Orthonormal DCT-II (inverse=0) / DCT-III (inverse=1) along one axis of an [n0][n1][n2] array

@@ -168,6 +168,7 @@ int Solver::init(const dotsocp_problem *p, int dev, int nslabs, bool multi_dev) 
     nt = p->nt;
     DS_ARG(ny >= 1 && nx >= 1, "grid too small");
     DS_ARG(nslabs >= 1 && nslabs <= nt / 2, "nslabs must be in [1, nt/2]");
+    DS_CHECK(dct_length_check(ny)); DS_CHECK(dct_length_check(nx)); DS_CHECK(dct_length_check(nt));
     if (const char *e = getenv("DOTSOCP_FUSED")) fused = (atoi(e) != 0);
     if (nslabs > 1 && !fused) {
         set_error("time slabs need the fused dataflow (unset DOTSOCP_FUSED=0)");

@@ -85,12 +85,15 @@ int dotsocp_bfd_conj1d(double *q, const double *z, dotsocp_i64 nt, dotsocp_i64 n
  * -- socp/dot2d/utils/oper_poisson3dim.m:4, initialize_FFTkernel.m:6-15,
  *    mirt_dctn.m / mirt_idctn.m (orthonormal DCT-II / DCT-III along every axis);
  *    call site solver_socp_inPALM.m:96,194.   For a 1-D problem pass ny = nx1d, nx = 1
- *    (socp/dot1d/utils/oper_poisson.m:4).  rhs and res hold ny*nx*nt doubles. */
+ *    (socp/dot1d/utils/oper_poisson.m:4).  rhs and res hold ny*nx*nt doubles.
+ *    Lengths: any; a power of two may have up to 2^20 points on every axis (dotsocp_dct_levels), a longer one is
+ *    refused with DOTSOCP_EINVAL before anything is launched. */
 int dotsocp_oper_poisson(double *res, const double *rhs, dotsocp_i64 ny, dotsocp_i64 nx,
                          dotsocp_i64 nt, double kernelScale);
 
 /* a <- dctn(a) (inverse = 0) or idctn(a) (inverse = 1) of an ny x nx x nt array
- * -- socp/dot2d/utils/mirt_dctn.m:64-141, mirt_idctn.m:59-128. */
+ * -- socp/dot2d/utils/mirt_dctn.m:64-141, mirt_idctn.m:59-128.  Power-of-two lengths up to 2^20 on every axis: in
+ *    one pass while the line fits the LDS, by a two-level FFT beyond (dotsocp_dct_levels); longer: DOTSOCP_EINVAL. */
 int dotsocp_dctn(double *a, dotsocp_i64 ny, dotsocp_i64 nx, dotsocp_i64 nt, int inverse);
 
 /* Same operators on DEVICE pointers (no PCIe traffic), enqueued on `stream`
@@ -213,6 +216,14 @@ dotsocp_i64 dotsocp_field_len(const dotsocp_problem *prob, int field);
  * DOTSOCP_PFA, DOTSOCP_CDFT, DOTSOCP_CDFT_MIN): 0 none (n <= 1), 1 power-of-two FFT, 2 prime-factor FFT, 3 Rader (257),
  * 4 Bluestein (other lengths up to 1024), 5 dense DCT-matrix product. */
 int dotsocp_dct_algorithm(dotsocp_i64 n);
+
+/* How many passes through memory the transform of an axis of length n takes along `axis` (0: y, the contiguous axis;
+ * 1: x; 2: t).  Pure host arithmetic, no device.  0: no transform (n <= 1); 1: one pass, the whole line in LDS (or one
+ * of the other transform families); 2: the two-level FFT for power-of-two lines that do not fit the LDS -- from 4096
+ * along y and 16384 along x / t, or from DOTSOCP_DCT_LONG_MIN (never below 256) along every axis, up to 2^20;
+ * negative: unsupported (a power of two above 2^20: dotsocp_dctn, dotsocp_oper_poisson and dotsocp_create refuse it
+ * with DOTSOCP_EINVAL before anything is launched).  dotsocp_dct_algorithm answers 1 (FFT) for every power of two. */
+int dotsocp_dct_levels(dotsocp_i64 n, int axis);
 
 /* May the single slab solve the t axis of its Poisson step as tridiagonal systems (tri.hip: k_tsolve_single / k_tsolve_pipe)
  * on an ny x nx x nt grid (1-D: ny = nx1d, nx = 1)?  1 if the powers rho^t of the mode with the largest

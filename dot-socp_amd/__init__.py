@@ -7,12 +7,14 @@ no CPU fallback; see include/dotsocp.h for the C ABI and INTEGRATION.md for the 
 """
 from . import capi  # noqa: F401
 from .capi import dct_algorithm, dct_levels  # noqa: F401
-from .examples import (ensure_barrier_validity, gene_barrier_of_circle_pillar, gene_barrier_of_love_heart,  # noqa: F401
+from .examples import (SpaceWeight, ensure_barrier_validity, gene_barrier_of_circle_pillar,  # noqa: F401
+                       gene_barrier_of_love_heart, gene_space_weight_circle, gene_space_weight_circleInv,
                        gene_weight_circle, gene_weight_circleInv, get_example_1d, get_example_2d,
-                       get_weight_by_barrier)
+                       get_space_weight_by_barrier, get_weight_by_barrier)
 from .mexops import (mexBFd, mexBFd1d, mexBFdConj, mexBFdConj1d, mexProjSoc, mirt_dctn, mirt_idctn,  # noqa: F401
                      oper_poisson, oper_poisson3dim)
 from .model import (InitialScaling, ModelHandle, VarHandle, check_massConservation, initialize,  # noqa: F401
                     initialize_slab, recover_q, recover_RhoE, recoverOrgVar)
+from .weights import WeightPyramid  # noqa: F401
 from .solvers import (InPALMContext, poisson_on_slabs, solver_dotsocp1d, solver_dotsocp2d, solver_socp_accADMM,  # noqa: F401
                       solver_socp_inPALM, solver_socp_PALM, solver_wdotsocp2d, solver_wsocp_accADMM, solver_wsocp_inPALM)

@@ -94,6 +94,15 @@ SYMBOLS = {
     "dotsocp_canary_check": (ctypes.c_int, []),
     "dotsocp_poisson_phi": (ctypes.c_int, [vp]),
     "dotsocp_synchronize": (ctypes.c_int, [vp]),
+    "dotsocp_weights_create": (vp, [ctypes.c_int, i64, i64, i64, ctypes.c_int]),
+    "dotsocp_weights_destroy": (None, [vp]),
+    "dotsocp_weights_len": (i64, [i64, i64, i64, ctypes.c_int, ctypes.c_int]),
+    "dotsocp_weights_set": (ctypes.c_int, [vp, vp]),
+    "dotsocp_weights_set_space": (ctypes.c_int, [vp, vp, vp]),
+    "dotsocp_weights_restrict": (ctypes.c_int, [vp, ctypes.c_int]),
+    "dotsocp_weights_log10_mean": (ctypes.c_int, [vp, ctypes.c_int, ctypes.POINTER(dbl)]),
+    "dotsocp_weights_download": (ctypes.c_int, [vp, ctypes.c_int, vp]),
+    "dotsocp_upload_weight_from": (ctypes.c_int, [vp, vp, ctypes.c_int]),
 }
 
 _lib = None

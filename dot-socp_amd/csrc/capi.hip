@@ -4,6 +4,7 @@
 
 #include "comm.h"
 #include "solver.h"
+#include "weights.h"
 
 using namespace dotsocp;
 
@@ -14,6 +15,10 @@ int dotsocp_slab_range_impl(i64 nt, int world, int rank, i64 *t0, i64 *t1);
 
 struct dotsocp_ctx {
     Solver s;
+};
+
+struct dotsocp_weights {
+    Weights w;
 };
 
 static int require_device() {
@@ -390,6 +395,46 @@ int dotsocp_canary_check(void) {
     const int bad = canary_check(&rep);
     if (bad) set_error("canary: %d device buffer(s) written out of bounds: %s", bad, rep.c_str());
     return bad;
+}
+
+// ------------------------------------------------------------------ weight pyramid (weights.hip)
+#define WEIGHTS_OR_FAIL()                                  \
+    do {                                                   \
+        if (!w) { set_error("weight pyramid is NULL"); return DOTSOCP_EINVAL; } \
+        (void)hipGetLastError();                           \
+    } while (0)
+
+dotsocp_weights *dotsocp_weights_create(int device, dotsocp_i64 ny, dotsocp_i64 nx, dotsocp_i64 nt, int levels) {
+    dotsocp_weights *w = new (std::nothrow) dotsocp_weights();
+    if (!w) { set_error("out of host memory"); return nullptr; }
+    if (w->w.init(device, ny, nx, nt, levels) != 0) {
+        delete w;
+        return nullptr;
+    }
+    return w;
+}
+
+void dotsocp_weights_destroy(dotsocp_weights *w) { delete w; }
+
+dotsocp_i64 dotsocp_weights_len(dotsocp_i64 ny, dotsocp_i64 nx, dotsocp_i64 nt, int levels, int level) {
+    return weights_level_len(ny, nx, nt, levels, level);
+}
+
+int dotsocp_weights_set(dotsocp_weights *w, const double *weight) { WEIGHTS_OR_FAIL(); return w->w.set(weight); }
+int dotsocp_weights_set_space(dotsocp_weights *w, const double *weightX, const double *weightY) {
+    WEIGHTS_OR_FAIL();
+    return w->w.set_space(weightX, weightY);
+}
+int dotsocp_weights_restrict(dotsocp_weights *w, int log_mean) { WEIGHTS_OR_FAIL(); return w->w.restrict_all(log_mean); }
+int dotsocp_weights_log10_mean(dotsocp_weights *w, int level, double *mean) { WEIGHTS_OR_FAIL(); return w->w.log10_mean(level, mean); }
+int dotsocp_weights_download(dotsocp_weights *w, int level, double *host) { WEIGHTS_OR_FAIL(); return w->w.download(level, host); }
+
+int dotsocp_upload_weight_from(dotsocp_ctx *ctx, dotsocp_weights *w, int level) {
+    CTX_OR_FAIL();
+    WEIGHTS_OR_FAIL();
+    const Weights::Level *L = nullptr;
+    DS_CHECK(w->w.level_for_upload(level, &L));
+    return ctx->s.upload_weight_from(L->w, w->w.device, L->ny, L->nx, L->nt);
 }
 
 int dotsocp_poisson_phi(dotsocp_ctx *ctx) { CTX_OR_FAIL(); return ctx->s.poisson_phi(); }

@@ -251,11 +251,17 @@ struct Solver {
 
     // ================ host <-> device fields, driver steps on the device: solver_io.hip ================
     i64 field_len(int field) const;
-    // rows of `rowlen` doubles between a device array with rows `pitch` apart and a host array in the reference layout
-    int copy_rows(double *dev, double *host, i64 rowlen, i64 pitch, i64 nrows, bool up, hipStream_t st);
+    // rows of `rowlen` doubles between a device array with rows `pitch` apart and an array in the reference layout: a host
+    // array (dir = ROWS_DOWN / ROWS_UP; `false` / `true` of the callers), or one on device `src_dev` that is read
+    // (ROWS_FROM_DEV; a peer copy where that is not the current device)
+    enum { ROWS_DOWN = 0, ROWS_UP = 1, ROWS_FROM_DEV = 2 };
+    int copy_rows(double *dev, double *host, i64 rowlen, i64 pitch, i64 nrows, int dir, hipStream_t st, int src_dev = -1);
     int upload(int field, const double *host);
     int upload_layers(int field, const double *host, i64 t0, i64 n);
     int download(int field, double *host);
+    // model.weight <- `src`: the weight of this grid in the reference layout on device `src_dev` (a level of a weight
+    // pyramid, weights.h); every slab takes its layers.  Replaces upload(DOTSOCP_F_WEIGHT, ...).
+    int upload_weight_from(const double *src, int src_dev, i64 src_ny, i64 src_nx, i64 src_nt);
     // c is zero off its two end layers (model.c of initialize.m:42-50): the q-step, k_rhs and the sigma fix skip the rest
     bool c_ends_on = true;       // DOTSOCP_C_ENDS=0: load all of c
     int detect_c_ends();

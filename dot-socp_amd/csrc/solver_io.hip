@@ -177,22 +177,61 @@ i64 Solver::field_len(int field) const {
     }
 }
 
-// rows of `rowlen` doubles: device rows `pitch` apart, host rows contiguous (reference layout)
-int Solver::copy_rows(double *dev, double *host, i64 rowlen, i64 pitch, i64 nrows, bool up, hipStream_t st) {
+// rows of `rowlen` doubles: device rows `pitch` apart, the other side contiguous (reference layout) -- host rows, or with
+// ROWS_FROM_DEV rows on device `src_dev` that are read
+int Solver::copy_rows(double *dev, double *host, i64 rowlen, i64 pitch, i64 nrows, int dir, hipStream_t st, int src_dev) {
     if (rowlen <= 0 || nrows <= 0) return 0;
+    const bool up = dir != ROWS_DOWN;
+    hipMemcpyKind kind = dir == ROWS_UP ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost;
+    if (dir == ROWS_FROM_DEV) {
+        kind = hipMemcpyDeviceToDevice;
+        int here = -1;
+        DS_HIP(hipGetDevice(&here));
+        if (src_dev >= 0 && src_dev != here) {
+            // between devices only whole blocks travel: copy_field stages the layers of a pitched slab on the slab's own
+            // device first, so a pitched request never arrives here
+            DS_ARG(pitch == rowlen, "pitched rows cannot be copied between devices");
+            DS_HIP(ds_memcpy_peer_async(dev, here, host, src_dev, sizeof(double) * rowlen * nrows, st));
+            return 0;
+        }
+    }
     if (pitch == rowlen) {
-        if (up) DS_HIP(ds_memcpy_async(dev, host, sizeof(double) * rowlen * nrows, hipMemcpyHostToDevice, st));
-        else DS_HIP(ds_memcpy_async(host, dev, sizeof(double) * rowlen * nrows, hipMemcpyDeviceToHost, st));
+        if (up) DS_HIP(ds_memcpy_async(dev, host, sizeof(double) * rowlen * nrows, kind, st));
+        else DS_HIP(ds_memcpy_async(host, dev, sizeof(double) * rowlen * nrows, kind, st));
         return 0;
     }
     if (up) DS_HIP(ds_memcpy2d_async(dev, sizeof(double) * pitch, host, sizeof(double) * rowlen, sizeof(double) * rowlen,
-                                    (size_t)nrows, hipMemcpyHostToDevice, st));
+                                    (size_t)nrows, kind, st));
     else DS_HIP(ds_memcpy2d_async(host, sizeof(double) * rowlen, dev, sizeof(double) * pitch, sizeof(double) * rowlen,
-                                 (size_t)nrows, hipMemcpyDeviceToHost, st));
+                                 (size_t)nrows, kind, st));
     return 0;
 }
 
-static int copy_field(Solver &S, int field, double *host, bool up) {
+// DOTSOCP_WEIGHT_STAGE=1: every slab stages its layers of a device source as if the source lived on another device
+static bool weight_stage_forced() {
+    const char *e = getenv("DOTSOCP_WEIGHT_STAGE");
+    return e && atoi(e) != 0;
+}
+
+// Staging buffers of copy_field: released once every stream of the context is idle, on the error paths too
+struct StagedBuffers {
+    Solver &S;
+    std::vector<double *> bufs;
+    explicit StagedBuffers(Solver &s) : S(s) {}
+    ~StagedBuffers() {
+        if (bufs.empty()) return;
+        S.cur_dev = -1;
+        (void)S.sync_all();
+        for (double *b : bufs) dfree(b);
+    }
+};
+
+// `host`: the global field in the reference layout -- on the host (dir = ROWS_DOWN / ROWS_UP), or on device `src_dev`
+// (ROWS_FROM_DEV: read from there).  A slab with pitched rows on ANOTHER device than the source cannot take its rows one
+// by one (copy_rows): its three contiguous layer ranges of [q0; bx; by] travel as peer copies into a staging buffer on
+// the slab's device and the rows are spread from there.
+static int copy_field(Solver &S, int field, double *host, int up, int src_dev = -1) {
+    StagedBuffers staged(S);
     const i64 ny = S.ny, nx = S.nx;
     i64 ntn = S.nt, ntc = S.nt - 1;
     if (S.remote()) { ntn = S.slabs[0].g.ntl; ntc = S.slabs[0].g.ncl; }
@@ -206,15 +245,30 @@ static int copy_field(Solver &S, int field, double *host, bool up) {
         hipStream_t cur = s.st;
         const Grid &g = s.g;
         const i64 t0 = S.remote() ? 0 : g.t0;
-        auto nodes = [&](double *dev, double *h, i64 layers) { return S.copy_rows(dev, h, ny, g.py, nx * layers, up, cur); };
+        auto nodes = [&](double *dev, double *h, i64 layers) { return S.copy_rows(dev, h, ny, g.py, nx * layers, up, cur, src_dev); };
         switch (field) {
             case DOTSOCP_F_PHI: DS_CHECK(nodes(s.phi, host + hplane * t0, g.ntl)); break;
             case DOTSOCP_F_C: DS_CHECK(nodes(s.c, host + hplane * t0, g.ntl)); break;
             case DOTSOCP_F_Q: case DOTSOCP_F_ALPHA: case DOTSOCP_F_WEIGHT: {
                 double *d = field == DOTSOCP_F_Q ? s.q : (field == DOTSOCP_F_ALPHA ? s.alpha : s.weight);
-                DS_CHECK(nodes(d, host + hplane * t0, g.ncl));
-                DS_CHECK(S.copy_rows(d + g.offBx, host + bxG + hbx * t0, ny, g.py, (nx - 1) * g.ntl, up, cur));
-                DS_CHECK(S.copy_rows(d + g.offBy, host + byG + hby * t0, ny - 1, g.pyb, nx * g.ntl, up, cur));
+                double *part[3] = {host + hplane * t0, host + bxG + hbx * t0, host + byG + hby * t0};
+                const i64 count[3] = {hplane * g.ncl, hbx * g.ntl, hby * g.ntl};
+                int from = src_dev;
+                if (up == Solver::ROWS_FROM_DEV && ((s.dev != src_dev && g.py > ny) || weight_stage_forced())) {
+                    double *buf = nullptr;
+                    DS_CHECK(dmalloc(&buf, count[0] + count[1] + count[2]));
+                    staged.bufs.push_back(buf);
+                    for (int k = 0; k < 3; ++k) {
+                        if (count[k] > 0)
+                            DS_HIP(ds_memcpy_peer_async(buf, s.dev, part[k], src_dev, sizeof(double) * (size_t)count[k], cur));
+                        part[k] = buf;
+                        buf += count[k];
+                    }
+                    from = s.dev;
+                }
+                DS_CHECK(S.copy_rows(d, part[0], ny, g.py, nx * g.ncl, up, cur, from));
+                DS_CHECK(S.copy_rows(d + g.offBx, part[1], ny, g.py, (nx - 1) * g.ntl, up, cur, from));
+                DS_CHECK(S.copy_rows(d + g.offBy, part[2], ny - 1, g.pyb, nx * g.ntl, up, cur, from));
                 break;
             }
             case DOTSOCP_F_Z: case DOTSOCP_F_BETA: {
@@ -242,6 +296,23 @@ int Solver::upload(int field, const double *host) {
     DS_CHECK(use_dev(device));
     DS_CHECK(ensure_alloc());
     return copy_field(*this, field, const_cast<double *>(host), true);
+}
+
+// model.weight from a device array in the reference layout (a level of a weight pyramid): the row copies of upload(),
+// device to device -- rows land py / pyb apart, the pad entries keep the ones alloc_slabs gave them, every slab takes its
+// layers (peer copies where the array lives on another device; copy_field stages those of a pitched slab).  The copies
+// between DIFFERENT devices have never run on hardware (one-GPU boxes); DOTSOCP_WEIGHT_STAGE=1 runs the staged form on one.
+int Solver::upload_weight_from(const double *src, int src_dev, i64 src_ny, i64 src_nx, i64 src_nt) {
+    DS_ARG(src != nullptr, "weight source is NULL");
+    DS_ARG(prob.weighted, "weight handed to an unweighted problem");
+    DS_ARG(prob.dim == 2, "the weight pyramid serves 2-D problems");
+    DS_ARG(!remote(), "contexts with an RCCL communicator take their weight from the host");
+    DS_ARG(src_ny == ny && src_nx == nx && src_nt == nt, "the pyramid level is not this context's grid");
+    if (begun) { set_error("upload() after begin()"); return DOTSOCP_ESTATE; }
+    cur_dev = -1;
+    DS_CHECK(use_dev(device));
+    DS_CHECK(ensure_alloc());
+    return copy_field(*this, DOTSOCP_F_WEIGHT, const_cast<double *>(src), ROWS_FROM_DEV, src_dev);
 }
 
 // model.c of initialize.m:42-50 is zero except on its first and last time layer, and every operation of the loop on c

@@ -191,9 +191,31 @@ def gene_barrier_of_love_heart():
     return lambda x, y: (heart(x, y + 0.05, 2.5) > 0) | (heart(x, y, 15.0) <= 0)
 
 
-def _gene_weight_radial(nt, nx, ny, fun):
+class SpaceWeight:
+    """A weight that does not depend on t: weightX (ny, nx-1) on the x edges and weightY (ny-1, nx) on the y edges, each
+    repeated over the nt time nodes, and 1 on every time edge (get_weight_by_barrier.m:20-33, gene_weight_circle.m:24-28).
+    The weighted driver takes it in place of the Nq array (opts["weight"]) and builds the levels' weights on the device
+    from the two 2-D arrays; expand(nt) is that Nq host array."""
+
+    def __init__(self, weightX, weightY):
+        self.weightX = np.asfortranarray(weightX, dtype=np.float64)
+        self.weightY = np.asfortranarray(weightY, dtype=np.float64)
+        if self.weightX.ndim != 2 or self.weightY.ndim != 2 or self.weightX.shape[0] < 2 or self.weightY.shape[1] < 2 \
+                or self.weightY.shape != (self.weightX.shape[0] - 1, self.weightX.shape[1] + 1):
+            raise ValueError("SpaceWeight needs weightX of shape (ny, nx-1) and weightY of shape (ny-1, nx)")
+        self.ny, self.nx = self.weightX.shape[0], self.weightY.shape[1]
+
+    def expand(self, nt):
+        """model.weight = [weightT; weightX over t; weightY over t] for nt time nodes"""
+        nt = int(nt)
+        wX = np.repeat(self.weightX[:, :, None], nt, axis=2).ravel(order="F")
+        wY = np.repeat(self.weightY[:, :, None], nt, axis=2).ravel(order="F")
+        return np.concatenate([np.ones(self.ny * self.nx * (nt - 1)), wX, wY])
+
+
+def _gene_space_weight_radial(nx, ny, fun):
     """examples/wdot2d/gene_weight_circle.m:8-28 / gene_weight_circleInv.m: a radial profile around (0.5, 0.5) on
-    the staggered edges, both edge families normalised with ny (nx - 1) as in the files, weight 1 on the time edges."""
+    the staggered edges, both edge families normalised with ny (nx - 1) as in the files."""
     hx, hy = 1.0 / (nx - 1), 1.0 / (ny - 1)
     xStag, xCent = np.linspace(0.5 * hx, 1 - 0.5 * hx, nx - 1), np.linspace(0, 1, nx)
     yStag, yCent = np.linspace(0.5 * hy, 1 - 0.5 * hy, ny - 1), np.linspace(0, 1, ny)
@@ -203,23 +225,32 @@ def _gene_weight_radial(nt, nx, ny, fun):
     xx, yy = np.meshgrid(xCent, yStag)
     wY = fun(np.sqrt((xx - 0.5) ** 2 + (yy - 0.5) ** 2))
     wY = wY * (ny * (nx - 1) / wY.sum())
-    return np.concatenate([np.ones(ny * nx * (nt - 1)), np.repeat(wX[:, :, None], nt, axis=2).ravel(order="F"),
-                           np.repeat(wY[:, :, None], nt, axis=2).ravel(order="F")])
+    return SpaceWeight(wX, wY)
+
+
+def gene_space_weight_circle(nx, ny):
+    """The two 2-D arrays of gene_weight_circle (weight = distance from the centre) as a SpaceWeight"""
+    return _gene_space_weight_radial(nx, ny, lambda r: r)
+
+
+def gene_space_weight_circleInv(nx, ny):
+    """The two 2-D arrays of gene_weight_circleInv (weight = 1 / (0.1 + distance from the centre)) as a SpaceWeight"""
+    return _gene_space_weight_radial(nx, ny, lambda r: 1.0 / (0.1 + r))
 
 
 def gene_weight_circle(nt, nx, ny):
-    """examples/wdot2d/gene_weight_circle.m: weight = distance from the centre"""
-    return _gene_weight_radial(nt, nx, ny, lambda r: r)
+    """examples/wdot2d/gene_weight_circle.m: weight = distance from the centre, weight 1 on the time edges"""
+    return gene_space_weight_circle(nx, ny).expand(nt)
 
 
 def gene_weight_circleInv(nt, nx, ny):
     """examples/wdot2d/gene_weight_circleInv.m: weight = 1 / (0.1 + distance from the centre)"""
-    return _gene_weight_radial(nt, nx, ny, lambda r: 1.0 / (0.1 + r))
+    return gene_space_weight_circleInv(nx, ny).expand(nt)
 
 
-def get_weight_by_barrier(nx, ny, nt, barrier, barrierWeight=1e6):
-    """examples/wdot2d/get_weight_by_barrier.m:8-33.  The MATLAB code evaluates
-    barrier(xx', yy') on transposed meshgrids and applies mask' -- i.e. weightX(iy, ix)
+def get_space_weight_by_barrier(nx, ny, barrier, barrierWeight=1e6):
+    """examples/wdot2d/get_weight_by_barrier.m:8-30 without the repetition over t: the SpaceWeight of a barrier.
+    The MATLAB code evaluates barrier(xx', yy') on transposed meshgrids and applies mask' -- i.e. weightX(iy, ix)
     is set where barrier(xStag(ix), yCent(iy)) holds."""
     hx, hy = 1.0 / (nx - 1), 1.0 / (ny - 1)
     xStag = np.linspace(0.5 * hx, 1 - 0.5 * hx, nx - 1)
@@ -232,10 +263,13 @@ def get_weight_by_barrier(nx, ny, nt, barrier, barrierWeight=1e6):
     xx, yy = np.meshgrid(xCent, yStag)          # (ny-1, nx)
     weightY = np.ones((ny - 1, nx))
     weightY[barrier(xx, yy) > 0] = barrierWeight
-    weightT = np.ones(ny * nx * (nt - 1))
-    wX = np.repeat(weightX[:, :, None], nt, axis=2).ravel(order="F")
-    wY = np.repeat(weightY[:, :, None], nt, axis=2).ravel(order="F")
-    return np.concatenate([weightT, wX, wY])
+    return SpaceWeight(weightX, weightY)
+
+
+def get_weight_by_barrier(nx, ny, nt, barrier, barrierWeight=1e6):
+    """examples/wdot2d/get_weight_by_barrier.m:8-33: get_space_weight_by_barrier repeated over the nt time nodes,
+    weight 1 on the time edges."""
+    return get_space_weight_by_barrier(nx, ny, barrier, barrierWeight).expand(nt)
 
 
 def ensure_barrier_validity(rho0, rho1, barrier):

@@ -121,7 +121,8 @@ def initialize_slab(rho0, rho1, nt, t0, t1):
 
 def InitialScaling(var, model, scalingYes, lastLevelKKT=None, dim=2, weighted=False):
     """socp/dot2d/solver_dotsocp2d.m:304-365; 1-D: solver_dotsocp1d.m:263-300 (hMean = h^(1/2));
-    weighted: solver_wdotsocp2d.m:297-343 (`adjust`, E2 safeguard 4)."""
+    weighted: solver_wdotsocp2d.m:297-343 (`adjust`, E2 safeguard 4); a model without `weight` carries
+    `weight_log10_mean`, taken on the device (weights.py: WeightPyramid.log10_mean)."""
     h = 1.0 / (model.n_global if hasattr(model, "n_global") else var.phi.size)
     ends = getattr(model, "_c_ends", None)      # initialize(lazy_zeros=True): only c's two end layers are non-zero
     hMean = h ** (1.0 / 3.0) if dim == 2 else h ** 0.5
@@ -147,7 +148,10 @@ def InitialScaling(var, model, scalingYes, lastLevelKKT=None, dim=2, weighted=Fa
     if scalingYes:
         norm_c = _norm_c() * np.sqrt(model.nt)
         norm_d = np.sqrt(2.0)
-        adjust = 10.0 ** np.mean(np.log10(model.weight + 1e-10)) if weighted else 1.0
+        if weighted and getattr(model, "weight", None) is None:
+            adjust = 10.0 ** model.weight_log10_mean      # the level's mean(log10(weight + 1e-10)) from the weight pyramid
+        else:
+            adjust = 10.0 ** np.mean(np.log10(model.weight + 1e-10)) if weighted else 1.0
         D = np.sqrt(2.0) * np.sqrt(hMean) * adjust
         E = D / Escale2
         cScale = max(1.0, norm_c * np.sqrt(hMean) / adjust)

@@ -16,8 +16,10 @@ import time
 import numpy as np
 
 from . import capi
+from .examples import SpaceWeight
 from .model import (InitialScaling, ModelHandle, VarHandle, check_massConservation, initialize,
                     recover_q, recover_RhoE, recoverOrgVar)
+from .weights import WeightPyramid
 
 TIME_NAMES = ['Step_1_1_FFT', 'Step_1_2_ProjSOC', 'Step_2_Q_Step', 'Step_3_Multiplier', 'KKT',
               'Total_Time', 'Iters']
@@ -46,7 +48,7 @@ class InPALMContext:
     """Stateful handle on one device-resident loop (create -> upload -> begin -> run* -> finish)."""
 
     def __init__(self, var, opts, model, weighted=False, device=0, nslabs=1, profiling=False, rccl=None,
-                 method="inPALM", warm_from=None, ngpu=None, z_unread=False):
+                 method="inPALM", warm_from=None, ngpu=None, z_unread=False, weight_from=None):
         """rccl = (unique_id_bytes, rank, world): one process per GPU, this process owns time slab
         `rank`; var / model then hold the LOCAL slab of every field (model.nt stays the global nt).
         method: which loop file of the reference runs ("inPALM"/"ALG2" by opts.tau, "PALM", "acc-ADMM").
@@ -56,7 +58,9 @@ class InPALMContext:
         (device + r) mod #devices; nslabs (diagnostic) keeps all slabs on `device`.
         z_unread: the caller will run at least one iteration of the inPALM / ALG2 loop, which overwrites z before its first
         use (solver_socp_inPALM.m:199; the rescale block, the only other reader, needs it >= 10): var.z is not uploaded --
-        10 of the 27 N doubles of the state (tests/test_gpu_solver.py::test_iterations_from_a_random_state)."""
+        10 of the 27 N doubles of the state (tests/test_gpu_solver.py::test_iterations_from_a_random_state).
+        weight_from = (WeightPyramid, level): model.weight is that level of the pyramid, copied device to device
+        (dotsocp_upload_weight_from); model.weight itself is not read."""
         L = capi.lib()
         self.method = method
         one_d = not hasattr(model, "ny")
@@ -94,7 +98,9 @@ class InPALMContext:
                     capi.check(L.dotsocp_upload_layers(self._ctx, capi.F_C, capi.fptr(np.ascontiguousarray(part)), t, 1))
             else:
                 self.upload(capi.F_C, model.c)
-            if weighted:
+            if weighted and weight_from is not None:
+                weight_from[0].upload_to(self, weight_from[1])
+            elif weighted:
                 self.upload(capi.F_WEIGHT, model.weight)
             if warm_from is not None:
                 capi.check(L.dotsocp_jump_next_level(warm_from._ctx, self._ctx))
@@ -274,18 +280,42 @@ def _driver_opts(opts, method, weighted, dim=2):
     return o
 
 
-def _solve_levels(rho0, rho1, nt, levelN, opts, method, dim, weighted, device, barrier=None, transfer="device"):
+def _weights_mode(weight, weights, transfer, weighted=True):
+    """Where the levels' weights of a weighted multilevel solve are made: the `weights` argument of solver_wdotsocp2d,
+    or its default -- "device" for a SpaceWeight whose state stays on the device, else "host" (today's path)."""
+    if weights is None:
+        weights = "device" if isinstance(weight, SpaceWeight) and transfer == "device" else "host"
+    if weights not in ("device", "host"):
+        raise ValueError("weights must be 'device' or 'host'")
+    if weights == "device" and (transfer != "device" or not weighted):
+        raise ValueError("weights='device' needs a weighted driver and transfer='device'")
+    return weights
+
+
+def _solve_levels(rho0, rho1, nt, levelN, opts, method, dim, weighted, device, barrier=None, transfer="device",
+                  weights=None):
     """The level loop of solver_dotsocp2d.m:154-250 (dot1d / wdot2d twins): restrict the data to
     levelN grids, solve coarse to fine with warm starts; every solve runs on the device.
     transfer = "device": the state never leaves the GPU -- jump_nextLevel and the output recovery run there
     (dotsocp_jump_next_level / dotsocp_recover_outputs); "host": download, numpy twins of jump_nextLevel.m /
-    recover_RhoE.m / recover_q.m, upload (the two agree to rounding, tests/test_multilevel.py)."""
+    recover_RhoE.m / recover_q.m, upload (the two agree to rounding, tests/test_multilevel.py).
+    weights (weighted drivers) = "host": every level's weight is restricted with numpy (multilevel.downSample_q /
+    downSample_barrier) and uploaded; "device": one WeightPyramid holds the weights of all levels -- the finest is uploaded
+    once (an Nq array, or the two 2-D arrays of a SpaceWeight), the others are restricted on the GPU, every level's
+    context takes its weight device to device and InitialScaling its log10 mean from the pyramid; needs
+    transfer="device".  None: "device" for a SpaceWeight with transfer="device", else "host" (a SpaceWeight is then
+    expanded on the host)."""
     from . import multilevel as ML
     from .examples import ensure_barrier_validity
     if not (isinstance(levelN, (int, np.integer)) and levelN >= 1):
         raise ValueError("Invalid input at position 4 (Number of levels in multilevel strategy)")
     if transfer not in ("device", "host"):
         raise ValueError("transfer must be 'device' or 'host'")
+    wopt = _get(opts, "weight") if weighted else None
+    weights = _weights_mode(wopt, weights, transfer, weighted)
+    wdev = weights == "device"
+    if isinstance(wopt, SpaceWeight) and not wdev:
+        wopt = wopt.expand(nt)
     o = _driver_opts(opts, method, weighted, dim)
     t_all = time.perf_counter()
     tolFactor = -1.0 if o["tol"] > 0.99e-3 else -0.5                     # :124-128
@@ -294,8 +324,8 @@ def _solve_levels(rho0, rho1, nt, levelN, opts, method, dim, weighted, device, b
     rho0s, rho1s, nts, tols, ws = [None] * L, [None] * L, [None] * L, [None] * L, [None] * L
     rho0s[-1], rho1s[-1] = np.asarray(rho0, dtype=np.float64), np.asarray(rho1, dtype=np.float64)
     nts[-1], tols[-1] = int(nt), o["tol"]
-    if weighted:
-        ws[-1] = np.asarray(_get(opts, "weight"), dtype=np.float64)
+    if weighted and not wdev:
+        ws[-1] = np.asarray(wopt, dtype=np.float64)
     for lv in range(L - 2, -1, -1):                                      # :166-178
         if (nts[lv + 1] - 1) % 2 or any((n - 1) % 2 for n in rho0s[lv + 1].shape):
             raise ValueError("multilevel needs 2^k*m+1 grid sizes on every level (solver_dotsocp2d.m:167)")
@@ -306,9 +336,11 @@ def _solve_levels(rho0, rho1, nt, levelN, opts, method, dim, weighted, device, b
             nyf, nxf = rho0s[lv + 1].shape
             if barrier is not None:                                      # solver_wdotsocp2d.m:186-189
                 rho0s[lv], rho1s[lv], _ = ensure_barrier_validity(rho0s[lv], rho1s[lv], barrier)
-                ws[lv] = ML.downSample_barrier(nts[lv + 1], nxf, nyf, ws[lv + 1])
+                if not wdev:
+                    ws[lv] = ML.downSample_barrier(nts[lv + 1], nxf, nyf, ws[lv + 1])
                 continue
-            ws[lv] = ML.downSample_q(nts[lv + 1], nxf, nyf, ws[lv + 1])
+            if not wdev:
+                ws[lv] = ML.downSample_q(nts[lv + 1], nxf, nyf, ws[lv + 1])
         N = rho0s[lv].size
         rho0s[lv] = rho0s[lv] / (rho0s[lv].sum() / N)
         rho1s[lv] = rho1s[lv] / (rho1s[lv].sum() / N)
@@ -317,15 +349,28 @@ def _solve_levels(rho0, rho1, nt, levelN, opts, method, dim, weighted, device, b
     # process (a level with few time nodes gets fewer slabs: at least two nodes per slab)
     ngpu = int(_get(opts, "ngpu", 1) or 1)
     var, model = initialize(rho0s[0], rho1s[0], nts[0], lazy_zeros=on_device)
-    if weighted:
-        model.weight = ws[0]
     timeML, runHistML, runHist, last = [], None, None, None
-    ctx = prev = None
+    ctx = prev = pyr = None
+
+    def level_weight(model, lv):
+        if wdev:                          # no Nq host array: InitialScaling reads the mean, the context the pyramid level
+            model.weight_log10_mean = pyr.log10_mean(lv)
+        elif weighted:
+            model.weight = ws[lv]
+
     try:
+        if wdev:
+            pyr = WeightPyramid(rho0s[-1].shape[0], rho0s[-1].shape[1], nts[-1], L, device=device)
+            pyr.set(wopt)
+            pyr.restrict(log_mean=barrier is not None)                   # solver_wdotsocp2d.m:186-191
+        level_weight(model, 0)
         for lv in range(L):
             InitialScaling(var, model, o["scaling"], last, dim=dim, weighted=weighted)
             ctx = InPALMContext(var, dict(o, tol=tols[lv]), model, weighted=weighted, device=device, method=method,
-                                warm_from=prev, ngpu=max(1, min(ngpu, nts[lv] // 2)))
+                                warm_from=prev, ngpu=max(1, min(ngpu, nts[lv] // 2)),
+                                weight_from=(pyr, lv) if wdev else None)
+            if wdev and lv == L - 1:
+                pyr.close()                                              # the last level has its weight
             if prev is not None:
                 prev.close()
                 prev = None
@@ -356,8 +401,7 @@ def _solve_levels(rho0, rho1, nt, levelN, opts, method, dim, weighted, device, b
                     E2 = var.E2
                     var, model = initialize(rho0s[lv + 1], rho1s[lv + 1], nts[lv + 1], lazy_zeros=True, phi=False)
                     var.E2 = E2                         # the state comes from the coarse level on the device
-                    if weighted:
-                        model.weight = wf
+                    level_weight(model, lv + 1)
                     prev = ctx
                 else:
                     var, model = ML.jump_nextLevel(var, model, rho0s[lv + 1], rho1s[lv + 1], nts[lv + 1], wf)
@@ -369,7 +413,7 @@ def _solve_levels(rho0, rho1, nt, levelN, opts, method, dim, weighted, device, b
             else:
                 output = dict(rho=rho_E[0], Ex=rho_E[1], q0=qs[0], bx=qs[1])
     finally:
-        for c in (ctx, prev):
+        for c in (ctx, prev, pyr):
             if c is not None:
                 c.close()
     timeML.append({"ML_Time": time.perf_counter() - t_all})
@@ -398,10 +442,12 @@ def solver_dotsocp1d(rho0, rho1, nt, levelN, opts, method="inPALM", device=0, tr
     return output, timeML, runHistML, runHist
 
 
-def solver_wdotsocp2d(rho0, rho1, nt, levelN, opts, method="inPALM", barrier=None, device=0, transfer="device"):
-    """socp/wdot2d/solver_wdotsocp2d.m:1"""
+def solver_wdotsocp2d(rho0, rho1, nt, levelN, opts, method="inPALM", barrier=None, device=0, transfer="device",
+                      weights=None):
+    """socp/wdot2d/solver_wdotsocp2d.m:1.  opts["weight"]: the Nq array, or a SpaceWeight (examples.py); weights:
+    where the levels' weights are made, "host" or "device" (_solve_levels)."""
     output, timeML, runHistML, runHist = _solve_levels(rho0, rho1, nt, levelN, opts, method, 2, True, device,
-                                                       barrier=barrier, transfer=transfer)
+                                                       barrier=barrier, transfer=transfer, weights=weights)
     if not check_massConservation(output["rho"], 1e-2):
         print("Warning: The tolerance of mass conservation constraint is under 0.01")
     return output, timeML, runHistML, runHist

@@ -293,6 +293,47 @@ int dotsocp_recover_outputs(dotsocp_ctx *ctx, const double *rho0, const double *
  * communicator attached are refused (DOTSOCP_EINVAL): their levels exchange state through the host. */
 int dotsocp_jump_next_level(dotsocp_ctx *coarse, dotsocp_ctx *fine);
 
+/* Weight pyramid: model.weight of every level of one weighted multilevel solve (socp/wdot2d/solver_wdotsocp2d.m:173-191),
+ * resident on the device.  The finest level is filled once -- from a host array, or from the two 2-D arrays the barrier
+ * and radial generators repeat over t -- the coarser ones are restricted from it on the device, and each level's context
+ * takes its weight by a device-to-device copy: no grid-sized weight array is built, restricted or reduced on the host.
+ * A level is stored in the reference layout [q0; bx; by] of its grid. */
+typedef struct dotsocp_weights dotsocp_weights;
+
+/* Grid of the FINEST level and the number of levels.  Level levels-1 is the finest; level l-1 has (n+1)/2 points per axis
+ * of level l.  levels > 1 needs 2^k*m+1 sizes on every axis down to the coarsest level (ny, nx, nt >= 2 always).
+ * NULL + last_error otherwise (and without a device). */
+dotsocp_weights *dotsocp_weights_create(int device, dotsocp_i64 ny, dotsocp_i64 nx, dotsocp_i64 nt, int levels);
+void dotsocp_weights_destroy(dotsocp_weights *w);
+
+/* Pure host arithmetic, no device: Nq of level `level`.  -1 for a bad level, or a grid that cannot be halved that often. */
+dotsocp_i64 dotsocp_weights_len(dotsocp_i64 ny, dotsocp_i64 nx, dotsocp_i64 nt, int levels, int level);
+
+/* Finest level from a host array in the reference layout [q0; bx; by] ... */
+int dotsocp_weights_set(dotsocp_weights *w, const double *weight);
+/* ... or from weightX (ny x (nx-1)) and weightY ((ny-1) x nx), column-major, repeated over the nt time nodes, with 1 on
+ * every time edge (examples/wdot2d/get_weight_by_barrier.m:20-33, gene_weight_circle.m).  Either call invalidates the
+ * coarser levels. */
+int dotsocp_weights_set_space(dotsocp_weights *w, const double *weightX, const double *weightY);
+
+/* Fill levels levels-2 .. 0 (DOTSOCP_ESTATE before a set).  log_mean = 0: socp/wdot2d/utils/downSample_q.m:4-21;
+ * log_mean = 1: downSample_barrier.m:4-21 (restriction of log(weight), then exp). */
+int dotsocp_weights_restrict(dotsocp_weights *w, int log_mean);
+
+/* mean(log10(weight + 1e-10)) of a level (solver_wdotsocp2d.m:312-316).  The order of the additions is fixed: two calls
+ * give the same bits.  A level that has not been filled: DOTSOCP_ESTATE (also for download / upload_weight_from). */
+int dotsocp_weights_log10_mean(dotsocp_weights *w, int level, double *mean);
+
+int dotsocp_weights_download(dotsocp_weights *w, int level, double *host);
+
+/* model.weight of `ctx` <- level `level`, device to device; replaces dotsocp_upload(ctx, DOTSOCP_F_WEIGHT, ...).  Serves
+ * one slab, `nslabs` slabs on one device and dotsocp_create_multi (each slab takes its layers, by peer copies where the
+ * devices differ: straight into place, or -- rows pitched -- through a staging buffer on the slab's device.  STATUS: as
+ * for dotsocp_create_multi, copies between DIFFERENT devices have never run on hardware; DOTSOCP_WEIGHT_STAGE=1 takes
+ * the staged form on one device).  DOTSOCP_EINVAL: an unweighted or 1-D context, a grid that is not the level's, a context with an RCCL
+ * communicator attached; DOTSOCP_ESTATE: after begin(). */
+int dotsocp_upload_weight_from(dotsocp_ctx *ctx, dotsocp_weights *w, int level);
+
 /* runHist.{kkt (len x 7, column-major), time, iter, pdGap} (:350-354); any pointer may be NULL */
 int dotsocp_get_history(dotsocp_ctx *ctx, double *kkt, double *time, double *iter, double *pdGap);
 

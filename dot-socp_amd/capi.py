@@ -74,6 +74,7 @@ SYMBOLS = {
     "dotsocp_field_len": (i64, [ctypes.POINTER(Problem), ctypes.c_int]),
     "dotsocp_dct_algorithm": (ctypes.c_int, [i64]),
     "dotsocp_dct_levels": (ctypes.c_int, [i64, ctypes.c_int]),
+    "dotsocp_cdft_levels": (ctypes.c_int, [i64]),
     "dotsocp_tsolve_tri_safe": (ctypes.c_int, [i64, i64, i64]),
     "dotsocp_cone_writes_beta": (ctypes.c_int, [i64, dbl, i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, dbl, dbl]),
     "dotsocp_rescale_due": (ctypes.c_int, [i64, ctypes.c_int, dbl, dbl]),
@@ -182,7 +183,7 @@ DCT_ALGORITHMS = ("none", "fft", "pfa", "rader", "bluestein", "dense")
 
 def dct_algorithm(n):
     """The transform the DCT passes use for an axis of length n: "fft" (power of two), "pfa" (prime-factor lengths),
-    "rader" (257), "bluestein" (other lengths up to 1024), "dense" (DCT-matrix product) or "none" (n <= 1).  No device needed."""
+    "rader" (257), "bluestein" (other lengths up to 1024, and from 4101 up to 2^19 - 1: cdft_levels), "dense" (DCT-matrix product) or "none" (n <= 1).  No device needed."""
     return DCT_ALGORITHMS[lib().dotsocp_dct_algorithm(int(n))]
 
 
@@ -192,3 +193,10 @@ def dct_levels(n, axis):
     lines beyond the LDS (from 4096 along y and 16384 along x / t up to 2^20; DOTSOCP_DCT_LONG_MIN lowers the start),
     negative: unsupported.  No device needed."""
     return int(lib().dotsocp_dct_levels(int(n), int(axis)))
+
+
+def cdft_levels(n):
+    """How the convolution-based transform of a length n runs: 0 no convolution transform (power of two, prime-factor
+    length, dense product), 1 Rader / Bluestein with the convolution in LDS, 2 Bluestein with a two-level convolution
+    through a scratch array (from 4101, or from DOTSOCP_CDFT_LONG_MIN >= 129, up to 2^19 - 1).  No device needed."""
+    return int(lib().dotsocp_cdft_levels(int(n)))

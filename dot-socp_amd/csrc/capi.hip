@@ -297,6 +297,7 @@ int dotsocp_attach_rccl(dotsocp_ctx *ctx, const unsigned char id[128], int rank,
 
 int dotsocp_dct_algorithm(dotsocp_i64 n) { return dct_choose_algorithm(n); }
 int dotsocp_dct_levels(dotsocp_i64 n, int axis) { return dct_levels(n, axis); }
+int dotsocp_cdft_levels(dotsocp_i64 n) { return cdft_levels(n); }
 int dotsocp_tsolve_tri_safe(dotsocp_i64 ny, dotsocp_i64 nx, dotsocp_i64 nt) { return tsolve_tri_safe(ny, nx, nt) ? 1 : 0; }
 
 int dotsocp_cone_writes_beta(dotsocp_i64 it, double last_sigma_it, dotsocp_i64 maxit, int check_step_by_step,

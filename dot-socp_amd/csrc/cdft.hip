@@ -12,7 +12,8 @@
 //     entry 0 adds it to every output of the convolution.
 //   Bluestein, 48 <= n <= 1024: chirp w_j = exp(-i pi j^2 / n) (exponent reduced exactly, (j * j) % (2 * n)),
 //     X_k = w_k sum_j (v_j w_j) conj(w_{k-j}), M = 2^ceil(log2(2n-1)) <= 2048.
-// Lengths above 1024 keep the dense product.
+// Lengths above 1024 do not fit a convolution in the LDS: cdft_long.hip runs the same algebra as a two-level FFT through a
+// scratch array (by default from 4101; DOTSOCP_CDFT_LONG_MIN), the lengths in between keep the dense product.
 #include "cdft.h"
 #include "device_utils.h"
 #include "fft_lds.h"
@@ -180,7 +181,7 @@ __global__ void __launch_bounds__(T) k_cdft(const double *src, double *dst, Line
 typedef std::complex<long double> cld;
 
 // in-place radix-2 FFT of length M = 2^lg in long double (twiddles from cosl / sinl, no recurrences)
-static void fft_ld(std::vector<cld> &a, int lg) {
+void cdft_fft_ld(std::vector<cld> &a, int lg) {
     const long double PI = 3.141592653589793238462643383279502884L;
     const int M = 1 << lg;
     std::vector<cld> W((size_t)M / 2 + 1);
@@ -247,7 +248,7 @@ CdftPlan *cdft_plan_create(i64 n64) {
             posIn[j] = posOut[j] = (int)j;
         }
     }
-    fft_ld(b, lg);
+    cdft_fft_ld(b, lg);
     std::vector<double2> spec(M), tw(M / 2), ww(n);
     for (int i = 0; i < M; ++i) {
         int j = 0;

@@ -9,7 +9,8 @@
 //     ... from 4096 (y) / 16384 (x, t) up to 2^20: two-level FFT through a scratch array   dct_long.hip
 //   the 2^k+1 grids of the multilevel driver   prime-factor transform                  pfa.hip
 //   257 and the other lengths up to 1024  Rader / Bluestein convolution                cdft.hip
-//   the rest                              product with the dense DCT matrix            dct_dense.hip
+//     ... from 4101 (DOTSOCP_CDFT_LONG_MIN) up to 2^19 - 1: Bluestein with a two-level convolution   cdft_long.hip
+//   the rest (up to 4100)                 product with the dense DCT matrix            dct_dense.hip
 // What is not a transform stays here too: the copy of a length-1 axis and the spectral division.
 #include "cdft.h"
 #include "dct_families.h"
@@ -37,24 +38,34 @@ int dct_choose_algorithm(i64 n) {
     if (n <= 1) return DCT_ALG_NONE;
     if ((n & (n - 1)) == 0) return DCT_ALG_FFT;
     if (pfa_supported(n)) return pfa_on ? DCT_ALG_PFA : DCT_ALG_DENSE;
+    // the two-level convolution first: its switch may claim lengths the LDS convolution or the dense product would serve
+    if (cdft_on && n >= cdft_long_min() && n <= CDFT_LONG_MAX_N) return DCT_ALG_BLUESTEIN;
     if (cdft_on && n == 257) return DCT_ALG_RADER;
     if (cdft_on && n >= nb && n <= CDFT_MAX_N) return DCT_ALG_BLUESTEIN;
     return DCT_ALG_DENSE;
 }
 
+int cdft_levels(i64 n) {
+    const int alg = dct_choose_algorithm(n);
+    if (alg == DCT_ALG_RADER) return 1;
+    if (alg == DCT_ALG_BLUESTEIN) return n >= cdft_long_min() ? 2 : 1;
+    return 0;
+}
+
 struct DctPlan {
     i64 n;
-    int alg;            // dct_choose_algorithm(n): which one of the four plans below exists
+    int alg;            // dct_choose_algorithm(n): which one of the plans below exists
     Pow2Plan *pow2;
     PfaPlan *pfa;
     CdftPlan *cdft;
+    CdftLongPlan *clong;   // DCT_ALG_BLUESTEIN with cdft_levels(n) == 2, instead of `cdft`
     DensePlan *dense;
 };
 
 DctPlan *dct_plan_create(i64 n) {
     DctPlan *p = new DctPlan();
     p->n = n;
-    p->alg = dct_choose_algorithm(n);      // the one place that reads DOTSOCP_PFA / DOTSOCP_CDFT / DOTSOCP_CDFT_MIN
+    p->alg = dct_choose_algorithm(n);      // reads DOTSOCP_PFA / DOTSOCP_CDFT / DOTSOCP_CDFT_MIN / DOTSOCP_CDFT_LONG_MIN
     bool ok = true;
     switch (p->alg) {
         case DCT_ALG_FFT: ok = (p->pow2 = pow2_plan_create(n)) != nullptr; break;
@@ -62,7 +73,10 @@ DctPlan *dct_plan_create(i64 n) {
         // n x n matrices of the dense product (16 MB and two million long-double cosines at n = 1025)
         case DCT_ALG_PFA: ok = (p->pfa = pfa_plan_create(n)) != nullptr; break;
         case DCT_ALG_RADER:
-        case DCT_ALG_BLUESTEIN: ok = (p->cdft = cdft_plan_create(n)) != nullptr; break;
+        case DCT_ALG_BLUESTEIN:
+            if (cdft_levels(n) == 2) ok = (p->clong = cdft_long_plan_create(n)) != nullptr;
+            else ok = (p->cdft = cdft_plan_create(n)) != nullptr;
+            break;
         case DCT_ALG_DENSE: ok = (p->dense = dense_plan_create(n)) != nullptr; break;
         default: break;                    // n <= 1: nothing to transform
     }
@@ -78,6 +92,7 @@ void dct_plan_destroy(DctPlan *p) {
     pow2_plan_destroy(p->pow2);
     pfa_plan_destroy(p->pfa);
     cdft_plan_destroy(p->cdft);
+    cdft_long_plan_destroy(p->clong);
     dense_plan_destroy(p->dense);
     delete p;
 }
@@ -156,7 +171,9 @@ int launch_dct_axis(const DctPlan *p, const double *src, double *dst, i64 n0, i6
             if (axis == 1) return pfa_launch_strided(p->pfa, src, dst, n0, n2, P0 * n1, P0, P0 * n1, P0, inverse ? 1 : 0, nullptr, st);
             return pfa_launch_strided(p->pfa, src, dst, n0, n1, P0, P0 * n1, P0, P0 * n1, inverse ? 1 : 0, nullptr, st);
         case DCT_ALG_RADER:
-        case DCT_ALG_BLUESTEIN: return cdft_launch(p->cdft, src, dst, map, axis == 0, inverse, st);
+        case DCT_ALG_BLUESTEIN:
+            if (p->clong) return cdft_long_launch(p->clong, src, dst, map, axis == 0, inverse, st);
+            return cdft_launch(p->cdft, src, dst, map, axis == 0, inverse, st);
         case DCT_ALG_DENSE: return dense_launch(p->dense, src, dst, map, axis == 0, inverse, st);
         default: set_error("dct plan of length %lld has no transform", (long long)p->n); return DOTSOCP_EINVAL;
     }

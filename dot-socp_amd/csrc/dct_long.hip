@@ -14,24 +14,19 @@
 // many consecutive columns / rows as the LDS budget holds; strided axes: as many pairs of lines consecutive in memory
 // as it holds.  Every line is addressed through LineMap on its own, so odd line counts, pitched rows and pairs that
 // straddle a row need no special case.
+#include "cdft.h"
 #include "dct_families.h"
 #include "device_utils.h"
 #include "fft_lds.h"
 #include "kernels.h"
-#include "solver.h"
+#include "long_scratch.h"
 
 #include <cmath>
 #include <cstdlib>
-#include <map>
-#include <mutex>
 #include <vector>
 
 namespace dotsocp {
 
-#define LONG_THREADS 256
-#define LONG_BATCH 4                       // global loads in flight per lane before the first dependent LDS write
-#define LONG_LDS_BUDGET (72 * 1024)        // two workgroups per CU
-#define LONG_MAX_ROWS 32                   // staged rows per workgroup: divides LONG_THREADS
 // Bound of the scratch array of one (plan, stream) pair; a pass over more lines runs in batches of whole tiles.
 #define LONG_SCRATCH_BYTES ((size_t)64 << 20)
 
@@ -61,6 +56,13 @@ int dct_length_check(i64 n) {
                   (long long)n, (long long)DCT_LONG_MAX_N);
         return DOTSOCP_EINVAL;
     }
+    // no other family serves a length above 1025 that is not a power of two, and the dense product's n x n matrices are
+    // out of reach long before
+    if (n > CDFT_LONG_MAX_N && (n & (n - 1)) != 0) {
+        set_error("DCT length %lld is not a power of two and above the limit of the two-level Bluestein transform "
+                  "(largest supported: %lld = 2^19 - 1)", (long long)n, (long long)CDFT_LONG_MAX_N);
+        return DOTSOCP_EINVAL;
+    }
     return 0;
 }
 
@@ -72,18 +74,8 @@ struct LongPlan {
     const double2 *hi, *lo;                // exp(-2 pi i m / n) = hi[m / n2] * lo[m % n2], m = j2 k1 < n
     const double2 *fa, *fb;                // ww[k1 + n1 k2] = fa[k1] * fb[k2]   (k > 0; ww of dct_pow2.hip)
     const double2 *ia, *ib;                // ww[j1 n2 + j2] = ia[j1] * ib[j2]
-    std::mutex mu;
-    struct Buf { double2 *p; size_t bytes; };
-    std::map<hipStream_t, Buf> scratch;    // one array per stream: two launches of one plan may be in flight
-    std::vector<double2 *> retired;        // outgrown arrays: work queued on them may still run, freed with the plan
+    LongScratch scratch;                   // long_scratch.h: one array per stream
 };
-
-// exp(-2 pi i num / den), the index reduced exactly in integers
-static double2 unit_root(i64 num, i64 den) {
-    const long double PI = 3.141592653589793238462643383279502884L;
-    const long double a = -2.0L * PI * (long double)(num % den) / (long double)den;
-    return make_double2((double)cosl(a), (double)sinl(a));
-}
 
 LongPlan *long_plan_create(i64 n) {
     if (n < 256 || n > DCT_LONG_MAX_N || (n & (n - 1))) return nullptr;
@@ -128,25 +120,9 @@ LongPlan *long_plan_create(i64 n) {
 
 void long_plan_destroy(LongPlan *p) {
     if (!p) return;
-    for (auto &kv : p->scratch) dfree(kv.second.p);
-    for (double2 *q : p->retired) dfree(q);
+    p->scratch.release();
     if (p->tab) (void)hipFree(p->tab);
     delete p;
-}
-
-// the scratch array of (plan, stream), at least `bytes` long
-static int long_scratch(LongPlan *p, hipStream_t st, size_t bytes, double2 **out) {
-    std::lock_guard<std::mutex> lk(p->mu);
-    LongPlan::Buf &b = p->scratch[st];
-    if (b.bytes < bytes) {
-        if (b.p) p->retired.push_back(b.p);
-        b.p = nullptr;
-        b.bytes = 0;
-        DS_CHECK(guarded_malloc((void **)&b.p, bytes));
-        b.bytes = bytes;
-    }
-    *out = b.p;
-    return 0;
 }
 
 struct LongArgs {
@@ -331,20 +307,6 @@ __global__ void __launch_bounds__(LONG_THREADS) k_long_rows(const double2 *__res
     }
 }
 
-static int floor_log2_i(i64 v) {
-    int l = 0;
-    while (((i64)2 << l) <= v) ++l;
-    return l;
-}
-
-// log2 of the complex rows of length m a workgroup stages: what the LDS budget holds, at most LONG_MAX_ROWS
-static int long_log2_rows(int m) {
-    i64 rows = (i64)(LONG_LDS_BUDGET / ((size_t)row_stride(m) * sizeof(double2)));
-    if (rows > LONG_MAX_ROWS) rows = LONG_MAX_ROWS;
-    if (rows < 2) rows = 2;
-    return floor_log2_i(rows);
-}
-
 int long_launch(LongPlan *p, const double *src, double *dst, const LineMap &map, bool axis0, int inverse, hipStream_t st) {
     if (map.nLines <= 0) return 0;
     const int n1 = 1 << p->lg1, n2 = 1 << p->lg2;
@@ -366,7 +328,7 @@ int long_launch(LongPlan *p, const double *src, double *dst, const LineMap &map,
     if (perBatch < 1) perBatch = 1;
     if (perBatch > nTiles) perBatch = nTiles;
     double2 *scratch = nullptr;
-    DS_CHECK(long_scratch(p, st, (size_t)perBatch * tileBytes, &scratch));
+    DS_CHECK(p->scratch.get(st, (size_t)perBatch * tileBytes, &scratch));
     static unsigned long long done = 0;
     if (DeviceOnce once_(done); once_) {
         allow_big_lds(k_long_cols<false>); allow_big_lds(k_long_cols<true>);

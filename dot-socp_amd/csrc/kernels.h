@@ -322,17 +322,21 @@ double *kkt_qstep_partials(const Grid &g, const KktWork &w);
 int launch_kkt_final(const Grid &g, const KktWork &w, hipStream_t st);
 
 // ---------------- dct.hip: plan, choice of the transform family, dispatch, spectral division ----------------
-// (the families: dct_pow2.hip, pfa.hip, cdft.hip, dct_dense.hip -- dct_families.h, pfa.h, cdft.h)
+// (the families: dct_pow2.hip / dct_long.hip, pfa.hip, cdft.hip / cdft_long.hip, dct_dense.hip -- dct_families.h, pfa.h, cdft.h)
 // Which transform a DCT plan of length n uses (dotsocp_dct_algorithm of include/dotsocp.h).
 enum { DCT_ALG_NONE = 0, DCT_ALG_FFT = 1, DCT_ALG_PFA = 2, DCT_ALG_RADER = 3, DCT_ALG_BLUESTEIN = 4, DCT_ALG_DENSE = 5 };
-// Pure host arithmetic (no HIP call); honours DOTSOCP_PFA, DOTSOCP_CDFT and DOTSOCP_CDFT_MIN, each read once per process.
+// Pure host arithmetic (no HIP call); honours DOTSOCP_PFA, DOTSOCP_CDFT, DOTSOCP_CDFT_MIN and
+// DOTSOCP_CDFT_LONG_MIN, each read once per process.
 int dct_choose_algorithm(i64 n);
 struct DctPlan;   // the choice for one axis length and the chosen family's tables
 // 0 no transform (n <= 1), 1 one pass with the line in LDS (or one of the other families), 2 the two-level transform of
-// dct_long.hip, negative: unsupported (a power of two above 2^20).  dct_length_check: 0, or DOTSOCP_EINVAL with the limit
+// dct_long.hip, negative: unsupported (a power of two above 2^20).  (Lengths that are no powers of two: 1 whatever the family.)  dct_length_check: 0, or DOTSOCP_EINVAL with the limit
 // in the error text -- asked before plans and contexts are made, so that nothing fails at a launch.
 int dct_levels(i64 n, int axis);
 int dct_length_check(i64 n);
+// 0 no convolution transform (power of two, prime-factor length, dense product), 1 Rader / Bluestein inside the LDS
+// (cdft.hip), 2 Bluestein with the two-level convolution of cdft_long.hip (DOTSOCP_CDFT_LONG_MIN)
+int cdft_levels(i64 n);
 DctPlan *dct_plan_create(i64 n);
 void dct_plan_destroy(DctPlan *p);
 // Orthonormal DCT-II (inverse=0) / DCT-III (inverse=1) along one axis of an [n0][n1][n2] array

@@ -86,14 +86,15 @@ int dotsocp_bfd_conj1d(double *q, const double *z, dotsocp_i64 nt, dotsocp_i64 n
  *    mirt_dctn.m / mirt_idctn.m (orthonormal DCT-II / DCT-III along every axis);
  *    call site solver_socp_inPALM.m:96,194.   For a 1-D problem pass ny = nx1d, nx = 1
  *    (socp/dot1d/utils/oper_poisson.m:4).  rhs and res hold ny*nx*nt doubles.
- *    Lengths: any; a power of two may have up to 2^20 points on every axis (dotsocp_dct_levels), a longer one is
- *    refused with DOTSOCP_EINVAL before anything is launched. */
+ *    Lengths: a power of two may have up to 2^20 points on every axis (dotsocp_dct_levels), any other length up to
+ *    2^19 - 1 (dotsocp_cdft_levels); a longer one is refused with DOTSOCP_EINVAL before anything is launched. */
 int dotsocp_oper_poisson(double *res, const double *rhs, dotsocp_i64 ny, dotsocp_i64 nx,
                          dotsocp_i64 nt, double kernelScale);
 
 /* a <- dctn(a) (inverse = 0) or idctn(a) (inverse = 1) of an ny x nx x nt array
  * -- socp/dot2d/utils/mirt_dctn.m:64-141, mirt_idctn.m:59-128.  Power-of-two lengths up to 2^20 on every axis: in
- *    one pass while the line fits the LDS, by a two-level FFT beyond (dotsocp_dct_levels); longer: DOTSOCP_EINVAL. */
+ *    one pass while the line fits the LDS, by a two-level FFT beyond (dotsocp_dct_levels); other lengths up to
+ *    2^19 - 1 (dotsocp_cdft_levels); longer: DOTSOCP_EINVAL. */
 int dotsocp_dctn(double *a, dotsocp_i64 ny, dotsocp_i64 nx, dotsocp_i64 nt, int inverse);
 
 /* Same operators on DEVICE pointers (no PCIe traffic), enqueued on `stream`
@@ -213,9 +214,19 @@ int dotsocp_slab_range(dotsocp_i64 nt, int world, int rank, dotsocp_i64 *t0, dot
 dotsocp_i64 dotsocp_field_len(const dotsocp_problem *prob, int field);
 
 /* Which transform the DCT passes use for an axis of length n (pure host arithmetic, no device; honours the switches
- * DOTSOCP_PFA, DOTSOCP_CDFT, DOTSOCP_CDFT_MIN): 0 none (n <= 1), 1 power-of-two FFT, 2 prime-factor FFT, 3 Rader (257),
- * 4 Bluestein (other lengths up to 1024), 5 dense DCT-matrix product. */
+ * DOTSOCP_PFA, DOTSOCP_CDFT, DOTSOCP_CDFT_MIN, DOTSOCP_CDFT_LONG_MIN): 0 none (n <= 1), 1 power-of-two FFT, 2 prime-factor
+ * FFT, 3 Rader (257), 4 Bluestein (other lengths up to 1024 in the LDS, from 4101 up to 2^19 - 1 with a two-level
+ * convolution: dotsocp_cdft_levels), 5 dense DCT-matrix product. */
 int dotsocp_dct_algorithm(dotsocp_i64 n);
+
+/* How the convolution-based transform of a length n runs (pure host arithmetic, no device).  0: no convolution transform
+ * (power of two, prime-factor length, dense product, or DOTSOCP_CDFT=0); 1: Rader / Bluestein with the whole convolution
+ * in LDS (257 and the Bluestein lengths up to 1024); 2: Bluestein with the convolution of length 2^ceil(log2(2n-1)) as a
+ * two-level FFT through a scratch array -- every length from DOTSOCP_CDFT_LONG_MIN (never below 129; default 4101) up
+ * to 2^19 - 1 that is neither a power of two nor a prime-factor length, on every axis.  A longer length that is not a
+ * power of two is refused with DOTSOCP_EINVAL by dotsocp_dctn, dotsocp_oper_poisson and dotsocp_create before anything
+ * is launched. */
+int dotsocp_cdft_levels(dotsocp_i64 n);
 
 /* How many passes through memory the transform of an axis of length n takes along `axis` (0: y, the contiguous axis;
  * 1: x; 2: t).  Pure host arithmetic, no device.  0: no transform (n <= 1); 1: one pass, the whole line in LDS (or one

@@ -10,8 +10,10 @@ import dotsocp_amd as D  # noqa: E402
 
 tol, nt, nx, levelN = 1e-4, 2 ** 5 + 1, 2 ** 7 + 1, 3
 rho0, rho1 = D.get_example_2d("example1", nx, nx)
-output, timeML, runHistML, runHist = D.solver_dotsocp2d(rho0, rho1, nt, levelN, dict(tol=tol, maxit=3000), "inPALM")
+output, timeML, runHistML, runHist = D.solver_dotsocp2d(rho0, rho1, nt, levelN, dict(tol=tol, maxit=3000), "inPALM", report=True)
 for lv, t in enumerate(timeML[:-1], 1):
     print(f"level {lv}: {int(t['Iters'])} iterations, {t['Total_Time']:.2f} s")
 print("final KKT (1,3,6,7):", runHist["kkt"][-1][[0, 2, 5, 6]])
 print("mass conservation within 1e-2:", D.check_massConservation(output["rho"], 1e-2))
+# the same judgement and more (negative densities, f(q) <= 0, cost), formed on the device from the resident state
+print(output["report"].summary())

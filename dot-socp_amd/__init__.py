@@ -15,6 +15,8 @@ from .mexops import (mexBFd, mexBFd1d, mexBFdConj, mexBFdConj1d, mexProjSoc, mir
                      oper_poisson, oper_poisson3dim)
 from .model import (InitialScaling, ModelHandle, VarHandle, check_massConservation, initialize,  # noqa: F401
                     initialize_slab, recover_q, recover_RhoE, recoverOrgVar)
+from .report import (SolutionReport, hist_negative_density, hist_positive_value, hist_violation_q_1d,  # noqa: F401
+                     hist_violation_q_2d, report_edges, solution_report)
 from .weights import WeightPyramid  # noqa: F401
 from .solvers import (InPALMContext, poisson_on_slabs, solver_dotsocp1d, solver_dotsocp2d, solver_socp_accADMM,  # noqa: F401
                       solver_socp_inPALM, solver_socp_PALM, solver_wdotsocp2d, solver_wsocp_accADMM, solver_wsocp_inPALM)

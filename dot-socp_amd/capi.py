@@ -45,6 +45,18 @@ class AccOpts(ctypes.Structure):
     _fields_ = [("restart", i64), ("rho", dbl), ("theta", dbl)]
 
 
+REPORT_BINS = 49               # DOTSOCP_REPORT_BINS
+REPORT_RHO_FLOOR = 1e-8        # DOTSOCP_REPORT_RHO_FLOOR
+
+
+class Report(ctypes.Structure):
+    """dotsocp_report"""
+    _fields_ = [("n_nodes", i64), ("n_cells", i64), ("mass_err", dbl), ("neg_err", dbl),
+                ("rho_min", dbl), ("rho_neg", i64), ("rho_hist", i64 * REPORT_BINS),
+                ("fq_max", dbl), ("fq_pos", i64), ("fq_hist", i64 * REPORT_BINS),
+                ("cost", dbl), ("nonfinite", i64)]
+
+
 METHOD_INPALM, METHOD_PALM, METHOD_ACCADMM = 0, 1, 2
 
 
@@ -87,6 +99,8 @@ SYMBOLS = {
     "dotsocp_begin_method": (ctypes.c_int, [vp, ctypes.POINTER(Opts), ctypes.c_int, ctypes.POINTER(AccOpts)]),
     "dotsocp_run": (ctypes.c_int, [vp, i64, ctypes.POINTER(i64)]),
     "dotsocp_recover_outputs": (ctypes.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "dotsocp_report_edges": (ctypes.c_int, [vp]),
+    "dotsocp_solution_report": (ctypes.c_int, [vp, vp, vp, ctypes.POINTER(Report), vp, vp]),
     "dotsocp_jump_next_level": (ctypes.c_int, [vp, vp]),
     "dotsocp_finish": (ctypes.c_int, [vp, ctypes.POINTER(Result)]),
     "dotsocp_get_history": (ctypes.c_int, [vp, vp, vp, vp, vp]),

@@ -347,6 +347,18 @@ int dotsocp_recover_outputs(dotsocp_ctx *ctx, const double *rho0, const double *
     return ctx->s.recover_outputs(rho0, rho1, rho, Ex, Ey, q0, bx, by);
 }
 
+int dotsocp_report_edges(double edges[DOTSOCP_REPORT_BINS + 1]) {
+    if (!edges) { set_error("invalid argument: report_edges() needs an array of %d doubles", DOTSOCP_REPORT_BINS + 1); return DOTSOCP_EINVAL; }
+    report_edges_host(edges);
+    return 0;
+}
+
+int dotsocp_solution_report(dotsocp_ctx *ctx, const double *rho0, const double *rho1, dotsocp_report *rep, double *layer_mass,
+                            double *layer_neg) {
+    CTX_OR_FAIL();
+    return ctx->s.solution_report(rho0, rho1, rep, layer_mass, layer_neg);
+}
+
 int dotsocp_jump_next_level(dotsocp_ctx *coarse, dotsocp_ctx *fine) {
     if (!coarse || !fine) { set_error("context is NULL"); return DOTSOCP_EINVAL; }
     return fine->s.jump_from(coarse->s);

@@ -161,6 +161,22 @@ int launch_outputs(const Grid &g, const double *q, const double *alpha, const do
 int launch_out_tail(const Grid &g, const double *alpha, const double *weight, double sig, double cD, double *out,
                     hipStream_t st);
 
+// ---------------- report.hip: the solution report (mass, negativity, f(q) histograms) in one pass over alpha and q ----------------
+// Slots of the 64-bit counters one report accumulates (device array, zeroed before the launch): the two histograms, three
+// counts, and min(rho) / max(fq) over the finite values as order-preserving integer keys (report_key_decode; 0: no value)
+enum { RC_RHO_HIST = 0, RC_FQ_HIST = DOTSOCP_REPORT_BINS, RC_RHO_NEG = 2 * DOTSOCP_REPORT_BINS, RC_FQ_POS, RC_NONFINITE,
+       RC_RHO_MIN, RC_FQ_MAX, RC_COUNT };
+void report_edges_host(double edges[DOTSOCP_REPORT_BINS + 1]);
+double report_key_decode(unsigned long long key, bool inverted, double none);
+// workgroups per layer (depends on ny, nx only) and doubles of the partial-sum buffer of a slab: [ntl][3][tiles]
+i64 report_tiles(const Grid &g);
+// one slab: `partials` [ntl][3][tiles] <- per-workgroup layer sums of rho, min(rho, 0) and the cost terms; `sums` [ntl][3]
+// <- their totals, added in tile order; counts[RC_COUNT] += this slab's share.  rho0 / rho1 / a_prev as for launch_outputs;
+// edges: DOTSOCP_REPORT_BINS + 1 doubles on the device.
+int launch_report(const Grid &g, const double *q, const double *alpha, const double *weight, const double *rho0,
+                  const double *rho1, const double *a_prev, double sig, double cD, double dD, bool dim1, const double *edges,
+                  double *partials, double *sums, unsigned long long *counts, hipStream_t st);
+
 // ---------------- qstep_march.hip: the q-step as one march through the time layers (march step: qstep_tile.h) ----------------
 // q-step + alpha update (alpha_in -> alpha_out, distinct buffers) + rhs of the next iteration's phi-step
 // ex (optional): a scaling of alpha_in that is still pending in memory (applied on load), and -- partials != nullptr, one

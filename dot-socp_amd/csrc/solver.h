@@ -114,6 +114,10 @@ struct Slab {
     // Halpern anchors / previous extrapolation points
     double *phi_p = nullptr, *alpha_p = nullptr, *z_p = nullptr;
     double *phi_a = nullptr, *q_a = nullptr, *alpha_a = nullptr, *z_a = nullptr, *beta_a = nullptr;
+    // solution report (report.hip; allocated at its first use): bin edges, per-tile layer sums [ntl][3][tiles], their totals
+    // [ntl][3], the 64-bit counters [RC_COUNT]
+    double *rep_edges = nullptr, *rep_part = nullptr, *rep_sums = nullptr;
+    unsigned long long *rep_counts = nullptr;
 };
 
 // every slab this process holds, with the slab's device made current first (member functions returning int)
@@ -268,6 +272,9 @@ struct Solver {
     int recover_outputs(const double *rho0, const double *rho1, double *rho, double *Ex, double *Ey, double *q0,
                         double *bx, double *by);
     int jump_from(Solver &coarse);
+    // mass / negativity / f(q) histograms / cost of the finished solve in one pass over alpha and q (report.hip);
+    // layer_mass, layer_neg: nt doubles each or NULL
+    int solution_report(const double *rho0, const double *rho1, dotsocp_report *rep, double *layer_mass, double *layer_neg);
 
     // ================ the inPALM loop and its profiling: solver.hip ================
     // ---- loop state (mirrors solver_socp_inPALM.m:11-135) ----

@@ -3,6 +3,7 @@
 // recover_RhoE / recover_q.  Kernels: transfer.hip.  Both work on in-process time slabs (dotsocp_create_multi).
 // Below them: the fields between host and device (upload, upload_layers, download, the zero test of c at begin()).
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 
 #include "solver.h"
@@ -51,6 +52,94 @@ int Solver::recover_outputs(const double *rho0, const double *rho1, double *rho,
         }
         DS_CHECK(sync_all());                               // w0 is reused by the next output
     }
+    return 0;
+}
+
+// The judgement the reference's demos pass on the downloaded outputs (check_massConservation, hist_negative_density,
+// hist_violation_q_*, the transport cost), from the device-resident alpha and q: one launch_report per slab, staged like
+// recover_outputs (rho0 / rho1 in w1, the left neighbour's last cell through k_out_tail / shift); what comes back is
+// 3 sums per layer and RC_COUNT integers per slab, combined here -- layers in layer order, counters by integer addition.
+int Solver::solution_report(const double *rho0, const double *rho1, dotsocp_report *rep, double *layer_mass, double *layer_neg) {
+    DS_ARG(rho0 != nullptr && rho1 != nullptr && rep != nullptr, "solution_report() needs rho0, rho1 and rep (one of them is NULL)");
+    DS_ARG(!remote(), "solution_report() serves the slabs of one process; contexts with an RCCL communicator are not reported");
+    if (!finished) { set_error("solution_report() needs finish()"); return DOTSOCP_ESTATE; }
+    DS_CHECK(need_beta_form("solution_report"));
+    DS_CHECK(need_q("solution_report"));
+    cur_dev = -1;
+    DS_CHECK(use_dev(device));
+    const i64 plane = slabs[0].g.plane, py = slabs[0].g.py;
+    const double cD = cScale * D, dD = dScale / D;         // recoverOrgVar (solver_dotsocp2d.m:368-386)
+    if (multi()) {
+        FOR_SLABS(s)
+            if (!s.g.last) DS_CHECK(launch_out_tail(s.g, s.alpha, s.weight, sigma, cD, s.send_plane, s.st));
+        DS_CHECK(shift(+1, [](Slab &s) { return s.send_plane; }, [](Slab &s) { return s.a0_prev; }, plane));
+    }
+    // host side of the copies: lives until the sync_all() below
+    double edges[DOTSOCP_REPORT_BINS + 1];
+    report_edges_host(edges);
+    std::vector<double> sums((size_t)(3 * nt));
+    std::vector<unsigned long long> counts((size_t)RC_COUNT * slabs.size());
+    size_t k = 0;
+    FOR_SLABS(s) {
+        const Grid &g = s.g;
+        if (!s.rep_counts) {
+            DS_CHECK(s.alloc(&s.rep_edges, DOTSOCP_REPORT_BINS + 1));
+            DS_CHECK(s.alloc(&s.rep_part, 3 * g.ntl * report_tiles(g)));
+            DS_CHECK(s.alloc(&s.rep_sums, 3 * g.ntl));
+            DS_CHECK(s.alloc(&s.rep_counts, RC_COUNT));
+        }
+        double *d_r0 = s.w1, *d_r1 = s.w1 + plane;         // w1 holds at least two layers (nt >= 2 per slab)
+        if (g.first) DS_CHECK(copy_rows(d_r0, const_cast<double *>(rho0), ny, py, nx, true, s.st));
+        if (g.last) DS_CHECK(copy_rows(d_r1, const_cast<double *>(rho1), ny, py, nx, true, s.st));
+        DS_HIP(ds_memcpy_async(s.rep_edges, edges, sizeof edges, hipMemcpyHostToDevice, s.st));
+        DS_HIP(ds_memset_async(s.rep_counts, 0, sizeof(unsigned long long) * RC_COUNT, s.st));
+        DS_CHECK(launch_report(g, s.q, s.alpha, s.weight, d_r0, d_r1, s.a0_prev, sigma, cD, dD, prob.dim == 1, s.rep_edges,
+                               s.rep_part, s.rep_sums, s.rep_counts, s.st));
+        DS_HIP(ds_memcpy_async(sums.data() + 3 * g.t0, s.rep_sums, sizeof(double) * 3 * g.ntl, hipMemcpyDeviceToHost, s.st));
+        DS_HIP(ds_memcpy_async(counts.data() + RC_COUNT * k++, s.rep_counts, sizeof(unsigned long long) * RC_COUNT,
+                               hipMemcpyDeviceToHost, s.st));
+    }
+    DS_CHECK(sync_all());
+    if (canary_enabled()) {        // DOTSOCP_CANARY=1: the report's kernels wrote inside their buffers
+        std::string what;
+        const int bad = canary_check(&what);
+        cur_dev = -1;
+        if (bad) {
+            set_error("canary: %d device buffer(s) written out of bounds: %s", bad, what.c_str());
+            return DOTSOCP_EHIP;
+        }
+    }
+    memset(rep, 0, sizeof *rep);
+    const i64 hplane = ny * nx;
+    rep->n_nodes = hplane * nt;
+    rep->n_cells = hplane * (nt - 1);
+    // max that keeps a NaN once it has met one (a layer with a NaN in it must not pass for a conserved one)
+    auto worst = [](double m, double d) { return (d > m || d != d) ? d : m; };
+    double cost = 0.0;
+    for (i64 t = 0; t < nt; ++t) {
+        const double mass = sums[3 * t] / (double)hplane, neg = sums[3 * t + 1] / (double)hplane;
+        if (layer_mass) layer_mass[t] = mass;
+        if (layer_neg) layer_neg[t] = neg;
+        rep->mass_err = worst(rep->mass_err, fabs(mass - 1.0));
+        rep->neg_err = worst(rep->neg_err, fabs(neg));
+        cost += sums[3 * t + 2];
+    }
+    rep->cost = cost / (double)rep->n_nodes;
+    unsigned long long kmin = 0, kmax = 0;
+    for (size_t j = 0; j < slabs.size(); ++j) {
+        const unsigned long long *c = counts.data() + RC_COUNT * j;
+        for (int b = 0; b < DOTSOCP_REPORT_BINS; ++b) {
+            rep->rho_hist[b] += (i64)c[RC_RHO_HIST + b];
+            rep->fq_hist[b] += (i64)c[RC_FQ_HIST + b];
+        }
+        rep->rho_neg += (i64)c[RC_RHO_NEG];
+        rep->fq_pos += (i64)c[RC_FQ_POS];
+        rep->nonfinite += (i64)c[RC_NONFINITE];
+        kmin = std::max(kmin, c[RC_RHO_MIN]);
+        kmax = std::max(kmax, c[RC_FQ_MAX]);
+    }
+    rep->rho_min = report_key_decode(kmin, true, INFINITY);
+    rep->fq_max = report_key_decode(kmax, false, -INFINITY);
     return 0;
 }
 

@@ -7,6 +7,7 @@
 // Index conventions as everywhere: y fastest, then x, then t; 1-D problems are ny = nx1d, nx = 1.
 #include "device_utils.h"
 #include "kernels.h"
+#include "outputs_node.h"
 
 namespace dotsocp {
 
@@ -129,56 +130,47 @@ int launch_scale_div(double *x, const double *w, i64 n, double sc, hipStream_t s
 // ---------------------------------------------------------------------------------------
 // Time slabs: t below is the slab-local layer, g.t0 + t the global one; the density at a slab's first node
 // averages over the left neighbour's last cell, whose a(.) arrives ready-made in `a_prev` (k_out_tail).
-struct OutArgs {
-    const double *q, *alpha, *weight, *rho0, *rho1, *a_prev;
-    double sig, cD, dD;
-};
-
+// The expressions themselves: outputs_node.h (k_report of report.hip forms the same values without storing them).
 __global__ void __launch_bounds__(TILE_Y *TILE_X) k_outputs(Grid g, OutArgs a, int which, double *__restrict__ out) {
     const i64 y = (i64)blockIdx.x * TILE_Y + threadIdx.x;
     const i64 x = (i64)blockIdx.y * TILE_X + threadIdx.y;
     const i64 t = blockIdx.z;
     if (y >= g.ny || x >= g.nx) return;
     const i64 nt = g.nt, tg = g.t0 + t;
-    auto A = [&](i64 k) {
-        const double v = a.cD * (a.sig * a.alpha[k]);
-        return a.weight ? a.weight[k] * v : v;
-    };
-    auto B = [&](i64 k) { return a.dD * a.q[k]; };
     const i64 node = y + g.py * (x + g.nx * t);
     double r = 0.0;
     if (which == 0) {
         if (tg == 0) r = a.rho0[y + g.py * x];
         else if (tg == nt - 1) r = a.rho1[y + g.py * x];
-        else r = ((t == 0 ? a.a_prev[y + g.py * x] : A(node - g.plane)) + A(node)) / 2;
+        else r = out_mean2(t == 0 ? a.a_prev[y + g.py * x] : out_a(a, node - g.plane), out_a(a, node));
     } else if (which == 1 || which == 2) {
         const double f = (tg == 0 || tg == nt - 1) ? 2.0 : 1.0;
         if (which == 1) {
             if (x >= 1 && x <= g.nx - 2) {
-                const i64 e = g.offBx + g.bxLayer * t + y + g.py * x;
-                r = (A(e - g.py) * f + A(e) * f) / 2;
+                const i64 e = out_edge_x(g, y, x, t);
+                r = out_flux(out_a(a, e - g.py), out_a(a, e), f);
             }
         } else {
             if (y >= 1 && y <= g.ny - 2) {
-                const i64 e = g.offBy + g.byLayer * t + y + g.pyb * x;
-                r = (A(e - 1) * f + A(e) * f) / 2;
+                const i64 e = out_edge_y(g, y, x, t);
+                r = out_flux(out_a(a, e - 1), out_a(a, e), f);
             }
         }
     } else if (which == 3) {
-        r = B(node);
+        r = out_b(a, node);
     } else if (which == 4) {
         if (x >= 1 && x <= g.nx - 2) {
-            const i64 e = g.offBx + g.bxLayer * t + y + g.py * x;
-            const double m0 = (B(e - g.py) + B(e)) / 2;
-            const double m1 = (B(e - g.py + g.bxLayer) + B(e + g.bxLayer)) / 2;
-            r = (m0 + m1) / 2;
+            const i64 e = out_edge_x(g, y, x, t);
+            const double m0 = out_mean2(out_b(a, e - g.py), out_b(a, e));
+            const double m1 = out_mean2(out_b(a, e - g.py + g.bxLayer), out_b(a, e + g.bxLayer));
+            r = out_mean2(m0, m1);
         }
     } else {
         if (y >= 1 && y <= g.ny - 2) {
-            const i64 e = g.offBy + g.byLayer * t + y + g.pyb * x;
-            const double m0 = (B(e - 1) + B(e)) / 2;
-            const double m1 = (B(e - 1 + g.byLayer) + B(e + g.byLayer)) / 2;
-            r = (m0 + m1) / 2;
+            const i64 e = out_edge_y(g, y, x, t);
+            const double m0 = out_mean2(out_b(a, e - 1), out_b(a, e));
+            const double m1 = out_mean2(out_b(a, e - 1 + g.byLayer), out_b(a, e + g.byLayer));
+            r = out_mean2(m0, m1);
         }
     }
     out[node] = r;
@@ -188,9 +180,7 @@ __global__ void __launch_bounds__(TILE_Y *TILE_X) k_outputs(Grid g, OutArgs a, i
 __global__ void __launch_bounds__(256) k_out_tail(Grid g, OutArgs a, double *__restrict__ out) {
     const i64 i = (i64)blockIdx.x * 256 + threadIdx.x;
     if (i >= g.plane) return;
-    const i64 k = i + g.plane * (g.ncl - 1);
-    const double v = a.cD * (a.sig * a.alpha[k]);
-    out[i] = a.weight ? a.weight[k] * v : v;
+    out[i] = out_a(a, i + g.plane * (g.ncl - 1));
 }
 
 int launch_out_tail(const Grid &g, const double *alpha, const double *weight, double sig, double cD, double *out,

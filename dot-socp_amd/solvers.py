@@ -182,6 +182,13 @@ class InPALMContext:
         self.result = res
         return runHist, res.sigma
 
+    def _rho_ends(self):
+        """model.rho0 / rho1 in the column-major layout the library reads, converted once per context (10 ms for a pair of
+        row-major 1024 x 1024 arrays: several times what the whole device report takes)"""
+        if getattr(self, "_ends", None) is None:
+            self._ends = (np.asfortranarray(self.model.rho0, dtype=np.float64), np.asfortranarray(self.model.rho1, dtype=np.float64))
+        return self._ends
+
     def outputs(self):
         """solver_dotsocp2d.m:262-281 on the device (recoverOrgVar + recover_RhoE + recover_q): dict with rho, Ex,
         [Ey,] q0, bx[, by]; call after finish()."""
@@ -191,12 +198,25 @@ class InPALMContext:
         shp = (int(m.nx),) if one_d else (int(m.ny), int(m.nx))
         names = ("rho", "Ex", "q0", "bx") if one_d else ("rho", "Ex", "Ey", "q0", "bx", "by")
         out = {k: np.empty(shp + ((nt - 1,) if k in ("q0", "bx", "by") else (nt,)), order="F") for k in names}
-        r0 = np.asfortranarray(m.rho0, dtype=np.float64)
-        r1 = np.asfortranarray(m.rho1, dtype=np.float64)
+        r0, r1 = self._rho_ends()
         ptr = lambda k: capi.fptr(out[k]) if k in out else None      # noqa: E731
         capi.check(capi.lib().dotsocp_recover_outputs(self._ctx, capi.fptr(r0), capi.fptr(r1), ptr("rho"), ptr("Ex"),
                                                       ptr("Ey"), ptr("q0"), ptr("bx"), ptr("by")))
         return out
+
+    def report(self):
+        """The solution report on the device (dotsocp_solution_report; report.py): mass conservation, negative densities,
+        violation of f(q) <= 0 and the transport cost of the finished solve, from one pass over the device-resident alpha
+        and q -- no output array is made or downloaded.  Call after finish(); same numbers as
+        report.solution_report(self.outputs())."""
+        from .report import from_struct
+        m = self.model
+        nt = int(m.nt)
+        r0, r1 = self._rho_ends()
+        rep, mass, neg = capi.Report(), np.empty(nt), np.empty(nt)
+        capi.check(capi.lib().dotsocp_solution_report(self._ctx, capi.fptr(r0), capi.fptr(r1), ctypes.byref(rep),
+                                                      capi.fptr(mass), capi.fptr(neg)))
+        return from_struct(rep, mass, neg)
 
     def close(self):
         if getattr(self, "_ctx", None):
@@ -293,7 +313,7 @@ def _weights_mode(weight, weights, transfer, weighted=True):
 
 
 def _solve_levels(rho0, rho1, nt, levelN, opts, method, dim, weighted, device, barrier=None, transfer="device",
-                  weights=None):
+                  weights=None, report=False):
     """The level loop of solver_dotsocp2d.m:154-250 (dot1d / wdot2d twins): restrict the data to
     levelN grids, solve coarse to fine with warm starts; every solve runs on the device.
     transfer = "device": the state never leaves the GPU -- jump_nextLevel and the output recovery run there
@@ -304,13 +324,17 @@ def _solve_levels(rho0, rho1, nt, levelN, opts, method, dim, weighted, device, b
     once (an Nq array, or the two 2-D arrays of a SpaceWeight), the others are restricted on the GPU, every level's
     context takes its weight device to device and InitialScaling its log10 mean from the pyramid; needs
     transfer="device".  None: "device" for a SpaceWeight with transfer="device", else "host" (a SpaceWeight is then
-    expanded on the host)."""
+    expanded on the host).
+    report = True: the last level's context is asked for its solution report (InPALMContext.report(), report.py) before it
+    is closed; output["report"] holds it.  Needs transfer="device"."""
     from . import multilevel as ML
     from .examples import ensure_barrier_validity
     if not (isinstance(levelN, (int, np.integer)) and levelN >= 1):
         raise ValueError("Invalid input at position 4 (Number of levels in multilevel strategy)")
     if transfer not in ("device", "host"):
         raise ValueError("transfer must be 'device' or 'host'")
+    if report and transfer != "device":
+        raise ValueError("report=True needs transfer='device' (the report is taken from the device-resident state)")
     wopt = _get(opts, "weight") if weighted else None
     weights = _weights_mode(wopt, weights, transfer, weighted)
     wdev = weights == "device"
@@ -389,6 +413,8 @@ def _solve_levels(rho0, rho1, nt, levelN, opts, method, dim, weighted, device, b
                 runHistML["len"] = runHistML["len"] + runHist["len"]
             if on_device and last_level:
                 output = ctx.outputs()
+                if report:
+                    output["report"] = ctx.report()
             if not on_device:
                 ctx.close()
                 recoverOrgVar(var)
@@ -423,31 +449,31 @@ def _solve_levels(rho0, rho1, nt, levelN, opts, method, dim, weighted, device, b
     return output, timeML, runHistML, runHist
 
 
-def solver_dotsocp2d(rho0, rho1, nt, levelN, opts, method="inPALM", device=0, transfer="device"):
+def solver_dotsocp2d(rho0, rho1, nt, levelN, opts, method="inPALM", device=0, transfer="device", report=False):
     """[output, timeML, runHistML, runHist] = solver_dotsocp2d(rho0, rho1, nt, levelN, opts, method)
-    socp/dot2d/solver_dotsocp2d.m:1"""
+    socp/dot2d/solver_dotsocp2d.m:1.  report=True: output["report"] = the device-side solution report (_solve_levels)."""
     output, timeML, runHistML, runHist = _solve_levels(rho0, rho1, nt, levelN, opts, method, 2, False, device,
-                                                       transfer=transfer)
+                                                       transfer=transfer, report=report)
     if not check_massConservation(output["rho"], 1e-2):
         print("Warning: The mass conservation constraint violation exceeds 0.01")
     return output, timeML, runHistML, runHist
 
 
-def solver_dotsocp1d(rho0, rho1, nt, levelN, opts, method="inPALM", device=0, transfer="device"):
-    """socp/dot1d/solver_dotsocp1d.m:1"""
+def solver_dotsocp1d(rho0, rho1, nt, levelN, opts, method="inPALM", device=0, transfer="device", report=False):
+    """socp/dot1d/solver_dotsocp1d.m:1.  report: as for solver_dotsocp2d."""
     output, timeML, runHistML, runHist = _solve_levels(rho0, rho1, nt, levelN, opts, method, 1, False, device,
-                                                       transfer=transfer)
+                                                       transfer=transfer, report=report)
     if not check_massConservation(output["rho"], 1e-2):
         print("Warning: The mass conservation constraint violation exceeds 0.01")
     return output, timeML, runHistML, runHist
 
 
 def solver_wdotsocp2d(rho0, rho1, nt, levelN, opts, method="inPALM", barrier=None, device=0, transfer="device",
-                      weights=None):
+                      weights=None, report=False):
     """socp/wdot2d/solver_wdotsocp2d.m:1.  opts["weight"]: the Nq array, or a SpaceWeight (examples.py); weights:
-    where the levels' weights are made, "host" or "device" (_solve_levels)."""
+    where the levels' weights are made, "host" or "device" (_solve_levels); report: as for solver_dotsocp2d."""
     output, timeML, runHistML, runHist = _solve_levels(rho0, rho1, nt, levelN, opts, method, 2, True, device,
-                                                       barrier=barrier, transfer=transfer, weights=weights)
+                                                       barrier=barrier, transfer=transfer, weights=weights, report=report)
     if not check_massConservation(output["rho"], 1e-2):
         print("Warning: The tolerance of mass conservation constraint is under 0.01")
     return output, timeML, runHistML, runHist

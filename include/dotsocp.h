@@ -294,6 +294,41 @@ int dotsocp_finish(dotsocp_ctx *ctx, dotsocp_result *res);
 int dotsocp_recover_outputs(dotsocp_ctx *ctx, const double *rho0, const double *rho1, double *rho, double *Ex,
                             double *Ey, double *q0, double *bx, double *by);
 
+/* Solution report on the device: what the reference's demos compute from the downloaded outputs --
+ * check_massConservation (utils/check_massConservation.m:16-27), hist_negative_density, hist_violation_q_{1d,2d}
+ * (utils/hist_positive_value.m:28-55) and the transport cost -- formed in ONE pass over the device-resident alpha and q;
+ * no grid-sized array is written or crosses PCIe.  rho, Ex, Ey, q0, bx, by at a node / cell are the values
+ * dotsocp_recover_outputs would write, bit for bit, and
+ *   fq = (q0 + .5 (bx^2 + by^2)) / (1 + |q0| + sqrt(bx^2 + by^2))          1-D: (q0 + .5 bx^2) / (1 + |q0| + |bx|).
+ * Histogram of y = -rho resp. y = fq over the edges of dotsocp_report_edges: bin j counts edges[j] <= y < edges[j+1],
+ * the last bin also y == edges[DOTSOCP_REPORT_BINS] (MATLAB histcounts with explicit edges, compared on y itself, not on
+ * log10(y)); y < edges[0], y > edges[last] and non-finite y are in no bin.  The layer sums are added in an order that
+ * depends on (ny, nx) alone and `cost` in layer order: two calls give the same bits, and so does a context cut into
+ * time slabs. */
+#define DOTSOCP_REPORT_BINS 49              /* hist_positive_value.m:28-30: 50 edges 10^linspace(-8,-1,50) */
+#define DOTSOCP_REPORT_RHO_FLOOR 1e-8       /* nodes with rho <= floor do not enter `cost` */
+typedef struct {
+    dotsocp_i64 n_nodes, n_cells;           /* ny*nx*nt, ny*nx*(nt-1)  (1-D: nx*nt, nx*(nt-1)) */
+    double mass_err, neg_err;               /* max_t |mean(rho(:,:,t)) - 1|, max_t |mean(min(rho(:,:,t),0))|
+                                               check_massConservation.m:16-27 (integralL2 = layer mean) */
+    double rho_min;  dotsocp_i64 rho_neg;   /* min over finite rho (+Inf if there is none); count of rho < 0 */
+    dotsocp_i64 rho_hist[DOTSOCP_REPORT_BINS];   /* y = -rho          hist_negative_density.m:14 */
+    double fq_max;   dotsocp_i64 fq_pos;    /* max over finite fq (-Inf if there is none); count of fq > 0 */
+    dotsocp_i64 fq_hist[DOTSOCP_REPORT_BINS];    /* y = fq            hist_violation_q_2d.m:4 / _1d.m:4 */
+    double cost;                            /* (1/n_nodes) * sum over nodes with rho > floor of (Ex^2 [+ Ey^2]) / rho */
+    dotsocp_i64 nonfinite;                  /* NaN / Inf among the rho and fq values (0 for a healthy solve) */
+} dotsocp_report;
+
+/* The DOTSOCP_REPORT_BINS + 1 bin edges 10^linspace(-8, -1, 50).  Pure host arithmetic, no device. */
+int dotsocp_report_edges(double edges[DOTSOCP_REPORT_BINS + 1]);
+/* Call after finish().  rho0, rho1: model.rho0 / rho1 (ny x nx, host) as for dotsocp_recover_outputs.  layer_mass /
+ * layer_neg (nt doubles each, or NULL): mean(rho(:,:,t)) and mean(min(rho(:,:,t), 0)) of every time layer.  Works on
+ * one slab, `nslabs` slabs and dotsocp_create_multi (per-slab partial results are combined on the host).
+ * DOTSOCP_ESTATE before finish(); DOTSOCP_EINVAL for a NULL rho0, rho1 or rep, and for a context with an RCCL
+ * communicator attached (rank-local reports are not provided). */
+int dotsocp_solution_report(dotsocp_ctx *ctx, const double *rho0, const double *rho1, dotsocp_report *rep,
+                            double *layer_mass /* nt or NULL */, double *layer_neg /* nt or NULL */);
+
 /* Multilevel transfer on the device: socp/dot2d/utils/jump_nextLevel.m:5-16 with
  * interpolate.m:20-84, between the finished context `coarse` and the context `fine` of the next level (created
  * from the fine level's InitialScaling scalars, c and weight uploaded, begin() not yet called; grid

@@ -1,0 +1,37 @@
+#!/usr/bin/env python3
+"""Where the mass goes: the transport map of Example 5.1 (Gaussian -> Gaussian, 129 x 129 x 33, 3 levels, inPALM,
+tol 1e-4), by carrying particles along the solved flow on the device (advect= of the drivers; dot-socp_amd/advect.py).
+Seeds: every 4th node where rho0 exceeds the floor max(rho0, rho1) / 100 (the mask of utils/show_movement_2d.m:31).
+The two Gaussians are equal and their centres (0.25, 0.75) and (0.75, 0.25) -- along (first, second) array index -- lie
+(+0.5, -0.5) apart in (y, x).  On the whole plane the map would be that translation; these Gaussians are wide (variance
+0.05: a standard deviation of 0.22) and cut off by the unit square, so only the mass near the centre moves by nearly that
+much, and a particle in the far corner has nowhere to go.  Printed: the deviation of the displacement from (+0.5, -0.5)
+over all particles, weighted by the mass rho0 they stand for, and over the seeds within 0.1 of the start centre."""
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import dotsocp_amd as D  # noqa: E402
+
+tol, nt, nx, levelN = 1e-4, 2 ** 5 + 1, 2 ** 7 + 1, 3
+rho0, rho1 = D.get_example_2d("example1", nx, nx)
+floor = D.default_rho_floor(rho0, rho1)
+x0, y0 = D.seeds_on_nodes(nx, nx, stride=4, mask=rho0 > floor)
+output, timeML, runHistML, runHist = D.solver_dotsocp2d(rho0, rho1, nt, levelN, dict(tol=tol, maxit=3000), "inPALM",
+                                                        advect=dict(x=x0, y=y0, nsub=2, trajectories=True))
+adv = output["advect"]
+dev = np.hypot(adv["x"] - x0 - (-0.5), adv["y"] - y0 - 0.5)
+print(f"{x0.size} particles (every 4th node with rho0 > {floor:.3g}), {adv['n_clamped']} clamped at the boundary")
+print(f"displacement (dy, dx): mean ({np.mean(adv['y'] - y0):+.4f}, {np.mean(adv['x'] - x0):+.4f}), expected (+0.5, -0.5)")
+print(f"deviation from the translation: mean {dev.mean():.4f}, worst {dev.max():.4f} ({dev.max() * (nx - 1):.2f} grid cells)")
+w = rho0[np.rint(y0 * (nx - 1)).astype(int), np.rint(x0 * (nx - 1)).astype(int)]
+print(f"  weighted by rho0: mean {np.sum(w * dev) / np.sum(w):.4f}")
+near = np.hypot(y0 - 0.25, x0 - 0.75) <= 0.1
+print(f"  {np.count_nonzero(near)} seeds within 0.1 of the start centre: mean {dev[near].mean():.4f}, worst {dev[near].max():.4f}")
+mid = nt // 2
+print(f"half-way (node {mid}): mean position (y, x) = ({adv['traj_y'][:, mid].mean():.4f}, {adv['traj_x'][:, mid].mean():.4f})")
+# and back: the particles at t = 1 return to their seeds along the same flow
+back = D.advect.advect({k: output[k] for k in ("rho", "Ex", "Ey")}, adv["x"], adv["y"], nsub=2, direction=-1)
+print(f"there and back (host twin, direction -1): worst distance from the seeds {np.hypot(back['x'] - x0, back['y'] - y0).max():.2e}")

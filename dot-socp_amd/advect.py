@@ -1,0 +1,144 @@
+"""Where the mass goes: the velocity v = E / rho of a solved flow and particles carried along it (the transport map).
+
+Host twins (numpy) of dotsocp_recover_velocity and dotsocp_advect_particles (include/dotsocp.h states the semantics once;
+csrc/advect.hip and this module follow them operation by operation -- no fused multiply-add on either side -- so
+InPALMContext.velocity() / .advect() and velocity(ctx.outputs(), floor) / advect(ctx.outputs(), ...) agree bit for bit).
+The velocity is the one utils/show_movement_2d.m draws: arrows of E, masked where rho is small.
+
+Coordinates: the unit square and t in [0, 1]; x runs along the SECOND array index of the outputs (nx columns, node i at
+i / (nx - 1)), y along the first (ny rows); 1-D outputs (nx, nt) have x alone.  E = +rho v.
+"""
+import numpy as np
+
+
+def default_rho_floor(rho0, rho1):
+    """max(rho0.max(), rho1.max()) / 100: the mask rule of show_movement_2d.m:31 (rho < max(rho) / 100 draws no arrow),
+    with the maximum taken over the two GIVEN densities instead of over all of rho, so that it needs no pass over rho (and
+    is known before the solve)."""
+    return max(float(np.max(rho0)), float(np.max(rho1))) / 100
+
+
+def _quot(E, rho, floor):
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        q = E / rho
+        return np.where((rho > floor) & np.isfinite(q), q, 0.0)
+
+
+def velocity(out, rho_floor):
+    """Twin of dotsocp_recover_velocity on the outputs dict (rho, Ex[, Ey]): dict(vx=..., [vy=...]) of the outputs'
+    shapes; v = E / rho where rho > rho_floor and the quotient is finite, else 0 (a NaN density gives 0)."""
+    rho = np.asarray(out["rho"], dtype=np.float64)
+    floor = float(rho_floor)
+    v = dict(vx=_quot(np.asarray(out["Ex"], dtype=np.float64), rho, floor))
+    if "Ey" in out:
+        v["vy"] = _quot(np.asarray(out["Ey"], dtype=np.float64), rho, floor)
+    return v
+
+
+def _clamp(u):
+    return np.where(u < 0.0, 0.0, np.where(u > 1.0, 1.0, u))
+
+
+def _cell(u, n):
+    f = u * float(n - 1)
+    i = np.minimum(np.floor(f).astype(np.int64), n - 2)
+    return i, f - i.astype(np.float64)
+
+
+class _Field:
+    """The node velocity, interpolated: bilinear in a layer, linear between the two layers of a time interval"""
+
+    def __init__(self, v):
+        self.vx, self.vy = v["vx"], v.get("vy")
+        self.one_d = self.vy is None
+        self.nx = self.vx.shape[0 if self.one_d else 1]
+        self.ny = None if self.one_d else self.vx.shape[0]
+
+    def _layer(self, F, i, a, j, c):
+        if self.one_d:
+            return (1.0 - a) * F[i] + a * F[i + 1]
+        f0 = (1.0 - c) * F[j, i] + c * F[j + 1, i]
+        f1 = (1.0 - c) * F[j, i + 1] + c * F[j + 1, i + 1]
+        return (1.0 - a) * f0 + a * f1
+
+    def __call__(self, x, y, k, b):
+        i, a = _cell(x, self.nx)
+        j, c = (None, None) if self.one_d else _cell(y, self.ny)
+        at = lambda V: (1.0 - b) * self._layer(V[..., k], i, a, j, c) + b * self._layer(V[..., k + 1], i, a, j, c)  # noqa: E731
+        return at(self.vx), (None if self.one_d else at(self.vy))
+
+
+def advect(out, x, y=None, nsub=1, direction=+1, rho_floor=None, trajectories=False):
+    """Twin of dotsocp_advect_particles on the outputs dict: classical RK4 along v = E / rho, nsub steps per time interval,
+    from t = 0 to 1 (direction=+1) or from 1 to 0 (-1).  x, y: seeds (y None for 1-D outputs); rho_floor None:
+    default_rho_floor of the first and last layer of rho (which are rho0 and rho1).  Returns dict(x, y, traj_x, traj_y,
+    n_clamped): final positions; with trajectories=True the (n, nt) positions at every time node, indexed by node in
+    both directions (else None); the number of particles that the clamp at the end of some step moved."""
+    rho = np.asarray(out["rho"], dtype=np.float64)
+    one_d = "Ey" not in out
+    if one_d != (y is None):
+        raise ValueError("advect(): y is given for 2-D outputs and only for them")
+    nsub, direction = int(nsub), int(direction)
+    if nsub < 1 or direction not in (1, -1):
+        raise ValueError("advect(): nsub >= 1 and direction +1 or -1")
+    if rho_floor is None:
+        rho_floor = default_rho_floor(rho[..., 0], rho[..., -1])
+    nt = rho.shape[-1]
+    x = np.array(x, dtype=np.float64).ravel()
+    y = None if one_d else np.array(y, dtype=np.float64).ravel()
+    if x.size < 1 or (y is not None and y.size != x.size):
+        raise ValueError("advect(): x and y hold the same number (>= 1) of seeds")
+    if not (np.all(np.isfinite(x)) and (one_d or np.all(np.isfinite(y)))):
+        raise ValueError("advect(): a seed is not finite")
+    V = _Field(velocity(out, rho_floor))
+    dt = direction / float((nt - 1) * nsub)
+    hh, h6 = 0.5 * dt, dt / 6.0
+    den = float(2 * nsub)
+    x = _clamp(x)
+    y = None if one_d else _clamp(y)
+    moved = np.zeros(x.size, dtype=bool)
+    step = lambda p, h, k: None if p is None else _clamp(p + h * k)          # noqa: E731
+    final = lambda p, k1, k2, k3, k4: p + h6 * (((k1 + 2.0 * k2) + 2.0 * k3) + k4)   # noqa: E731
+    tx = np.empty((x.size, nt), order="F") if trajectories else None
+    ty = np.empty((x.size, nt), order="F") if trajectories and not one_d else None
+
+    def record(node):
+        if trajectories:
+            tx[:, node] = x
+            if not one_d:
+                ty[:, node] = y
+
+    record(0 if direction > 0 else nt - 1)
+    for it in range(nt - 1):
+        k = it if direction > 0 else nt - 2 - it
+        for s in range(nsub):
+            e0 = 2 * s if direction > 0 else 2 * (nsub - s)
+            b0, b1, b2 = e0 / den, (e0 + direction) / den, (e0 + 2 * direction) / den
+            k1x, k1y = V(x, y, k, b0)
+            k2x, k2y = V(step(x, hh, k1x), step(y, hh, k1y), k, b1)
+            k3x, k3y = V(step(x, hh, k2x), step(y, hh, k2y), k, b1)
+            k4x, k4y = V(step(x, dt, k3x), step(y, dt, k3y), k, b2)
+            ux = final(x, k1x, k2x, k3x, k4x)
+            moved |= (ux < 0.0) | (ux > 1.0)
+            x = _clamp(ux)
+            if not one_d:
+                uy = final(y, k1y, k2y, k3y, k4y)
+                moved |= (uy < 0.0) | (uy > 1.0)
+                y = _clamp(uy)
+        record(k + 1 if direction > 0 else k)
+    return dict(x=x, y=y, traj_x=tx, traj_y=ty, n_clamped=int(np.count_nonzero(moved)))
+
+
+def seeds_on_nodes(nx, ny=None, stride=1, mask=None):
+    """Seeds on every stride-th node: (x, y) of the nodes (j, i), j = 0, stride, .. < ny and i = 0, stride, .. < nx, in
+    the grid's own order (y fastest: neighbouring particles then gather from neighbouring memory); 1-D (ny None): (x, None).
+    mask: boolean (ny, nx) array (1-D: (nx,)); only the nodes where it is true are kept."""
+    i = np.arange(0, int(nx), int(stride))
+    if ny is None:
+        keep = np.ones(i.size, dtype=bool) if mask is None else np.asarray(mask, dtype=bool)[i]
+        return (i / float(nx - 1))[keep], None
+    j = np.arange(0, int(ny), int(stride))
+    jj, ii = np.meshgrid(j, i, indexing="ij")
+    jj, ii = jj.ravel(order="F"), ii.ravel(order="F")
+    keep = np.ones(jj.size, dtype=bool) if mask is None else np.asarray(mask, dtype=bool)[jj, ii]
+    return (ii / float(nx - 1))[keep], (jj / float(ny - 1))[keep]

@@ -57,6 +57,11 @@ class Report(ctypes.Structure):
                 ("cost", dbl), ("nonfinite", i64)]
 
 
+class AdvectOpts(ctypes.Structure):
+    """dotsocp_advect_opts"""
+    _fields_ = [("n", i64), ("nsub", ctypes.c_int), ("direction", ctypes.c_int), ("rho_floor", dbl)]
+
+
 METHOD_INPALM, METHOD_PALM, METHOD_ACCADMM = 0, 1, 2
 
 
@@ -101,6 +106,8 @@ SYMBOLS = {
     "dotsocp_recover_outputs": (ctypes.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "dotsocp_report_edges": (ctypes.c_int, [vp]),
     "dotsocp_solution_report": (ctypes.c_int, [vp, vp, vp, ctypes.POINTER(Report), vp, vp]),
+    "dotsocp_recover_velocity": (ctypes.c_int, [vp, vp, vp, dbl, vp, vp]),
+    "dotsocp_advect_particles": (ctypes.c_int, [vp, vp, vp, ctypes.POINTER(AdvectOpts), vp, vp, vp, vp, ctypes.POINTER(i64)]),
     "dotsocp_jump_next_level": (ctypes.c_int, [vp, vp]),
     "dotsocp_finish": (ctypes.c_int, [vp, ctypes.POINTER(Result)]),
     "dotsocp_get_history": (ctypes.c_int, [vp, vp, vp, vp, vp]),

@@ -1,0 +1,202 @@
+// Particle transport along the solved flow: the velocity v = E / rho of the Benamou-Brenier solution at the nodes
+// (the arrows of utils/show_movement_2d.m, without the plot) and its characteristics, the Monge map, by classical RK4.
+// Semantics: include/dotsocp.h (dotsocp_recover_velocity, dotsocp_advect_particles); the numpy twin dot-socp_amd/advect.py
+// follows the kernels below operation by operation, and this file is built without contraction (Makefile), so the two
+// agree bit for bit.
+//   k_velocity_layer  one node layer of (vX, vY) from alpha: rho, Ex, Ey are the expressions of outputs_node.h, i.e. the
+//                     bits dotsocp_recover_outputs writes; no grid-sized velocity array is ever made
+//   k_advect          one thread per particle, one launch per time interval: all nsub RK4 steps with the position in
+//                     registers; every stage gathers 4 corners x 2 layers x 2 components from the two layers of the interval
+// Index conventions as everywhere: y fastest (rows `py` apart); X = the component / coordinate along the second array
+// index, Y = along the first.  1-D problems live in the Y slot (ny = nx1d, nx = 1): their kernels touch Y alone.
+#include "device_utils.h"
+#include "kernels.h"
+#include "outputs_node.h"
+
+namespace dotsocp {
+
+// a(.) of outputs_node.h with the weight's presence known at compile time (as report.hip's rep_a)
+template <bool WEIGHTED>
+__device__ __forceinline__ double vel_a(const OutArgs &o, i64 k) {
+    const double v = o.cD * (o.sig * o.alpha[k]);
+    return WEIGHTED ? o.weight[k] * v : v;
+}
+
+// v = E / rho where rho > floor and the quotient is finite, else 0: the field is finite everywhere (a NaN density fails
+// the comparison)
+__device__ __forceinline__ double vel_quot(double E, double rho, double floor) {
+    const double q = E / rho;
+    return (rho > floor && isfinite(q)) ? q : 0.0;
+}
+
+// node layer `tl` (slab-local) -> vX, vY [y + py * x]
+template <int DIM, bool WEIGHTED>
+__global__ void __launch_bounds__(TILE_Y *TILE_X) k_velocity_layer(Grid g, OutArgs o, i64 tl, double floor,
+                                                                    double *__restrict__ vX, double *__restrict__ vY) {
+    const i64 y = (i64)blockIdx.x * TILE_Y + threadIdx.x;
+    const i64 x = (i64)blockIdx.y * TILE_X + threadIdx.y;
+    if (y >= g.ny || x >= g.nx) return;
+    const i64 tg = g.t0 + tl, col = y + g.py * x, node = col + g.plane * tl;
+    const bool ends = (tg == 0 || tg == g.nt - 1);
+    double rho;
+    if (tg == 0) rho = o.rho0[col];
+    else if (tg == g.nt - 1) rho = o.rho1[col];
+    else rho = out_mean2(tl == 0 ? o.a_prev[col] : vel_a<WEIGHTED>(o, node - g.plane), vel_a<WEIGHTED>(o, node));
+    const double f = ends ? 2.0 : 1.0;
+    if (DIM == 2) {
+        double Ex = 0.0;
+        if (x >= 1 && x <= g.nx - 2) {
+            const i64 e = out_edge_x(g, y, x, tl);
+            Ex = out_flux(vel_a<WEIGHTED>(o, e - g.py), vel_a<WEIGHTED>(o, e), f);
+        }
+        vX[col] = vel_quot(Ex, rho, floor);
+    }
+    double Ey = 0.0;
+    if (y >= 1 && y <= g.ny - 2) {
+        const i64 e = out_edge_y(g, y, x, tl);
+        Ey = out_flux(vel_a<WEIGHTED>(o, e - 1), vel_a<WEIGHTED>(o, e), f);
+    }
+    vY[col] = vel_quot(Ey, rho, floor);
+}
+
+int launch_velocity_layer(const Grid &g, const double *alpha, const double *weight, const double *rho0, const double *rho1,
+                          const double *a_prev, double sig, double cD, bool dim1, i64 tl, double floor, double *vX, double *vY,
+                          hipStream_t st) {
+    if (tl < 0 || tl >= g.ntl) { set_error("internal: velocity layer outside its slab"); return DOTSOCP_ESTATE; }
+    OutArgs o{nullptr, alpha, weight, rho0, rho1, a_prev, sig, cD, 0.0};
+    dim3 grid((unsigned)((g.ny + TILE_Y - 1) / TILE_Y), (unsigned)((g.nx + TILE_X - 1) / TILE_X), 1), block(TILE_Y, TILE_X);
+    if (dim1) {
+        if (weight) DS_KLAUNCH((k_velocity_layer<1, true>), grid, block, 0, st, g, o, tl, floor, vX, vY);
+        else DS_KLAUNCH((k_velocity_layer<1, false>), grid, block, 0, st, g, o, tl, floor, vX, vY);
+    } else {
+        if (weight) DS_KLAUNCH((k_velocity_layer<2, true>), grid, block, 0, st, g, o, tl, floor, vX, vY);
+        else DS_KLAUNCH((k_velocity_layer<2, false>), grid, block, 0, st, g, o, tl, floor, vX, vY);
+    }
+    DS_HIP(hipGetLastError());
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------
+// particles
+// ---------------------------------------------------------------------------------------
+// one particle per thread; workgroups of 64, 128, 256 and 512 ran within 5 % of each other (profiles/advect_time.txt)
+#define ADV_BLOCK 256
+
+__device__ __forceinline__ double adv_clamp(double u) { return u < 0.0 ? 0.0 : (u > 1.0 ? 1.0 : u); }
+
+// seeds outside [0, 1] are moved onto the boundary before the first step (not counted as clamped); flags start at zero
+template <int DIM>
+__global__ void __launch_bounds__(ADV_BLOCK) k_advect_seed(i64 n, double *__restrict__ px, double *__restrict__ py,
+                                                          unsigned int *__restrict__ flag) {
+    const i64 p = (i64)blockIdx.x * ADV_BLOCK + threadIdx.x;
+    if (p >= n) return;
+    if (DIM == 2) px[p] = adv_clamp(px[p]);
+    py[p] = adv_clamp(py[p]);
+    flag[p] = 0u;
+}
+
+struct AdvectArgs {
+    const double *vX0, *vY0, *vX1, *vY1;    // velocity layers of node k and node k + 1 of the interval
+    i64 ny, nx, py;                         // nodes along Y / along X, row pitch
+    i64 n;
+    int nsub, dir;
+    double dt, hh, h6;                      // dir / ((nt - 1) nsub), dt / 2, dt / 6
+    double *px, *py_;                       // positions, SoA
+    unsigned int *flag;                     // sticky: the clamp at the end of some step moved this particle
+};
+
+// cell index and weight along one axis of n nodes: u in [0, 1]
+__device__ __forceinline__ void adv_cell(double u, i64 n, i64 &i, double &a) {
+    const double f = u * (double)(n - 1);
+    i = (i64)floor(f);
+    if (i > n - 2) i = n - 2;
+    a = f - (double)i;
+}
+
+// one layer at (x, y): along Y (the contiguous index) first, then along X
+template <int DIM>
+__device__ __forceinline__ double adv_layer(const double *__restrict__ F, i64 py, i64 i, double a, i64 j, double c) {
+    if (DIM == 1) return (1.0 - c) * F[j] + c * F[j + 1];
+    const double *p = F + j + py * i;
+    const double f0 = (1.0 - c) * p[0] + c * p[1];
+    const double f1 = (1.0 - c) * p[py] + c * p[py + 1];
+    return (1.0 - a) * f0 + a * f1;
+}
+
+template <int DIM>
+__device__ __forceinline__ void adv_velocity(const AdvectArgs &A, double x, double y, double b, double &vx, double &vy) {
+    i64 i = 0, j;
+    double a = 0.0, c;
+    if (DIM == 2) adv_cell(x, A.nx, i, a);
+    adv_cell(y, A.ny, j, c);
+    if (DIM == 2) vx = (1.0 - b) * adv_layer<2>(A.vX0, A.py, i, a, j, c) + b * adv_layer<2>(A.vX1, A.py, i, a, j, c);
+    else vx = 0.0;
+    vy = (1.0 - b) * adv_layer<DIM>(A.vY0, A.py, i, a, j, c) + b * adv_layer<DIM>(A.vY1, A.py, i, a, j, c);
+}
+
+template <int DIM>
+__global__ void __launch_bounds__(ADV_BLOCK) k_advect(AdvectArgs A) {
+    const i64 p = (i64)blockIdx.x * ADV_BLOCK + threadIdx.x;
+    if (p >= A.n) return;
+    double x = DIM == 2 ? A.px[p] : 0.0, y = A.py_[p];
+    bool moved = false;
+    const double den = (double)(2 * A.nsub);
+    for (int s = 0; s < A.nsub; ++s) {
+        // stage fractions inside the interval: forward from node k, backward from node k + 1
+        const int e0 = A.dir > 0 ? 2 * s : 2 * (A.nsub - s);
+        const double b0 = (double)e0 / den, b1 = (double)(e0 + A.dir) / den, b2 = (double)(e0 + 2 * A.dir) / den;
+        double k1x, k1y, k2x, k2y, k3x, k3y, k4x, k4y;
+        adv_velocity<DIM>(A, x, y, b0, k1x, k1y);
+        adv_velocity<DIM>(A, adv_clamp(x + A.hh * k1x), adv_clamp(y + A.hh * k1y), b1, k2x, k2y);
+        adv_velocity<DIM>(A, adv_clamp(x + A.hh * k2x), adv_clamp(y + A.hh * k2y), b1, k3x, k3y);
+        adv_velocity<DIM>(A, adv_clamp(x + A.dt * k3x), adv_clamp(y + A.dt * k3y), b2, k4x, k4y);
+        const double ux = x + A.h6 * (((k1x + 2.0 * k2x) + 2.0 * k3x) + k4x);
+        const double uy = y + A.h6 * (((k1y + 2.0 * k2y) + 2.0 * k3y) + k4y);
+        moved = moved || ux < 0.0 || ux > 1.0 || uy < 0.0 || uy > 1.0;
+        x = adv_clamp(ux);
+        y = adv_clamp(uy);
+    }
+    if (DIM == 2) A.px[p] = x;
+    A.py_[p] = y;
+    if (moved) A.flag[p] = 1u;
+}
+
+// *count += number of set flags
+__global__ void __launch_bounds__(ADV_BLOCK) k_advect_count(const unsigned int *__restrict__ flag, i64 n,
+                                                           unsigned long long *__restrict__ count) {
+    unsigned long long c = 0;
+    for (i64 p = (i64)blockIdx.x * ADV_BLOCK + threadIdx.x; p < n; p += (i64)gridDim.x * ADV_BLOCK) c += flag[p] ? 1u : 0u;
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) c += __shfl_down(c, off, 64);
+    if ((threadIdx.x & 63) == 0 && c) atomicAdd(count, c);
+}
+
+int launch_advect_seed(bool dim1, i64 n, double *px, double *py, unsigned int *flag, hipStream_t st) {
+    if (n <= 0) return 0;
+    const dim3 grid((unsigned)launch_blocks(n, ADV_BLOCK, (i64)1 << 30));
+    if (dim1) DS_KLAUNCH(k_advect_seed<1>, grid, dim3(ADV_BLOCK), 0, st, n, px, py, flag);
+    else DS_KLAUNCH(k_advect_seed<2>, grid, dim3(ADV_BLOCK), 0, st, n, px, py, flag);
+    DS_HIP(hipGetLastError());
+    return 0;
+}
+
+int launch_advect(bool dim1, i64 ny, i64 nx, i64 py, const double *vX0, const double *vY0, const double *vX1,
+                  const double *vY1, i64 n, int nsub, int dir, double dt, double *px, double *py_, unsigned int *flag,
+                  hipStream_t st) {
+    if (n <= 0) return 0;
+    AdvectArgs A{vX0, vY0, vX1, vY1, ny, nx, py, n, nsub, dir, dt, 0.5 * dt, dt / 6.0, px, py_, flag};
+    const dim3 grid((unsigned)launch_blocks(n, ADV_BLOCK, (i64)1 << 30));
+    if (dim1) DS_KLAUNCH(k_advect<1>, grid, dim3(ADV_BLOCK), 0, st, A);
+    else DS_KLAUNCH(k_advect<2>, grid, dim3(ADV_BLOCK), 0, st, A);
+    DS_HIP(hipGetLastError());
+    return 0;
+}
+
+int launch_advect_count(const unsigned int *flag, i64 n, unsigned long long *count, hipStream_t st) {
+    if (n <= 0) return 0;
+    DS_KLAUNCH(k_advect_count, dim3((unsigned)launch_blocks(n, ADV_BLOCK, 1024)), dim3(ADV_BLOCK), 0, st, flag, n, count);
+    DS_HIP(hipGetLastError());
+    return 0;
+}
+
+}  // namespace dotsocp

@@ -359,6 +359,21 @@ int dotsocp_solution_report(dotsocp_ctx *ctx, const double *rho0, const double *
     return ctx->s.solution_report(rho0, rho1, rep, layer_mass, layer_neg);
 }
 
+int dotsocp_recover_velocity(dotsocp_ctx *ctx, const double *rho0, const double *rho1, double rho_floor, double *vx, double *vy) {
+    CTX_OR_FAIL();
+    if (ctx->s.prob.dim == 1)     // 1-D problems live in the y slot of the engine (ny = nx1d, nx = 1)
+        return ctx->s.recover_velocity(rho0, rho1, rho_floor, nullptr, vx);
+    return ctx->s.recover_velocity(rho0, rho1, rho_floor, vx, vy);
+}
+
+int dotsocp_advect_particles(dotsocp_ctx *ctx, const double *rho0, const double *rho1, const dotsocp_advect_opts *o, double *x,
+                             double *y, double *traj_x, double *traj_y, dotsocp_i64 *n_clamped) {
+    CTX_OR_FAIL();
+    if (ctx->s.prob.dim == 1)
+        return ctx->s.advect_particles(rho0, rho1, o, nullptr, x, nullptr, traj_x, n_clamped);
+    return ctx->s.advect_particles(rho0, rho1, o, x, y, traj_x, traj_y, n_clamped);
+}
+
 int dotsocp_jump_next_level(dotsocp_ctx *coarse, dotsocp_ctx *fine) {
     if (!coarse || !fine) { set_error("context is NULL"); return DOTSOCP_EINVAL; }
     return fine->s.jump_from(coarse->s);
@@ -391,7 +406,8 @@ int dotsocp_kernel_time(dotsocp_ctx *ctx, const char *name, double *avg_ms, dots
     DS_ARG(name != nullptr, "name is NULL");
     static const char *names[PH_COUNT] = {"rhs", "poisson", "cone_proj", "qstep", "beta", "kkt",
                                           "cone_fused_a", "cone_fused_b", "materialise", "comm",
-                                          "interp", "acc_cone", "acc_gather", "qstep_first", "transpose", "cone_carry", "qcone"};
+                                          "interp", "acc_cone", "acc_gather", "qstep_first", "transpose", "cone_carry", "qcone",
+                                          "velocity_layer", "advect"};
     for (int i = 0; i < PH_COUNT; ++i)
         if (strcmp(name, names[i]) == 0) {
             const i64 n = ctx->s.phase_launches[i];

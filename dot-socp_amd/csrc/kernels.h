@@ -161,6 +161,21 @@ int launch_outputs(const Grid &g, const double *q, const double *alpha, const do
 int launch_out_tail(const Grid &g, const double *alpha, const double *weight, double sig, double cD, double *out,
                     hipStream_t st);
 
+// ---------------- advect.hip: node velocity v = E / rho layer by layer, particles along it (RK4) ----------------
+// node layer `tl` of the slab -> vX, vY (rows g.py apart; 1-D: vY alone): E / rho of the values launch_outputs writes where
+// rho > floor and the quotient is finite, else 0.  rho0 / rho1 / a_prev as for launch_outputs.
+int launch_velocity_layer(const Grid &g, const double *alpha, const double *weight, const double *rho0, const double *rho1,
+                          const double *a_prev, double sig, double cD, bool dim1, i64 tl, double floor, double *vX, double *vY,
+                          hipStream_t st);
+// particles: positions SoA (px along the second array index, py along the first; 1-D: py alone), one sticky flag each
+int launch_advect_seed(bool dim1, i64 n, double *px, double *py, unsigned int *flag, hipStream_t st);     // clamp to [0, 1], flags <- 0
+// the nsub RK4 steps of one time interval between the velocity layers (vX0, vY0) of node k and (vX1, vY1) of node k + 1;
+// dt = dir / ((nt - 1) nsub)
+int launch_advect(bool dim1, i64 ny, i64 nx, i64 py, const double *vX0, const double *vY0, const double *vX1,
+                  const double *vY1, i64 n, int nsub, int dir, double dt, double *px, double *py_, unsigned int *flag,
+                  hipStream_t st);
+int launch_advect_count(const unsigned int *flag, i64 n, unsigned long long *count, hipStream_t st);       // *count += set flags
+
 // ---------------- report.hip: the solution report (mass, negativity, f(q) histograms) in one pass over alpha and q ----------------
 // Slots of the 64-bit counters one report accumulates (device array, zeroed before the launch): the two histograms, three
 // counts, and min(rho) / max(fq) over the finite values as order-preserving integer keys (report_key_decode; 0: no value)

@@ -118,6 +118,10 @@ struct Slab {
     // [ntl][3], the 64-bit counters [RC_COUNT]
     double *rep_edges = nullptr, *rep_part = nullptr, *rep_sums = nullptr;
     unsigned long long *rep_counts = nullptr;
+    // particle transport (advect.hip; allocated at its first use): a ring of two velocity layers, slot (global node & 1) at
+    // adv_vel + 2 * plane * slot = [vX | vY]; adv_have: the global node each slot holds (-1: none)
+    double *adv_vel = nullptr;
+    i64 adv_have[2] = {-1, -1};
 };
 
 // every slab this process holds, with the slab's device made current first (member functions returning int)
@@ -130,7 +134,8 @@ void pencil_range(i64 plane, int world, int j, i64 *l0, i64 *l1);
 bool if_adjust_sigma(double iter, double last_iter);   // IfAdjustSigma (solver_socp_inPALM.m:361-379)
 
 enum Phase { PH_RHS = 0, PH_POISSON, PH_PROJ, PH_QSTEP, PH_BETA, PH_KKT, PH_FUSED_A, PH_FUSED_B, PH_MATERIALISE,
-             PH_COMM, PH_INTERP, PH_ACC_CONE, PH_ACC_GATHER, PH_QSTEP0, PH_TRANSPOSE, PH_CONE_CARRY, PH_QCONE, PH_COUNT };
+             PH_COMM, PH_INTERP, PH_ACC_CONE, PH_ACC_GATHER, PH_QSTEP0, PH_TRANSPOSE, PH_CONE_CARRY, PH_QCONE, PH_VELOCITY, PH_ADVECT,
+             PH_COUNT };
 
 // The schedule of the gamma form (fused.hip, Solver::step): pure host arithmetic, also behind the C ABI.
 // rescale_due: the rescale block of iteration `it` takes its norms or rescales (solver_socp_inPALM.m:138-151), given the
@@ -275,6 +280,13 @@ struct Solver {
     // mass / negativity / f(q) histograms / cost of the finished solve in one pass over alpha and q (report.hip);
     // layer_mass, layer_neg: nt doubles each or NULL
     int solution_report(const double *rho0, const double *rho1, dotsocp_report *rep, double *layer_mass, double *layer_neg);
+    // v = E / rho at the nodes and particles along it (advect.hip).  Coordinates of the engine: X along the second array
+    // index, Y along the first; a 1-D problem lives in Y (capi.hip hands its x over as y).
+    int velocity_stage(const double *rho0, const double *rho1);          // rho0 / rho1 / a_prev in place, rings empty
+    int velocity_layer(Slab &s, i64 tg, double floor);                   // the slab's ring holds global node layer tg
+    int recover_velocity(const double *rho0, const double *rho1, double floor, double *vX, double *vY);
+    int advect_particles(const double *rho0, const double *rho1, const dotsocp_advect_opts *o, double *x, double *y,
+                         double *traj_x, double *traj_y, i64 *n_clamped);
 
     // ================ the inPALM loop and its profiling: solver.hip ================
     // ---- loop state (mirrors solver_socp_inPALM.m:11-135) ----

@@ -143,6 +143,185 @@ int Solver::solution_report(const double *rho0, const double *rho1, dotsocp_repo
     return 0;
 }
 
+// --------------------------------------------------------------------------------------
+// Velocity v = E / rho and particles along it (advect.hip; semantics: include/dotsocp.h).  The velocity exists one node
+// layer at a time: every slab keeps a ring of two layers, slot (global node & 1), filled by k_velocity_layer from the
+// slab's own alpha -- or, for the node behind a slab's last cell, by its right neighbour, which owns that node, and copied
+// over.  Staging as for solution_report: rho0 / rho1 in w1, the left neighbour's last cell through k_out_tail / shift.
+// --------------------------------------------------------------------------------------
+int Solver::velocity_stage(const double *rho0, const double *rho1) {
+    cur_dev = -1;
+    DS_CHECK(use_dev(device));
+    const i64 plane = slabs[0].g.plane, py = slabs[0].g.py;
+    const double cD = cScale * D;                          // recoverOrgVar (solver_dotsocp2d.m:368-386)
+    if (multi()) {
+        FOR_SLABS(s)
+            if (!s.g.last) DS_CHECK(launch_out_tail(s.g, s.alpha, s.weight, sigma, cD, s.send_plane, s.st));
+        DS_CHECK(shift(+1, [](Slab &s) { return s.send_plane; }, [](Slab &s) { return s.a0_prev; }, plane));
+    }
+    FOR_SLABS(s) {
+        if (!s.adv_vel) DS_CHECK(s.zalloc(&s.adv_vel, 4 * plane));
+        s.adv_have[0] = s.adv_have[1] = -1;
+        if (s.g.first) DS_CHECK(copy_rows(s.w1, const_cast<double *>(rho0), ny, py, nx, true, s.st));
+        if (s.g.last) DS_CHECK(copy_rows(s.w1 + plane, const_cast<double *>(rho1), ny, py, nx, true, s.st));
+    }
+    return 0;
+}
+
+int Solver::velocity_layer(Slab &s, i64 tg, double floor) {
+    const int slot = (int)(tg & 1);
+    if (s.adv_have[slot] == tg) return 0;
+    const Grid &g = s.g;
+    const i64 plane = g.plane;
+    double *dst = s.adv_vel + 2 * plane * slot;
+    if (tg >= g.t0 && tg < g.t0 + g.ntl) {
+        DS_CHECK(use(s));
+        const bool prof = &s == &slabs[0];
+        if (prof) prof_begin(PH_VELOCITY);
+        DS_CHECK(launch_velocity_layer(g, s.alpha, s.weight, s.w1, s.w1 + plane, s.a0_prev, sigma, cScale * D, prob.dim == 1,
+                                       tg - g.t0, floor, dst, dst + plane, s.st));
+        if (prof) prof_end(PH_VELOCITY);
+    } else {
+        const size_t r = (size_t)(&s - slabs.data()) + 1;
+        if (tg != g.t0 + g.ntl || r >= slabs.size()) { set_error("internal: velocity layer %lld is not this slab's", tg); return DOTSOCP_ESTATE; }
+        DS_CHECK(velocity_layer(slabs[r], tg, floor));
+        DS_CHECK(xcopy(slabs[r], slabs[r].adv_vel + 2 * plane * slot, s, dst, 2 * plane));
+    }
+    s.adv_have[slot] = tg;
+    return 0;
+}
+
+// the guard bands of DOTSOCP_CANARY=1, checked while the buffers of the call are live
+static int canary_after(Solver &S) {
+    if (!canary_enabled()) return 0;
+    std::string what;
+    const int bad = canary_check(&what);
+    S.cur_dev = -1;
+    if (bad) {
+        set_error("canary: %d device buffer(s) written out of bounds: %s", bad, what.c_str());
+        return DOTSOCP_EHIP;
+    }
+    return 0;
+}
+
+int Solver::recover_velocity(const double *rho0, const double *rho1, double floor, double *vX, double *vY) {
+    DS_ARG(rho0 != nullptr && rho1 != nullptr, "recover_velocity() needs rho0 and rho1 (one of them is NULL)");
+    DS_ARG(!remote(), "recover_velocity() serves the slabs of one process; contexts with an RCCL communicator are not served");
+    if (!finished) { set_error("recover_velocity() needs finish()"); return DOTSOCP_ESTATE; }
+    DS_CHECK(need_beta_form("recover_velocity"));
+    DS_CHECK(velocity_stage(rho0, rho1));
+    const i64 hplane = ny * nx;
+    FOR_SLABS(s) {
+        const Grid &g = s.g;
+        for (i64 tl = 0; tl < g.ntl; ++tl) {
+            const i64 tg = g.t0 + tl;
+            DS_CHECK(velocity_layer(s, tg, floor));
+            double *d = s.adv_vel + 2 * g.plane * (tg & 1);
+            if (vX) DS_CHECK(copy_rows(d, vX + hplane * tg, ny, g.py, nx, false, s.st));
+            if (vY) DS_CHECK(copy_rows(d + g.plane, vY + hplane * tg, ny, g.py, nx, false, s.st));
+        }
+    }
+    DS_CHECK(sync_all());
+    DS_CHECK(prof_flush());
+    return canary_after(*this);
+}
+
+// particle block of one slab: [px (n) | py (n) | flags (n x 32 bit) | count (64 bit)], in doubles
+struct ParticleBlocks {
+    Solver &S;
+    std::vector<double *> bufs;
+    explicit ParticleBlocks(Solver &s) : S(s) {}
+    ~ParticleBlocks() {
+        if (bufs.empty()) return;
+        S.cur_dev = -1;
+        (void)S.sync_all();
+        for (double *b : bufs) dfree(b);
+    }
+};
+
+int Solver::advect_particles(const double *rho0, const double *rho1, const dotsocp_advect_opts *o, double *x, double *y,
+                             double *traj_x, double *traj_y, i64 *n_clamped) {
+    const bool dim1 = prob.dim == 1;
+    DS_ARG(rho0 != nullptr && rho1 != nullptr && o != nullptr && y != nullptr && (dim1 || x != nullptr),
+           "advect_particles() needs rho0, rho1, opts and x (2-D: y too); one of them is NULL");
+    DS_ARG(o->n >= 1, "advect_particles() needs n >= 1 particles");
+    DS_ARG(o->nsub >= 1, "advect_particles() needs nsub >= 1 steps per time interval");
+    DS_ARG(o->direction == 1 || o->direction == -1, "advect_particles() runs in direction +1 or -1");
+    DS_ARG(!remote(), "advect_particles() serves the slabs of one process; contexts with an RCCL communicator are not served");
+    const i64 n = o->n;
+    for (i64 p = 0; p < n; ++p)
+        DS_ARG(std::isfinite(y[p]) && (dim1 || std::isfinite(x[p])), "advect_particles(): a seed is not finite");
+    if (!finished) { set_error("advect_particles() needs finish()"); return DOTSOCP_ESTATE; }
+    DS_CHECK(need_beta_form("advect_particles"));
+    DS_ARG(ny >= 2 && (dim1 || nx >= 2), "advect_particles() needs two nodes along every axis");
+    DS_CHECK(velocity_stage(rho0, rho1));
+    const int dir = o->direction, nsub = o->nsub;
+    const double floor = o->rho_floor;
+    const double dt = (double)dir / (double)((nt - 1) * (i64)nsub);
+    const size_t nb = sizeof(double) * (size_t)n;
+    const i64 nflag = (n + 1) / 2, PB = 2 * n + nflag + 1;
+    ParticleBlocks blocks(*this);
+    FOR_SLABS(s) {
+        double *b = nullptr;
+        DS_CHECK(dmalloc(&b, PB));
+        blocks.bufs.push_back(b);
+    }
+    auto PX = [&](size_t k) { return blocks.bufs[k]; };
+    auto PY = [&](size_t k) { return blocks.bufs[k] + n; };
+    auto FL = [&](size_t k) { return (unsigned int *)(blocks.bufs[k] + 2 * n); };
+    auto CT = [&](size_t k) { return (unsigned long long *)(blocks.bufs[k] + 2 * n + nflag); };
+    // positions of slab `k` -> column `node` of the trajectories
+    auto record = [&](size_t k, i64 node) -> int {
+        if (traj_x && !dim1) DS_HIP(ds_memcpy_async(traj_x + n * node, PX(k), nb, hipMemcpyDeviceToHost, slabs[k].st));
+        if (traj_y) DS_HIP(ds_memcpy_async(traj_y + n * node, PY(k), nb, hipMemcpyDeviceToHost, slabs[k].st));
+        return 0;
+    };
+    size_t cur = dir > 0 ? 0 : slabs.size() - 1;
+    {
+        Slab &s = slabs[cur];
+        DS_CHECK(use(s));
+        DS_HIP(ds_memset_async(PX(cur), 0, sizeof(double) * (size_t)PB, s.st));
+        if (!dim1) DS_HIP(ds_memcpy_async(PX(cur), x, nb, hipMemcpyHostToDevice, s.st));
+        DS_HIP(ds_memcpy_async(PY(cur), y, nb, hipMemcpyHostToDevice, s.st));
+        DS_CHECK(launch_advect_seed(dim1, n, PX(cur), PY(cur), FL(cur), s.st));
+        DS_CHECK(record(cur, dir > 0 ? 0 : nt - 1));
+    }
+    for (i64 step = 0; step < nt - 1; ++step) {
+        const i64 k = dir > 0 ? step : nt - 2 - step;      // the interval between nodes k and k + 1: run by the slab that owns cell k
+        while (k < slabs[cur].g.t0 || k >= slabs[cur].g.t0 + slabs[cur].g.ncl) {
+            const size_t nxt = dir > 0 ? cur + 1 : cur - 1;
+            if (nxt >= slabs.size()) { set_error("internal: no slab owns cell layer %lld", k); return DOTSOCP_ESTATE; }
+            DS_CHECK(xcopy(slabs[cur], PX(cur), slabs[nxt], PX(nxt), PB));
+            cur = nxt;
+        }
+        Slab &s = slabs[cur];
+        DS_CHECK(velocity_layer(s, k, floor));
+        DS_CHECK(velocity_layer(s, k + 1, floor));
+        DS_CHECK(use(s));
+        const double *L0 = s.adv_vel + 2 * s.g.plane * (k & 1), *L1 = s.adv_vel + 2 * s.g.plane * ((k + 1) & 1);
+        const bool prof = cur == 0;
+        if (prof) prof_begin(PH_ADVECT);
+        DS_CHECK(launch_advect(dim1, ny, nx, s.g.py, L0, L0 + s.g.plane, L1, L1 + s.g.plane, n, nsub, dir, dt, PX(cur), PY(cur),
+                               FL(cur), s.st));
+        if (prof) prof_end(PH_ADVECT);
+        DS_CHECK(record(cur, dir > 0 ? k + 1 : k));
+    }
+    unsigned long long count = 0;
+    {
+        Slab &s = slabs[cur];
+        DS_CHECK(use(s));
+        DS_CHECK(launch_advect_count(FL(cur), n, CT(cur), s.st));
+        if (!dim1) DS_HIP(ds_memcpy_async(x, PX(cur), nb, hipMemcpyDeviceToHost, s.st));
+        DS_HIP(ds_memcpy_async(y, PY(cur), nb, hipMemcpyDeviceToHost, s.st));
+        DS_HIP(ds_memcpy_async(&count, CT(cur), sizeof count, hipMemcpyDeviceToHost, s.st));
+    }
+    DS_CHECK(sync_all());
+    DS_CHECK(prof_flush());
+    DS_CHECK(canary_after(*this));
+    if (n_clamped) *n_clamped = (i64)count;
+    return 0;
+}
+
 // jump_nextLevel.m:5-16: this = fine level (created, c / weight uploaded, begin() not yet called),
 // `coarse` = the finished coarse level.  Both may be cut into in-process time slabs (any numbers of slabs, any
 // placement on devices): a fine slab interpolates from the coarse layers it needs -- nodes floor(t/2) and, for odd

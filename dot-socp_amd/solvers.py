@@ -218,6 +218,48 @@ class InPALMContext:
                                                       capi.fptr(mass), capi.fptr(neg)))
         return from_struct(rep, mass, neg)
 
+    def _rho_floor(self, rho_floor):
+        from .advect import default_rho_floor
+        return default_rho_floor(self.model.rho0, self.model.rho1) if rho_floor is None else float(rho_floor)
+
+    def velocity(self, rho_floor=None):
+        """v = E / rho at the nodes on the device (dotsocp_recover_velocity; advect.py): dict(vx[, vy]) of the shapes of
+        outputs()["rho"]; zero where rho <= rho_floor (None: advect.default_rho_floor(rho0, rho1)) or the quotient is not
+        finite.  Call after finish(); same bits as advect.velocity(self.outputs(), rho_floor)."""
+        m = self.model
+        one_d = not hasattr(m, "ny")
+        shp = ((int(m.nx),) if one_d else (int(m.ny), int(m.nx))) + (int(m.nt),)
+        v = {k: np.empty(shp, order="F") for k in (("vx",) if one_d else ("vx", "vy"))}
+        r0, r1 = self._rho_ends()
+        capi.check(capi.lib().dotsocp_recover_velocity(self._ctx, capi.fptr(r0), capi.fptr(r1), self._rho_floor(rho_floor),
+                                                       capi.fptr(v["vx"]), None if one_d else capi.fptr(v["vy"])))
+        return v
+
+    def advect(self, x, y=None, nsub=1, direction=+1, rho_floor=None, trajectories=False):
+        """Particles along the solved flow on the device (dotsocp_advect_particles; advect.py): RK4 along v = E / rho from
+        the seeds x, y (y None on a 1-D context) over t = 0 -> 1 (direction=+1) or 1 -> 0 (-1), nsub steps per time
+        interval.  Returns dict(x, y, traj_x, traj_y, n_clamped) as advect.advect does, with the same bits as
+        advect.advect(self.outputs(), ...).  Call after finish()."""
+        m = self.model
+        one_d = not hasattr(m, "ny")
+        if one_d != (y is None):
+            raise ValueError("advect(): y is given on a 2-D context and only there")
+        px = np.array(x, dtype=np.float64).ravel()
+        py = None if one_d else np.array(y, dtype=np.float64).ravel()
+        if py is not None and py.size != px.size:
+            raise ValueError("advect(): x and y hold the same number of seeds")
+        o = capi.AdvectOpts()
+        o.n, o.nsub, o.direction, o.rho_floor = int(px.size), int(nsub), int(direction), self._rho_floor(rho_floor)
+        nt = int(m.nt)
+        tx = np.empty((px.size, nt), order="F") if trajectories else None
+        ty = np.empty((px.size, nt), order="F") if trajectories and not one_d else None
+        ptr = lambda a: None if a is None else capi.fptr(a)                 # noqa: E731
+        r0, r1 = self._rho_ends()
+        nc = capi.i64()
+        capi.check(capi.lib().dotsocp_advect_particles(self._ctx, capi.fptr(r0), capi.fptr(r1), ctypes.byref(o), ptr(px), ptr(py),
+                                                       ptr(tx), ptr(ty), ctypes.byref(nc)))
+        return dict(x=px, y=py, traj_x=tx, traj_y=ty, n_clamped=int(nc.value))
+
     def close(self):
         if getattr(self, "_ctx", None):
             capi.lib().dotsocp_destroy(self._ctx)
@@ -313,7 +355,7 @@ def _weights_mode(weight, weights, transfer, weighted=True):
 
 
 def _solve_levels(rho0, rho1, nt, levelN, opts, method, dim, weighted, device, barrier=None, transfer="device",
-                  weights=None, report=False):
+                  weights=None, report=False, advect=None):
     """The level loop of solver_dotsocp2d.m:154-250 (dot1d / wdot2d twins): restrict the data to
     levelN grids, solve coarse to fine with warm starts; every solve runs on the device.
     transfer = "device": the state never leaves the GPU -- jump_nextLevel and the output recovery run there
@@ -326,7 +368,10 @@ def _solve_levels(rho0, rho1, nt, levelN, opts, method, dim, weighted, device, b
     transfer="device".  None: "device" for a SpaceWeight with transfer="device", else "host" (a SpaceWeight is then
     expanded on the host).
     report = True: the last level's context is asked for its solution report (InPALMContext.report(), report.py) before it
-    is closed; output["report"] holds it.  Needs transfer="device"."""
+    is closed; output["report"] holds it.  Needs transfer="device".
+    advect = dict(x=..., y=..., nsub=..., direction=..., rho_floor=..., trajectories=...): the keyword arguments of
+    InPALMContext.advect(), which is asked of the last level's context in the same way; output["advect"] holds its
+    result.  Needs transfer="device"."""
     from . import multilevel as ML
     from .examples import ensure_barrier_validity
     if not (isinstance(levelN, (int, np.integer)) and levelN >= 1):
@@ -335,6 +380,8 @@ def _solve_levels(rho0, rho1, nt, levelN, opts, method, dim, weighted, device, b
         raise ValueError("transfer must be 'device' or 'host'")
     if report and transfer != "device":
         raise ValueError("report=True needs transfer='device' (the report is taken from the device-resident state)")
+    if advect is not None and transfer != "device":
+        raise ValueError("advect= needs transfer='device' (the particles move through the device-resident state)")
     wopt = _get(opts, "weight") if weighted else None
     weights = _weights_mode(wopt, weights, transfer, weighted)
     wdev = weights == "device"
@@ -415,6 +462,8 @@ def _solve_levels(rho0, rho1, nt, levelN, opts, method, dim, weighted, device, b
                 output = ctx.outputs()
                 if report:
                     output["report"] = ctx.report()
+                if advect is not None:
+                    output["advect"] = ctx.advect(**advect)
             if not on_device:
                 ctx.close()
                 recoverOrgVar(var)
@@ -449,31 +498,35 @@ def _solve_levels(rho0, rho1, nt, levelN, opts, method, dim, weighted, device, b
     return output, timeML, runHistML, runHist
 
 
-def solver_dotsocp2d(rho0, rho1, nt, levelN, opts, method="inPALM", device=0, transfer="device", report=False):
+def solver_dotsocp2d(rho0, rho1, nt, levelN, opts, method="inPALM", device=0, transfer="device", report=False,
+                     advect=None):
     """[output, timeML, runHistML, runHist] = solver_dotsocp2d(rho0, rho1, nt, levelN, opts, method)
-    socp/dot2d/solver_dotsocp2d.m:1.  report=True: output["report"] = the device-side solution report (_solve_levels)."""
+    socp/dot2d/solver_dotsocp2d.m:1.  report=True: output["report"] = the device-side solution report; advect=dict(x=..., y=...,
+    ...): output["advect"] = the particles carried along the solved flow (both: _solve_levels)."""
     output, timeML, runHistML, runHist = _solve_levels(rho0, rho1, nt, levelN, opts, method, 2, False, device,
-                                                       transfer=transfer, report=report)
+                                                       transfer=transfer, report=report, advect=advect)
     if not check_massConservation(output["rho"], 1e-2):
         print("Warning: The mass conservation constraint violation exceeds 0.01")
     return output, timeML, runHistML, runHist
 
 
-def solver_dotsocp1d(rho0, rho1, nt, levelN, opts, method="inPALM", device=0, transfer="device", report=False):
-    """socp/dot1d/solver_dotsocp1d.m:1.  report: as for solver_dotsocp2d."""
+def solver_dotsocp1d(rho0, rho1, nt, levelN, opts, method="inPALM", device=0, transfer="device", report=False,
+                     advect=None):
+    """socp/dot1d/solver_dotsocp1d.m:1.  report, advect: as for solver_dotsocp2d."""
     output, timeML, runHistML, runHist = _solve_levels(rho0, rho1, nt, levelN, opts, method, 1, False, device,
-                                                       transfer=transfer, report=report)
+                                                       transfer=transfer, report=report, advect=advect)
     if not check_massConservation(output["rho"], 1e-2):
         print("Warning: The mass conservation constraint violation exceeds 0.01")
     return output, timeML, runHistML, runHist
 
 
 def solver_wdotsocp2d(rho0, rho1, nt, levelN, opts, method="inPALM", barrier=None, device=0, transfer="device",
-                      weights=None, report=False):
+                      weights=None, report=False, advect=None):
     """socp/wdot2d/solver_wdotsocp2d.m:1.  opts["weight"]: the Nq array, or a SpaceWeight (examples.py); weights:
-    where the levels' weights are made, "host" or "device" (_solve_levels); report: as for solver_dotsocp2d."""
+    where the levels' weights are made, "host" or "device" (_solve_levels); report, advect: as for solver_dotsocp2d."""
     output, timeML, runHistML, runHist = _solve_levels(rho0, rho1, nt, levelN, opts, method, 2, True, device,
-                                                       barrier=barrier, transfer=transfer, weights=weights, report=report)
+                                                       barrier=barrier, transfer=transfer, weights=weights, report=report,
+                                                       advect=advect)
     if not check_massConservation(output["rho"], 1e-2):
         print("Warning: The tolerance of mass conservation constraint is under 0.01")
     return output, timeML, runHistML, runHist

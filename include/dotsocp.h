@@ -329,6 +329,50 @@ int dotsocp_report_edges(double edges[DOTSOCP_REPORT_BINS + 1]);
 int dotsocp_solution_report(dotsocp_ctx *ctx, const double *rho0, const double *rho1, dotsocp_report *rep,
                             double *layer_mass /* nt or NULL */, double *layer_neg /* nt or NULL */);
 
+/* Where the mass goes: the velocity v = E / rho of the solved flow (the arrows of utils/show_movement_2d.m:31-40, masked
+ * where rho is small) and particles carried along it -- the transport (Monge) map -- from the device-resident alpha.
+ *
+ * Inputs.  rho, Ex, Ey at the nodes (y, x, t) are the values dotsocp_recover_outputs writes, bit for bit (weight of
+ *   wdot2d, rho0 / rho1 on the first / last layer included).
+ * Coordinates.  Unit square, t in [0, 1].  x in [0, 1] runs along the SECOND array index (nx columns, node i at
+ *   i / (nx - 1)), y along the first (ny rows); Ex is the x component; E = +rho v; v in domain lengths per unit time.
+ * Velocity at a node.  ok = rho > rho_floor;  qx = Ex / rho;  vx = (ok && isfinite(qx)) ? qx : 0;  vy likewise: the
+ *   field is finite everywhere, a NaN density gives v = 0.
+ * Interpolation (clamp(u): u < 0 -> 0, u > 1 -> 1).  fx = x * (double)(nx - 1);  i = min((i64)floor(fx), nx - 2);
+ *   a = fx - (double)i;  fy, j, c likewise with ny.  In one layer F:
+ *       f0 = (1 - c) * F[j, i] + c * F[j + 1, i];   f1 = (1 - c) * F[j, i + 1] + c * F[j + 1, i + 1];
+ *       lay = (1 - a) * f0 + a * f1
+ *   and between the layers k, k + 1 of a time interval  v = (1 - b) * lay_k + b * lay_{k+1}  (both always evaluated).
+ *   1-D drops y, j, c: lay = (1 - a) * F[i] + a * F[i + 1].
+ * Integration.  Classical RK4, nsub >= 1 steps per time interval;  dt = dir / (double)((nt - 1) * nsub), hh = 0.5 * dt,
+ *   h6 = dt / 6.0.  Forward (dir = +1): interval k = 0 .. nt - 2, sub-step s = 0 .. nsub - 1, stage fractions
+ *   b = (double)(2 s + m) / (double)(2 nsub), m = 0, 1, 1, 2.  Backward (dir = -1): intervals nt - 2 down to 0, each
+ *   entered at node k + 1, b = (double)(2 (nsub - s) - m) / (double)(2 nsub).
+ *       k1 = v(x, y; b0)
+ *       k2 = v(clamp(x + hh * k1x), clamp(y + hh * k1y); b1)
+ *       k3 = v(clamp(x + hh * k2x), clamp(y + hh * k2y); b1)
+ *       k4 = v(clamp(x + dt * k3x), clamp(y + dt * k3y); b2)
+ *       x  = clamp(x + h6 * (((k1x + 2 * k2x) + 2 * k3x) + k4x))          (y likewise)
+ *   Seeds outside [0, 1] are clamped before the first step; a non-finite seed is DOTSOCP_EINVAL.  n_clamped counts the
+ *   particles for which the clamp at the END of some step changed a coordinate, each once.
+ * The kernels are built without contraction of a * b + c, so a restatement of the above in IEEE doubles (advect.py)
+ * gives the same bits.
+ *
+ * Both calls: after finish() (DOTSOCP_ESTATE before); inPALM / ALG2, PALM, acc-ADMM, weighted and 1-D contexts; one
+ * slab, `nslabs` slabs and dotsocp_create_multi (the slab that owns cell layer k runs interval k, the particles travel
+ * from slab to slab).  DOTSOCP_EINVAL: a NULL rho0 / rho1 / o / x, a NULL y on a 2-D context, n < 1, nsub < 1, a
+ * direction other than +1 / -1, a context with an RCCL communicator attached. */
+/* v = E / rho at the nodes; host arrays ny x nx x nt (1-D: nx x nt, vy ignored); either may be NULL */
+int dotsocp_recover_velocity(dotsocp_ctx *ctx, const double *rho0, const double *rho1, double rho_floor,
+                             double *vx, double *vy);
+
+typedef struct { dotsocp_i64 n; int nsub; int direction; double rho_floor; } dotsocp_advect_opts;
+/* x, y (n doubles, in: seeds, out: positions at t = 1, or t = 0 for direction -1; y NULL for 1-D);
+ * traj_x / traj_y: n x nt column-major, position at every time NODE, indexed by node in both directions, or NULL;
+ * n_clamped may be NULL */
+int dotsocp_advect_particles(dotsocp_ctx *ctx, const double *rho0, const double *rho1, const dotsocp_advect_opts *o,
+                             double *x, double *y, double *traj_x, double *traj_y, dotsocp_i64 *n_clamped);
+
 /* Multilevel transfer on the device: socp/dot2d/utils/jump_nextLevel.m:5-16 with
  * interpolate.m:20-84, between the finished context `coarse` and the context `fine` of the next level (created
  * from the fine level's InitialScaling scalars, c and weight uploaded, begin() not yet called; grid
@@ -391,7 +435,8 @@ int dotsocp_get_history(dotsocp_ctx *ctx, double *kkt, double *time, double *ite
  * begin(), and their count; names: "rhs", "poisson", "cone_proj", "qstep", "beta", "kkt", "cone_fused_a",
  * "cone_fused_b", "materialise", "comm", "interp", "acc_cone", "acc_gather", "qstep_first", "transpose", "cone_carry"
  * (the cone passes that read gamma and no q^{k-1}; "cone_fused_b" keeps the passes that move 8 (20 Nz + 3 Nq) bytes),
- * "qcone" (a q-step with the next iteration's gamma-reading cone pass in the same kernel: counted here alone). */
+ * "qcone" (a q-step with the next iteration's gamma-reading cone pass in the same kernel: counted here alone),
+ * "velocity_layer", "advect" (the launches of dotsocp_recover_velocity / dotsocp_advect_particles on the first slab). */
 int dotsocp_set_profiling(dotsocp_ctx *ctx, int on);
 int dotsocp_kernel_time(dotsocp_ctx *ctx, const char *name, double *avg_ms, dotsocp_i64 *launches);
 

@@ -6,7 +6,10 @@ The two Gaussians are equal and their centres (0.25, 0.75) and (0.75, 0.25) -- a
 (+0.5, -0.5) apart in (y, x).  On the whole plane the map would be that translation; these Gaussians are wide (variance
 0.05: a standard deviation of 0.22) and cut off by the unit square, so only the mass near the centre moves by nearly that
 much, and a particle in the far corner has nowhere to go.  Printed: the deviation of the displacement from (+0.5, -0.5)
-over all particles, weighted by the mass rho0 they stand for, and over the seeds within 0.1 of the start centre."""
+over all particles, weighted by the mass rho0 they stand for, and over the seeds within 0.1 of the start centre.
+After the particles, the mass itself (push= of the drivers): rho0 carried by a particle on every node and deposited on the
+grid -- the displacement interpolant next to the Eulerian rho layers -- with its mean distance l1 to rho at t = 1 (the
+defect of the map) and half-way, and the check that every frame holds exactly the same number of mass units."""
 import os
 import sys
 
@@ -20,7 +23,8 @@ rho0, rho1 = D.get_example_2d("example1", nx, nx)
 floor = D.default_rho_floor(rho0, rho1)
 x0, y0 = D.seeds_on_nodes(nx, nx, stride=4, mask=rho0 > floor)
 output, timeML, runHistML, runHist = D.solver_dotsocp2d(rho0, rho1, nt, levelN, dict(tol=tol, maxit=3000), "inPALM",
-                                                        advect=dict(x=x0, y=y0, nsub=2, trajectories=True))
+                                                        advect=dict(x=x0, y=y0, nsub=2, trajectories=True),
+                                                        push=dict(stride=1, frames=[0, nt // 2, nt - 1], nsub=2))
 adv = output["advect"]
 dev = np.hypot(adv["x"] - x0 - (-0.5), adv["y"] - y0 - 0.5)
 print(f"{x0.size} particles (every 4th node with rho0 > {floor:.3g}), {adv['n_clamped']} clamped at the boundary")
@@ -35,3 +39,10 @@ print(f"half-way (node {mid}): mean position (y, x) = ({adv['traj_y'][:, mid].me
 # and back: the particles at t = 1 return to their seeds along the same flow
 back = D.advect.advect({k: output[k] for k in ("rho", "Ex", "Ey")}, adv["x"], adv["y"], nsub=2, direction=-1)
 print(f"there and back (host twin, direction -1): worst distance from the seeds {np.hypot(back['x'] - x0, back['y'] - y0).max():.2e}")
+# the mass itself: rho0 pushed along the flow and deposited on the grid
+push = output["push"]
+print(f"pushed rho0 ({push['x'].size} particles, {push['n_clamped']} clamped): l1 against rho at t = 1: {push['l1'][-1]:.4e}, "
+      f"at the middle frame (node {push['nodes'][1]}): {push['l1'][1]:.4e} (mean density 1)")
+units = push["counts"].sum(axis=(0, 1))
+print(f"units of 2^{int(np.log2(push['unit']))} per frame: {units.tolist()}; all equal to the particles' {push['total_units']}: "
+      f"{bool(np.all(units == push['total_units']))}")

@@ -4,10 +4,15 @@ Host twins (numpy) of dotsocp_recover_velocity and dotsocp_advect_particles (inc
 csrc/advect.hip and this module follow them operation by operation -- no fused multiply-add on either side -- so
 InPALMContext.velocity() / .advect() and velocity(ctx.outputs(), floor) / advect(ctx.outputs(), ...) agree bit for bit).
 The velocity is the one utils/show_movement_2d.m draws: arrows of E, masked where rho is small.
+push_forward is the twin of dotsocp_push_mass: the masses the particles carry, deposited on the grid at chosen time nodes
+in whole units (int64 planes, np.add.at), so that every frame conserves the mass exactly and no bit depends on the order
+of the particles; InPALMContext.push_forward() returns the same bits.
 
 Coordinates: the unit square and t in [0, 1]; x runs along the SECOND array index of the outputs (nx columns, node i at
 i / (nx - 1)), y along the first (ny rows); 1-D outputs (nx, nt) have x alone.  E = +rho v.
 """
+import math
+
 import numpy as np
 
 
@@ -127,6 +132,92 @@ def advect(out, x, y=None, nsub=1, direction=+1, rho_floor=None, trajectories=Fa
                 y = _clamp(uy)
         record(k + 1 if direction > 0 else k)
     return dict(x=x, y=y, traj_x=tx, traj_y=ty, n_clamped=int(np.count_nonzero(moved)))
+
+
+def mass_unit(n, mass_max):
+    """The unit of dotsocp_push_mass: 2^(e - 50) with frexp(n * mass_max) = (f, e), so that n particles of at most
+    mass_max stay below 2^51 units in total."""
+    top = float(n) * float(mass_max)
+    if not (math.isfinite(top) and top > 0.0):
+        raise ValueError("push_forward(): n * max(mass) must be positive and finite")
+    unit = math.ldexp(1.0, math.frexp(top)[1] - 50)
+    if unit < 2.2250738585072014e-308:
+        raise ValueError("push_forward(): the unit 2^(e-50) of n * max(mass) is not a normal double")
+    return unit
+
+
+def _deposit(counts, x, y, M):
+    """counts (int64 plane) += the bilinear split of the units M of the particles at (x, y): three corners rounded half
+    to even, the fourth takes the remainder (include/dotsocp.h)"""
+    Md = M.astype(np.float64)
+    rnd = lambda w: np.rint(w * Md).astype(np.int64)                        # noqa: E731
+    if y is None:
+        i, a = _cell(x, counts.shape[0])
+        d0 = rnd(1.0 - a)
+        np.add.at(counts, i, d0)
+        np.add.at(counts, i + 1, M - d0)
+        return
+    i, a = _cell(x, counts.shape[1])
+    j, c = _cell(y, counts.shape[0])
+    d00, d10, d01 = rnd((1.0 - c) * (1.0 - a)), rnd(c * (1.0 - a)), rnd((1.0 - c) * a)
+    np.add.at(counts, (j, i), d00)
+    np.add.at(counts, (j + 1, i), d10)
+    np.add.at(counts, (j, i + 1), d01)
+    np.add.at(counts, (j + 1, i + 1), M - d00 - d10 - d01)
+
+
+def push_forward(out, x, y=None, mass=None, frames=None, nsub=1, direction=+1, rho_floor=None, unit=None):
+    """Twin of dotsocp_push_mass on the outputs dict: the particles of advect() carry `mass` (n values, finite, >= 0, not
+    all zero) and deposit it at the time nodes `frames` (strictly ascending indices; None: every node) by integer
+    accumulation -- exact conservation, no dependence on the particle order (include/dotsocp.h).  unit (twin only): a
+    unit fixed by the caller, mass_unit(n, max) of a larger particle set this call deposits a part of.  Returns
+    dict(frames, counts, nodes, unit, l1, x, y, n_clamped, total_units): frames (ny, nx, nf) (1-D: (nx, nf)) =
+    counts * unit, counts the signed int64 planes, l1[k] = mean |frames[..., k] - rho[..., nodes[k]]|, final positions and
+    n_clamped as advect() returns them, total_units = sum of the particles' units = counts[..., k].sum() for every k."""
+    rho = np.asarray(out["rho"], dtype=np.float64)
+    one_d = "Ey" not in out
+    nt = rho.shape[-1]
+    if mass is None:
+        raise ValueError("push_forward(): mass is needed")
+    mass = np.array(mass, dtype=np.float64).ravel()
+    n = np.asarray(x).size
+    if mass.size != n:
+        raise ValueError("push_forward(): one mass per seed")
+    if not np.all(np.isfinite(mass)) or np.any(mass < 0.0):
+        raise ValueError("push_forward(): a mass is negative or not finite")
+    if not np.any(mass > 0.0):
+        raise ValueError("push_forward(): all masses are zero")
+    nodes = np.arange(nt, dtype=np.int64) if frames is None else np.array(frames, dtype=np.int64).ravel()
+    if nodes.size < 1 or nodes[0] < 0 or nodes[-1] >= nt or np.any(np.diff(nodes) <= 0):
+        raise ValueError("push_forward(): frames must be strictly ascending node indices in [0, nt)")
+    unit = mass_unit(n, mass.max()) if unit is None else float(unit)
+    M = np.rint(mass / unit).astype(np.int64)
+    adv = advect(out, x, y, nsub=nsub, direction=direction, rho_floor=rho_floor, trajectories=True)
+    counts = np.zeros(rho.shape[:-1] + (nodes.size,), dtype=np.int64, order="F")
+    for k, node in enumerate(nodes):
+        plane = np.zeros(rho.shape[:-1], dtype=np.int64)
+        _deposit(plane, adv["traj_x"][:, node], None if one_d else adv["traj_y"][:, node], M)
+        counts[..., k] = plane
+    fr = np.asfortranarray(counts.astype(np.float64) * unit)
+    l1 = np.array([np.mean(np.abs(fr[..., k] - rho[..., node])) for k, node in enumerate(nodes)])
+    return dict(frames=fr, counts=counts, nodes=nodes, unit=unit, l1=l1, x=adv["x"], y=adv["y"], n_clamped=adv["n_clamped"],
+                total_units=int(M.sum()))
+
+
+def masses_on_nodes(rho, stride=1, mask=None):
+    """The companion of seeds_on_nodes: the values of a 2-D (ny, nx) or 1-D (nx,) density at the same nodes, in the same
+    order -- the masses of the particles seeded there."""
+    rho = np.asarray(rho, dtype=np.float64)
+    if rho.ndim == 1:
+        i = np.arange(0, rho.shape[0], int(stride))
+        keep = np.ones(i.size, dtype=bool) if mask is None else np.asarray(mask, dtype=bool)[i]
+        return rho[i][keep]
+    j = np.arange(0, rho.shape[0], int(stride))
+    i = np.arange(0, rho.shape[1], int(stride))
+    jj, ii = np.meshgrid(j, i, indexing="ij")
+    jj, ii = jj.ravel(order="F"), ii.ravel(order="F")
+    keep = np.ones(jj.size, dtype=bool) if mask is None else np.asarray(mask, dtype=bool)[jj, ii]
+    return rho[jj, ii][keep]
 
 
 def seeds_on_nodes(nx, ny=None, stride=1, mask=None):

@@ -62,6 +62,11 @@ class AdvectOpts(ctypes.Structure):
     _fields_ = [("n", i64), ("nsub", ctypes.c_int), ("direction", ctypes.c_int), ("rho_floor", dbl)]
 
 
+class PushOpts(ctypes.Structure):
+    """dotsocp_push_opts"""
+    _fields_ = [("n", i64), ("nsub", ctypes.c_int), ("direction", ctypes.c_int), ("rho_floor", dbl), ("nf", i64)]
+
+
 METHOD_INPALM, METHOD_PALM, METHOD_ACCADMM = 0, 1, 2
 
 
@@ -108,6 +113,8 @@ SYMBOLS = {
     "dotsocp_solution_report": (ctypes.c_int, [vp, vp, vp, ctypes.POINTER(Report), vp, vp]),
     "dotsocp_recover_velocity": (ctypes.c_int, [vp, vp, vp, dbl, vp, vp]),
     "dotsocp_advect_particles": (ctypes.c_int, [vp, vp, vp, ctypes.POINTER(AdvectOpts), vp, vp, vp, vp, ctypes.POINTER(i64)]),
+    "dotsocp_push_mass": (ctypes.c_int, [vp, vp, vp, ctypes.POINTER(PushOpts), vp, vp, vp, vp, vp, ctypes.POINTER(i64),
+                                         ctypes.POINTER(dbl), vp]),
     "dotsocp_jump_next_level": (ctypes.c_int, [vp, vp]),
     "dotsocp_finish": (ctypes.c_int, [vp, ctypes.POINTER(Result)]),
     "dotsocp_get_history": (ctypes.c_int, [vp, vp, vp, vp, vp]),

@@ -1,12 +1,15 @@
 // Particle transport along the solved flow: the velocity v = E / rho of the Benamou-Brenier solution at the nodes
 // (the arrows of utils/show_movement_2d.m, without the plot) and its characteristics, the Monge map, by classical RK4.
-// Semantics: include/dotsocp.h (dotsocp_recover_velocity, dotsocp_advect_particles); the numpy twin dot-socp_amd/advect.py
+// Semantics: include/dotsocp.h (dotsocp_recover_velocity, dotsocp_advect_particles, dotsocp_push_mass); the numpy twin dot-socp_amd/advect.py
 // follows the kernels below operation by operation, and this file is built without contraction (Makefile), so the two
 // agree bit for bit.
 //   k_velocity_layer  one node layer of (vX, vY) from alpha: rho, Ex, Ey are the expressions of outputs_node.h, i.e. the
 //                     bits dotsocp_recover_outputs writes; no grid-sized velocity array is ever made
 //   k_advect          one thread per particle, one launch per time interval: all nsub RK4 steps with the position in
 //                     registers; every stage gathers 4 corners x 2 layers x 2 components from the two layers of the interval
+//   k_deposit         one thread per particle, once per requested frame: the particle's mass units split over the corners of
+//                     its cell and added to a plane of 64-bit counts by four returnless integer atomics
+//   k_frame_l1        counts -> frame (in place) and the tile sums of |frame - rho| against the node layer, in the report's order
 // Index conventions as everywhere: y fastest (rows `py` apart); X = the component / coordinate along the second array
 // index, Y = along the first.  1-D problems live in the Y slot (ny = nx1d, nx = 1): their kernels touch Y alone.
 #include "device_utils.h"
@@ -197,6 +200,103 @@ int launch_advect_count(const unsigned int *flag, i64 n, unsigned long long *cou
     DS_KLAUNCH(k_advect_count, dim3((unsigned)launch_blocks(n, ADV_BLOCK, 1024)), dim3(ADV_BLOCK), 0, st, flag, n, count);
     DS_HIP(hipGetLastError());
     return 0;
+}
+
+// ---------------------------------------------------------------------------------------
+// mass carried by the particles (dotsocp_push_mass): bilinear deposit in integer units, frame and its distance to rho
+// ---------------------------------------------------------------------------------------
+// One thread per particle: its M units are split over the corners of its cell -- the cell and the weights of adv_cell, as the
+// velocity interpolation takes them -- by round-to-nearest-even of weight * M on three corners and the remainder on the
+// fourth, and added with returnless 64-bit integer atomics (two's complement: a remainder of -1 wraps exactly).  Integer
+// sums know no order, so neither the particle order nor the launch shape nor the slab split shows in a bit.  Particles in
+// grid order (seeds_on_nodes) put the lanes of a wavefront on contiguous row segments of the plane.
+template <int DIM>
+__global__ void __launch_bounds__(ADV_BLOCK) k_deposit(i64 n, const double *__restrict__ px, const double *__restrict__ py_,
+                                                      const i64 *__restrict__ units, i64 ny, i64 nx, i64 py,
+                                                      unsigned long long *__restrict__ cnt) {
+    const i64 p = (i64)blockIdx.x * ADV_BLOCK + threadIdx.x;
+    if (p >= n) return;
+    const i64 M = units[p];
+    if (M == 0) return;
+    const double Md = (double)M;
+    i64 j;
+    double c;
+    adv_cell(py_[p], ny, j, c);
+    if (j < 0) j = 0;               // positions are finite and in [0, 1]; whatever else arrives stays inside the plane
+    if (DIM == 1) {
+        const i64 d0 = __double2ll_rn((1.0 - c) * Md);
+        atomicAdd(cnt + j, (unsigned long long)d0);
+        atomicAdd(cnt + j + 1, (unsigned long long)(M - d0));
+        return;
+    }
+    i64 i;
+    double a;
+    adv_cell(px[p], nx, i, a);
+    if (i < 0) i = 0;
+    const i64 d00 = __double2ll_rn(((1.0 - c) * (1.0 - a)) * Md);
+    const i64 d10 = __double2ll_rn((c * (1.0 - a)) * Md);
+    const i64 d01 = __double2ll_rn(((1.0 - c) * a) * Md);
+    const i64 d11 = M - d00 - d10 - d01;
+    unsigned long long *q = cnt + j + py * i;
+    atomicAdd(q, (unsigned long long)d00);
+    atomicAdd(q + 1, (unsigned long long)d10);
+    atomicAdd(q + py, (unsigned long long)d01);
+    atomicAdd(q + py + 1, (unsigned long long)d11);
+}
+
+int launch_deposit(bool dim1, i64 ny, i64 nx, i64 py, i64 n, const double *px, const double *py_, const i64 *units,
+                   unsigned long long *cnt, hipStream_t st) {
+    if (n <= 0) return 0;
+    const dim3 grid((unsigned)launch_blocks(n, ADV_BLOCK, (i64)1 << 30));
+    if (dim1) DS_KLAUNCH(k_deposit<1>, grid, dim3(ADV_BLOCK), 0, st, n, px, py_, units, ny, nx, py, cnt);
+    else DS_KLAUNCH(k_deposit<2>, grid, dim3(ADV_BLOCK), 0, st, n, px, py_, units, ny, nx, py, cnt);
+    DS_HIP(hipGetLastError());
+    return 0;
+}
+
+// counts -> frame = (double)count * unit, in place, and the tile sums of |frame - rho| against node layer `tl` of the slab:
+// rho as k_velocity_layer forms it, tiles and the order of the additions as k_report's layer sums (lanes, then wavefronts;
+// launch_report_rows adds the tiles), so the sum depends on (ny, nx) alone
+template <bool WEIGHTED>
+__global__ void __launch_bounds__(TILE_Y *TILE_X) k_frame_l1(Grid g, OutArgs o, i64 tl, double unit, double *__restrict__ frame,
+                                                              double *__restrict__ partials) {
+    __shared__ double s_red[TILE_X];
+    const int lane = threadIdx.x, xl = threadIdx.y;
+    const i64 y = (i64)blockIdx.x * TILE_Y + lane;
+    const i64 x = (i64)blockIdx.y * TILE_X + xl;
+    double v = 0.0;
+    if (y < g.ny && x < g.nx) {
+        const i64 tg = g.t0 + tl, col = y + g.py * x, node = col + g.plane * tl;
+        double rho;
+        if (tg == 0) rho = o.rho0[col];
+        else if (tg == g.nt - 1) rho = o.rho1[col];
+        else rho = out_mean2(tl == 0 ? o.a_prev[col] : vel_a<WEIGHTED>(o, node - g.plane), vel_a<WEIGHTED>(o, node));
+        const double f = (double)__double_as_longlong(frame[col]) * unit;
+        frame[col] = f;
+        v = fabs(f - rho);
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off, 64);
+    if (lane == 0) s_red[xl] = v;
+    __syncthreads();
+    if (lane == 0 && xl == 0) {
+        double s = s_red[0];
+#pragma unroll
+        for (int wv = 1; wv < TILE_X; ++wv) s += s_red[wv];
+        partials[blockIdx.x + (i64)gridDim.x * blockIdx.y] = s;
+    }
+}
+
+int launch_frame_l1(const Grid &g, const double *alpha, const double *weight, const double *rho0, const double *rho1,
+                    const double *a_prev, double sig, double cD, i64 tl, double unit, double *frame, double *partials,
+                    double *sum, hipStream_t st) {
+    if (tl < 0 || tl >= g.ntl) { set_error("internal: frame layer outside its slab"); return DOTSOCP_ESTATE; }
+    OutArgs o{nullptr, alpha, weight, rho0, rho1, a_prev, sig, cD, 0.0};
+    dim3 grid((unsigned)((g.ny + TILE_Y - 1) / TILE_Y), (unsigned)((g.nx + TILE_X - 1) / TILE_X), 1), block(TILE_Y, TILE_X);
+    if (weight) DS_KLAUNCH(k_frame_l1<true>, grid, block, 0, st, g, o, tl, unit, frame, partials);
+    else DS_KLAUNCH(k_frame_l1<false>, grid, block, 0, st, g, o, tl, unit, frame, partials);
+    DS_HIP(hipGetLastError());
+    return launch_report_rows(partials, report_tiles(g), 1, sum, st);
 }
 
 }  // namespace dotsocp

@@ -374,6 +374,15 @@ int dotsocp_advect_particles(dotsocp_ctx *ctx, const double *rho0, const double 
     return ctx->s.advect_particles(rho0, rho1, o, x, y, traj_x, traj_y, n_clamped);
 }
 
+int dotsocp_push_mass(dotsocp_ctx *ctx, const double *rho0, const double *rho1, const dotsocp_push_opts *o, double *x, double *y,
+                      const double *mass, const dotsocp_i64 *frame_nodes, double *frames, dotsocp_i64 *n_clamped, double *unit,
+                      double *l1) {
+    CTX_OR_FAIL();
+    if (ctx->s.prob.dim == 1)
+        return ctx->s.push_mass(rho0, rho1, o, nullptr, x, mass, frame_nodes, frames, n_clamped, unit, l1);
+    return ctx->s.push_mass(rho0, rho1, o, x, y, mass, frame_nodes, frames, n_clamped, unit, l1);
+}
+
 int dotsocp_jump_next_level(dotsocp_ctx *coarse, dotsocp_ctx *fine) {
     if (!coarse || !fine) { set_error("context is NULL"); return DOTSOCP_EINVAL; }
     return fine->s.jump_from(coarse->s);
@@ -407,7 +416,7 @@ int dotsocp_kernel_time(dotsocp_ctx *ctx, const char *name, double *avg_ms, dots
     static const char *names[PH_COUNT] = {"rhs", "poisson", "cone_proj", "qstep", "beta", "kkt",
                                           "cone_fused_a", "cone_fused_b", "materialise", "comm",
                                           "interp", "acc_cone", "acc_gather", "qstep_first", "transpose", "cone_carry", "qcone",
-                                          "velocity_layer", "advect"};
+                                          "velocity_layer", "advect", "deposit", "frame_l1"};
     for (int i = 0; i < PH_COUNT; ++i)
         if (strcmp(name, names[i]) == 0) {
             const i64 n = ctx->s.phase_launches[i];

@@ -175,6 +175,16 @@ int launch_advect(bool dim1, i64 ny, i64 nx, i64 py, const double *vX0, const do
                   const double *vY1, i64 n, int nsub, int dir, double dt, double *px, double *py_, unsigned int *flag,
                   hipStream_t st);
 int launch_advect_count(const unsigned int *flag, i64 n, unsigned long long *count, hipStream_t st);       // *count += set flags
+// dotsocp_push_mass: cnt (ny x nx 64-bit counts, rows py apart, zeroed by the caller) += the bilinear split of every
+// particle's units[p] over the corners of its cell, by integer atomics (include/dotsocp.h states the rounding)
+int launch_deposit(bool dim1, i64 ny, i64 nx, i64 py, i64 n, const double *px, const double *py_, const i64 *units,
+                   unsigned long long *cnt, hipStream_t st);
+// frame: the counts of launch_deposit, converted in place to (double)count * unit; *sum <- the sum over the nodes of
+// |frame - rho(:, :, tl)|, rho as launch_outputs writes it, added in the report's order (report_tiles(g) doubles at
+// `partials`).  rho0 / rho1 / a_prev as for launch_outputs.
+int launch_frame_l1(const Grid &g, const double *alpha, const double *weight, const double *rho0, const double *rho1,
+                    const double *a_prev, double sig, double cD, i64 tl, double unit, double *frame, double *partials,
+                    double *sum, hipStream_t st);
 
 // ---------------- report.hip: the solution report (mass, negativity, f(q) histograms) in one pass over alpha and q ----------------
 // Slots of the 64-bit counters one report accumulates (device array, zeroed before the launch): the two histograms, three
@@ -185,6 +195,8 @@ void report_edges_host(double edges[DOTSOCP_REPORT_BINS + 1]);
 double report_key_decode(unsigned long long key, bool inverted, double none);
 // workgroups per layer (depends on ny, nx only) and doubles of the partial-sum buffer of a slab: [ntl][3][tiles]
 i64 report_tiles(const Grid &g);
+// sums[r] = partials[r * tiles] + ... + partials[r * tiles + tiles - 1], r < rows, by the fixed tree of the report's layer sums
+int launch_report_rows(const double *partials, i64 tiles, i64 rows, double *sums, hipStream_t st);
 // one slab: `partials` [ntl][3][tiles] <- per-workgroup layer sums of rho, min(rho, 0) and the cost terms; `sums` [ntl][3]
 // <- their totals, added in tile order; counts[RC_COUNT] += this slab's share.  rho0 / rho1 / a_prev as for launch_outputs;
 // edges: DOTSOCP_REPORT_BINS + 1 doubles on the device.

@@ -212,6 +212,13 @@ __global__ void __launch_bounds__(256) k_report_final(const double *__restrict__
     if (threadIdx.x == 0) sums[blockIdx.x] = red[0];
 }
 
+int launch_report_rows(const double *partials, i64 tiles, i64 rows, double *sums, hipStream_t st) {
+    if (rows <= 0) return 0;
+    DS_KLAUNCH(k_report_final, dim3((unsigned)rows), dim3(256), 0, st, partials, tiles, sums);
+    DS_HIP(hipGetLastError());
+    return 0;
+}
+
 i64 report_tiles(const Grid &g) { return ((g.ny + TILE_Y - 1) / TILE_Y) * ((g.nx + TILE_X - 1) / TILE_X); }
 
 int launch_report(const Grid &g, const double *q, const double *alpha, const double *weight, const double *rho0,

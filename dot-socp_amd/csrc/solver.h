@@ -135,7 +135,7 @@ bool if_adjust_sigma(double iter, double last_iter);   // IfAdjustSigma (solver_
 
 enum Phase { PH_RHS = 0, PH_POISSON, PH_PROJ, PH_QSTEP, PH_BETA, PH_KKT, PH_FUSED_A, PH_FUSED_B, PH_MATERIALISE,
              PH_COMM, PH_INTERP, PH_ACC_CONE, PH_ACC_GATHER, PH_QSTEP0, PH_TRANSPOSE, PH_CONE_CARRY, PH_QCONE, PH_VELOCITY, PH_ADVECT,
-             PH_COUNT };
+             PH_DEPOSIT, PH_FRAME_L1, PH_COUNT };
 
 // The schedule of the gamma form (fused.hip, Solver::step): pure host arithmetic, also behind the C ABI.
 // rescale_due: the rescale block of iteration `it` takes its norms or rescales (solver_socp_inPALM.m:138-151), given the
@@ -287,6 +287,18 @@ struct Solver {
     int recover_velocity(const double *rho0, const double *rho1, double floor, double *vX, double *vY);
     int advect_particles(const double *rho0, const double *rho1, const dotsocp_advect_opts *o, double *x, double *y,
                          double *traj_x, double *traj_y, i64 *n_clamped);
+    // the mass the particles carry, deposited at the requested nodes (dotsocp_push_mass): the same march with frames
+    struct PushIO {
+        const i64 *units;          // n: units per particle (host)
+        const i64 *nodes;          // nf ascending frame nodes
+        i64 nf;
+        double unit;
+        double *frames, *l1;       // host: ny x nx x nf; nf or NULL
+    };
+    int push_mass(const double *rho0, const double *rho1, const dotsocp_push_opts *o, double *x, double *y, const double *mass,
+                  const i64 *frame_nodes, double *frames, i64 *n_clamped, double *unit, double *l1);
+    int march_particles(const double *rho0, const double *rho1, i64 n, int nsub, int dir, double floor, double *x, double *y,
+                        double *traj_x, double *traj_y, i64 *n_clamped, const PushIO *push);
 
     // ================ the inPALM loop and its profiling: solver.hip ================
     // ---- loop state (mirrors solver_socp_inPALM.m:11-135) ----

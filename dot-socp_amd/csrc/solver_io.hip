@@ -254,22 +254,85 @@ int Solver::advect_particles(const double *rho0, const double *rho1, const dotso
     if (!finished) { set_error("advect_particles() needs finish()"); return DOTSOCP_ESTATE; }
     DS_CHECK(need_beta_form("advect_particles"));
     DS_ARG(ny >= 2 && (dim1 || nx >= 2), "advect_particles() needs two nodes along every axis");
+    return march_particles(rho0, rho1, n, o->nsub, o->direction, o->rho_floor, x, y, traj_x, traj_y, n_clamped, nullptr);
+}
+
+// dotsocp_push_mass: the march of advect_particles with a deposit at the requested nodes.  The checks name this call; the
+// units per particle are formed here, on the host (one division by a power of two and one rounding each).
+int Solver::push_mass(const double *rho0, const double *rho1, const dotsocp_push_opts *o, double *x, double *y,
+                      const double *mass, const i64 *frame_nodes, double *frames, i64 *n_clamped, double *unit, double *l1) {
+    const bool dim1 = prob.dim == 1;
+    DS_ARG(rho0 != nullptr && rho1 != nullptr && o != nullptr && y != nullptr && (dim1 || x != nullptr),
+           "push_mass() needs rho0, rho1, opts and x (2-D: y too); one of them is NULL");
+    DS_ARG(mass != nullptr && frame_nodes != nullptr && frames != nullptr,
+           "push_mass() needs mass, frame_nodes and frames; one of them is NULL");
+    DS_ARG(o->n >= 1, "push_mass() needs n >= 1 particles");
+    DS_ARG(o->nsub >= 1, "push_mass() needs nsub >= 1 steps per time interval");
+    DS_ARG(o->direction == 1 || o->direction == -1, "push_mass() runs in direction +1 or -1");
+    DS_ARG(o->nf >= 1, "push_mass() needs nf >= 1 frame nodes");
+    DS_ARG(!remote(), "push_mass() serves the slabs of one process; contexts with an RCCL communicator are not served");
+    for (i64 k = 0; k < o->nf; ++k)
+        DS_ARG(frame_nodes[k] >= 0 && frame_nodes[k] < nt && (k == 0 || frame_nodes[k] > frame_nodes[k - 1]),
+               "push_mass(): frame_nodes must be strictly ascending node indices in [0, nt)");
+    const i64 n = o->n;
+    double mmax = 0.0;
+    for (i64 p = 0; p < n; ++p) {
+        DS_ARG(std::isfinite(y[p]) && (dim1 || std::isfinite(x[p])), "push_mass(): a seed is not finite");
+        DS_ARG(std::isfinite(mass[p]) && mass[p] >= 0.0, "push_mass(): a mass is negative or not finite");
+        mmax = mass[p] > mmax ? mass[p] : mmax;
+    }
+    DS_ARG(mmax > 0.0, "push_mass(): all masses are zero");
+    const double top = (double)n * mmax;
+    int e = 0;
+    (void)frexp(top, &e);
+    const double u = ldexp(1.0, e - 50);
+    DS_ARG(std::isfinite(top) && u >= 2.2250738585072014e-308, "push_mass(): n * max(mass) overflows, or its unit 2^(e-50) is not a normal double");
+    if (!finished) { set_error("push_mass() needs finish()"); return DOTSOCP_ESTATE; }
+    DS_CHECK(need_beta_form("push_mass"));
+    DS_ARG(ny >= 2 && (dim1 || nx >= 2), "push_mass() needs two nodes along every axis");
+    std::vector<i64> units((size_t)n);
+    for (i64 p = 0; p < n; ++p) units[(size_t)p] = llrint(mass[p] / u);
+    PushIO io{units.data(), frame_nodes, o->nf, u, frames, l1};
+    if (unit) *unit = u;
+    return march_particles(rho0, rho1, n, o->nsub, o->direction, o->rho_floor, x, y, nullptr, nullptr, n_clamped, &io);
+}
+
+// push != NULL: the block of a slab also carries the units [.. | units (n x 64 bit) | ..] from slab to slab, and every slab
+// has [count plane / frame (plane) | tile sums (report_tiles) | l1 sums (nf)].  A frame is deposited by the slab that OWNS
+// its node (whose rho layer the comparison needs): going forward the particles are handed to the right neighbour before
+// the deposit at a slab's first node instead of before the interval behind it -- the same copy, one step earlier.  One
+// plane per slab serves all its frames: zeroing, deposit, conversion and download follow each other on the slab's stream.
+int Solver::march_particles(const double *rho0, const double *rho1, i64 n, int nsub, int dir, double floor, double *x, double *y,
+                            double *traj_x, double *traj_y, i64 *n_clamped, const PushIO *push) {
+    const bool dim1 = prob.dim == 1;
     DS_CHECK(velocity_stage(rho0, rho1));
-    const int dir = o->direction, nsub = o->nsub;
-    const double floor = o->rho_floor;
     const double dt = (double)dir / (double)((nt - 1) * (i64)nsub);
     const size_t nb = sizeof(double) * (size_t)n;
-    const i64 nflag = (n + 1) / 2, PB = 2 * n + nflag + 1;
+    const i64 nflag = (n + 1) / 2, nunit = push ? n : 0, PB = 2 * n + nunit + nflag + 1;
+    const size_t S = slabs.size();
+    const i64 plane = slabs[0].g.plane, tiles = report_tiles(slabs[0].g), nf = push ? push->nf : 0;
+    std::vector<double> l1_host((size_t)(nf * (i64)S));     // host side of the copies: outlives the blocks' last sync
+    std::vector<size_t> owner((size_t)nf);
     ParticleBlocks blocks(*this);
     FOR_SLABS(s) {
         double *b = nullptr;
         DS_CHECK(dmalloc(&b, PB));
         blocks.bufs.push_back(b);
     }
+    if (push) {                     // bufs[S + k]: the frame buffers of slab k
+        FOR_SLABS(s) {
+            double *b = nullptr;
+            DS_CHECK(dmalloc(&b, plane + tiles + nf));
+            blocks.bufs.push_back(b);
+        }
+    }
     auto PX = [&](size_t k) { return blocks.bufs[k]; };
     auto PY = [&](size_t k) { return blocks.bufs[k] + n; };
-    auto FL = [&](size_t k) { return (unsigned int *)(blocks.bufs[k] + 2 * n); };
-    auto CT = [&](size_t k) { return (unsigned long long *)(blocks.bufs[k] + 2 * n + nflag); };
+    auto UN = [&](size_t k) { return (i64 *)(blocks.bufs[k] + 2 * n); };
+    auto FL = [&](size_t k) { return (unsigned int *)(blocks.bufs[k] + 2 * n + nunit); };
+    auto CT = [&](size_t k) { return (unsigned long long *)(blocks.bufs[k] + 2 * n + nunit + nflag); };
+    auto FR = [&](size_t k) { return blocks.bufs[S + k]; };
+    const i64 hplane = ny * nx;
     // positions of slab `k` -> column `node` of the trajectories
     auto record = [&](size_t k, i64 node) -> int {
         if (traj_x && !dim1) DS_HIP(ds_memcpy_async(traj_x + n * node, PX(k), nb, hipMemcpyDeviceToHost, slabs[k].st));
@@ -277,23 +340,50 @@ int Solver::advect_particles(const double *rho0, const double *rho1, const dotso
         return 0;
     };
     size_t cur = dir > 0 ? 0 : slabs.size() - 1;
+    auto hand_over = [&]() -> int {
+        const size_t nxt = dir > 0 ? cur + 1 : cur - 1;
+        if (nxt >= slabs.size()) { set_error("internal: the particles left the last slab"); return DOTSOCP_ESTATE; }
+        DS_CHECK(xcopy(slabs[cur], PX(cur), slabs[nxt], PX(nxt), PB));
+        cur = nxt;
+        return 0;
+    };
+    // the particles stand at `node`: if it is the next requested frame, deposit, convert, compare and download it
+    i64 fi = dir > 0 ? 0 : nf - 1;
+    auto frame_at = [&](i64 node) -> int {
+        if (!push || fi < 0 || fi >= nf || push->nodes[fi] != node) return 0;
+        while (dir > 0 && node >= slabs[cur].g.t0 + slabs[cur].g.ntl) DS_CHECK(hand_over());
+        Slab &s = slabs[cur];
+        const Grid &g = s.g;
+        if (node < g.t0 || node >= g.t0 + g.ntl) { set_error("internal: frame node %lld is not this slab's", node); return DOTSOCP_ESTATE; }
+        DS_CHECK(use(s));
+        double *F = FR(cur);
+        const bool prof = cur == 0;
+        DS_HIP(ds_memset_async(F, 0, sizeof(double) * (size_t)plane, s.st));
+        if (prof) prof_begin(PH_DEPOSIT);
+        DS_CHECK(launch_deposit(dim1, ny, nx, g.py, n, PX(cur), PY(cur), UN(cur), (unsigned long long *)F, s.st));
+        if (prof) { prof_end(PH_DEPOSIT); prof_begin(PH_FRAME_L1); }
+        DS_CHECK(launch_frame_l1(g, s.alpha, s.weight, s.w1, s.w1 + plane, s.a0_prev, sigma, cScale * D, node - g.t0, push->unit, F,
+                                 F + plane, F + plane + tiles + fi, s.st));
+        if (prof) prof_end(PH_FRAME_L1);
+        DS_CHECK(copy_rows(F, push->frames + hplane * fi, ny, g.py, nx, false, s.st));
+        owner[(size_t)fi] = cur;
+        fi += dir;
+        return 0;
+    };
     {
         Slab &s = slabs[cur];
         DS_CHECK(use(s));
         DS_HIP(ds_memset_async(PX(cur), 0, sizeof(double) * (size_t)PB, s.st));
         if (!dim1) DS_HIP(ds_memcpy_async(PX(cur), x, nb, hipMemcpyHostToDevice, s.st));
         DS_HIP(ds_memcpy_async(PY(cur), y, nb, hipMemcpyHostToDevice, s.st));
+        if (push) DS_HIP(ds_memcpy_async(UN(cur), push->units, nb, hipMemcpyHostToDevice, s.st));
         DS_CHECK(launch_advect_seed(dim1, n, PX(cur), PY(cur), FL(cur), s.st));
         DS_CHECK(record(cur, dir > 0 ? 0 : nt - 1));
+        DS_CHECK(frame_at(dir > 0 ? 0 : nt - 1));
     }
     for (i64 step = 0; step < nt - 1; ++step) {
         const i64 k = dir > 0 ? step : nt - 2 - step;      // the interval between nodes k and k + 1: run by the slab that owns cell k
-        while (k < slabs[cur].g.t0 || k >= slabs[cur].g.t0 + slabs[cur].g.ncl) {
-            const size_t nxt = dir > 0 ? cur + 1 : cur - 1;
-            if (nxt >= slabs.size()) { set_error("internal: no slab owns cell layer %lld", k); return DOTSOCP_ESTATE; }
-            DS_CHECK(xcopy(slabs[cur], PX(cur), slabs[nxt], PX(nxt), PB));
-            cur = nxt;
-        }
+        while (k < slabs[cur].g.t0 || k >= slabs[cur].g.t0 + slabs[cur].g.ncl) DS_CHECK(hand_over());
         Slab &s = slabs[cur];
         DS_CHECK(velocity_layer(s, k, floor));
         DS_CHECK(velocity_layer(s, k + 1, floor));
@@ -305,6 +395,7 @@ int Solver::advect_particles(const double *rho0, const double *rho1, const dotso
                                FL(cur), s.st));
         if (prof) prof_end(PH_ADVECT);
         DS_CHECK(record(cur, dir > 0 ? k + 1 : k));
+        DS_CHECK(frame_at(dir > 0 ? k + 1 : k));
     }
     unsigned long long count = 0;
     {
@@ -315,10 +406,22 @@ int Solver::advect_particles(const double *rho0, const double *rho1, const dotso
         DS_HIP(ds_memcpy_async(y, PY(cur), nb, hipMemcpyDeviceToHost, s.st));
         DS_HIP(ds_memcpy_async(&count, CT(cur), sizeof count, hipMemcpyDeviceToHost, s.st));
     }
+    if (push && push->l1) {
+        size_t k = 0;
+        FOR_SLABS(s) {
+            bool mine = false;
+            for (i64 f = 0; f < nf; ++f) mine = mine || owner[(size_t)f] == k;
+            if (mine) DS_HIP(ds_memcpy_async(l1_host.data() + nf * (i64)k, FR(k) + plane + tiles, sizeof(double) * (size_t)nf,
+                                             hipMemcpyDeviceToHost, s.st));
+            ++k;
+        }
+    }
     DS_CHECK(sync_all());
     DS_CHECK(prof_flush());
     DS_CHECK(canary_after(*this));
     if (n_clamped) *n_clamped = (i64)count;
+    if (push && push->l1)
+        for (i64 f = 0; f < nf; ++f) push->l1[f] = l1_host[(size_t)(nf * (i64)owner[(size_t)f] + f)] / (double)hplane;
     return 0;
 }
 

@@ -260,6 +260,53 @@ class InPALMContext:
                                                        ptr(tx), ptr(ty), ctypes.byref(nc)))
         return dict(x=px, y=py, traj_x=tx, traj_y=ty, n_clamped=int(nc.value))
 
+    def push_forward(self, x, y=None, mass=None, frames=None, nsub=1, direction=+1, rho_floor=None):
+        """The mass the particles carry, deposited on the grid at the time nodes `frames` (None: every node) on the device
+        (dotsocp_push_mass; advect.py): the particles of advect() with one mass each (finite, >= 0, not all zero), integer
+        accumulation -- exact conservation, the same bits for any particle order and slab split.  Returns dict(frames,
+        counts, nodes, unit, l1, x, y, n_clamped, total_units) as advect.push_forward does, with the same bits as
+        advect.push_forward(self.outputs(), ...) (l1: to rounding; identical between two calls).  Call after finish()."""
+        m = self.model
+        one_d = not hasattr(m, "ny")
+        if one_d != (y is None):
+            raise ValueError("push_forward(): y is given on a 2-D context and only there")
+        if mass is None:
+            raise ValueError("push_forward(): mass is needed")
+        px = np.array(x, dtype=np.float64).ravel()
+        py = None if one_d else np.array(y, dtype=np.float64).ravel()
+        ms = np.array(mass, dtype=np.float64).ravel()
+        if (py is not None and py.size != px.size) or ms.size != px.size:
+            raise ValueError("push_forward(): x, y and mass hold one entry per seed")
+        nt = int(m.nt)
+        nodes = np.arange(nt, dtype=np.int64) if frames is None else np.array(frames, dtype=np.int64).ravel()
+        o = capi.PushOpts()
+        o.n, o.nsub, o.direction, o.rho_floor, o.nf = int(px.size), int(nsub), int(direction), self._rho_floor(rho_floor), int(nodes.size)
+        shp = (int(m.nx),) if one_d else (int(m.ny), int(m.nx))
+        fr = np.empty(shp + (nodes.size,), order="F")
+        l1 = np.empty(nodes.size)
+        ptr = lambda a: None if a is None else capi.fptr(a)                 # noqa: E731
+        r0, r1 = self._rho_ends()
+        nc, unit = capi.i64(), capi.dbl()
+        capi.check(capi.lib().dotsocp_push_mass(self._ctx, capi.fptr(r0), capi.fptr(r1), ctypes.byref(o), ptr(px), ptr(py),
+                                                capi.fptr(ms), nodes.ctypes.data, capi.fptr(fr), ctypes.byref(nc),
+                                                ctypes.byref(unit), capi.fptr(l1)))
+        u = unit.value
+        counts = (fr / u).astype(np.int64)                 # exact: the frames are whole multiples of a power of two
+        return dict(frames=fr, counts=counts, nodes=nodes, unit=u, l1=l1, x=px, y=py, n_clamped=int(nc.value),
+                    total_units=int(np.rint(ms / u).astype(np.int64).sum()))
+
+    def push_from_nodes(self, stride=1, frames=None, nsub=1, direction=+1, rho_floor=None):
+        """push_forward() of the given density itself: a particle on every stride-th node (advect.seeds_on_nodes) with the
+        value of rho0 there as its mass (direction=-1: of rho1, carried back from t = 1).  With stride=1, l1 at the far end
+        is the defect of the transport map: how far the pushed rho0 is from rho1."""
+        from .advect import masses_on_nodes, seeds_on_nodes
+        m = self.model
+        one_d = not hasattr(m, "ny")
+        dens = np.asarray(m.rho0 if int(direction) > 0 else m.rho1, dtype=np.float64)
+        x, y = seeds_on_nodes(int(m.nx), None if one_d else int(m.ny), stride=stride)
+        return self.push_forward(x, y, mass=masses_on_nodes(dens, stride=stride), frames=frames, nsub=nsub, direction=direction,
+                                 rho_floor=rho_floor)
+
     def close(self):
         if getattr(self, "_ctx", None):
             capi.lib().dotsocp_destroy(self._ctx)
@@ -355,7 +402,7 @@ def _weights_mode(weight, weights, transfer, weighted=True):
 
 
 def _solve_levels(rho0, rho1, nt, levelN, opts, method, dim, weighted, device, barrier=None, transfer="device",
-                  weights=None, report=False, advect=None):
+                  weights=None, report=False, advect=None, push=None):
     """The level loop of solver_dotsocp2d.m:154-250 (dot1d / wdot2d twins): restrict the data to
     levelN grids, solve coarse to fine with warm starts; every solve runs on the device.
     transfer = "device": the state never leaves the GPU -- jump_nextLevel and the output recovery run there
@@ -371,7 +418,10 @@ def _solve_levels(rho0, rho1, nt, levelN, opts, method, dim, weighted, device, b
     is closed; output["report"] holds it.  Needs transfer="device".
     advect = dict(x=..., y=..., nsub=..., direction=..., rho_floor=..., trajectories=...): the keyword arguments of
     InPALMContext.advect(), which is asked of the last level's context in the same way; output["advect"] holds its
-    result.  Needs transfer="device"."""
+    result.  Needs transfer="device".
+    push = dict(stride=..., frames=..., nsub=..., direction=..., rho_floor=...): the keyword arguments of
+    InPALMContext.push_from_nodes() -- the given density carried along the solved flow and deposited at the frame nodes --
+    asked of the last level's context; output["push"] holds its result.  Needs transfer="device"."""
     from . import multilevel as ML
     from .examples import ensure_barrier_validity
     if not (isinstance(levelN, (int, np.integer)) and levelN >= 1):
@@ -382,6 +432,8 @@ def _solve_levels(rho0, rho1, nt, levelN, opts, method, dim, weighted, device, b
         raise ValueError("report=True needs transfer='device' (the report is taken from the device-resident state)")
     if advect is not None and transfer != "device":
         raise ValueError("advect= needs transfer='device' (the particles move through the device-resident state)")
+    if push is not None and transfer != "device":
+        raise ValueError("push= needs transfer='device' (the mass moves through the device-resident state)")
     wopt = _get(opts, "weight") if weighted else None
     weights = _weights_mode(wopt, weights, transfer, weighted)
     wdev = weights == "device"
@@ -464,6 +516,8 @@ def _solve_levels(rho0, rho1, nt, levelN, opts, method, dim, weighted, device, b
                     output["report"] = ctx.report()
                 if advect is not None:
                     output["advect"] = ctx.advect(**advect)
+                if push is not None:
+                    output["push"] = ctx.push_from_nodes(**push)
             if not on_device:
                 ctx.close()
                 recoverOrgVar(var)
@@ -499,34 +553,35 @@ def _solve_levels(rho0, rho1, nt, levelN, opts, method, dim, weighted, device, b
 
 
 def solver_dotsocp2d(rho0, rho1, nt, levelN, opts, method="inPALM", device=0, transfer="device", report=False,
-                     advect=None):
+                     advect=None, push=None):
     """[output, timeML, runHistML, runHist] = solver_dotsocp2d(rho0, rho1, nt, levelN, opts, method)
     socp/dot2d/solver_dotsocp2d.m:1.  report=True: output["report"] = the device-side solution report; advect=dict(x=..., y=...,
-    ...): output["advect"] = the particles carried along the solved flow (both: _solve_levels)."""
+    ...): output["advect"] = the particles carried along the solved flow; push=dict(stride=..., frames=..., ...):
+    output["push"] = the given density carried along it and deposited at the frame nodes (all three: _solve_levels)."""
     output, timeML, runHistML, runHist = _solve_levels(rho0, rho1, nt, levelN, opts, method, 2, False, device,
-                                                       transfer=transfer, report=report, advect=advect)
+                                                       transfer=transfer, report=report, advect=advect, push=push)
     if not check_massConservation(output["rho"], 1e-2):
         print("Warning: The mass conservation constraint violation exceeds 0.01")
     return output, timeML, runHistML, runHist
 
 
 def solver_dotsocp1d(rho0, rho1, nt, levelN, opts, method="inPALM", device=0, transfer="device", report=False,
-                     advect=None):
-    """socp/dot1d/solver_dotsocp1d.m:1.  report, advect: as for solver_dotsocp2d."""
+                     advect=None, push=None):
+    """socp/dot1d/solver_dotsocp1d.m:1.  report, advect, push: as for solver_dotsocp2d."""
     output, timeML, runHistML, runHist = _solve_levels(rho0, rho1, nt, levelN, opts, method, 1, False, device,
-                                                       transfer=transfer, report=report, advect=advect)
+                                                       transfer=transfer, report=report, advect=advect, push=push)
     if not check_massConservation(output["rho"], 1e-2):
         print("Warning: The mass conservation constraint violation exceeds 0.01")
     return output, timeML, runHistML, runHist
 
 
 def solver_wdotsocp2d(rho0, rho1, nt, levelN, opts, method="inPALM", barrier=None, device=0, transfer="device",
-                      weights=None, report=False, advect=None):
+                      weights=None, report=False, advect=None, push=None):
     """socp/wdot2d/solver_wdotsocp2d.m:1.  opts["weight"]: the Nq array, or a SpaceWeight (examples.py); weights:
-    where the levels' weights are made, "host" or "device" (_solve_levels); report, advect: as for solver_dotsocp2d."""
+    where the levels' weights are made, "host" or "device" (_solve_levels); report, advect, push: as for solver_dotsocp2d."""
     output, timeML, runHistML, runHist = _solve_levels(rho0, rho1, nt, levelN, opts, method, 2, True, device,
                                                        barrier=barrier, transfer=transfer, weights=weights, report=report,
-                                                       advect=advect)
+                                                       advect=advect, push=push)
     if not check_massConservation(output["rho"], 1e-2):
         print("Warning: The tolerance of mass conservation constraint is under 0.01")
     return output, timeML, runHistML, runHist

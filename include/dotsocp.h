@@ -373,6 +373,45 @@ typedef struct { dotsocp_i64 n; int nsub; int direction; double rho_floor; } dot
 int dotsocp_advect_particles(dotsocp_ctx *ctx, const double *rho0, const double *rho1, const dotsocp_advect_opts *o,
                              double *x, double *y, double *traj_x, double *traj_y, dotsocp_i64 *n_clamped);
 
+/* Where the mass goes, literally: every particle of dotsocp_advect_particles carries a mass, and at the requested time
+ * nodes the masses are deposited on the grid -- the push-forward of the seeded measure by the flow map, the displacement
+ * (McCann) interpolant drawn next to the Eulerian rho layers.  With the masses rho0[j, i] on all nodes, l1 at node nt - 1
+ * is the defect of the map: how far T#rho0 is from rho1.
+ *
+ * Trajectories.  Exactly those of dotsocp_advect_particles with the same rho0, rho1, n, nsub, direction, rho_floor and
+ *   seeds: final x / y and n_clamped carry the same bits.
+ * Deposit by integer accumulation: no result depends on the particle order, the launch shape or the slab split, and
+ *   every frame holds the same number of units.
+ *   Unit.       frexp((double)n * max_p mass[p]) = (f, e);  unit = 2^(e - 50).  The total stays below 2^51 units: every
+ *               count converts to a double exactly.  (DOTSOCP_EINVAL if the product overflows or unit is not a normal double.)
+ *   Units.      M_p = llrint(mass[p] / unit)                               (round half to even, = numpy.rint)
+ *   Weights.    At a frame node the particle at (x, y) takes (i, a) and (j, c) as the velocity interpolation above does.
+ *                   d00 = llrint(((1 - c) * (1 - a)) * (double)M_p)   -> count[j, i]
+ *                   d10 = llrint((c * (1 - a)) * (double)M_p)         -> count[j + 1, i]
+ *                   d01 = llrint(((1 - c) * a) * (double)M_p)         -> count[j, i + 1]
+ *                   d11 = M_p - d00 - d10 - d01                       -> count[j + 1, i + 1]
+ *               The last corner takes the remainder (it can be -1): a particle deposits exactly M_p units.  1-D:
+ *               d0 = llrint((1 - a) * (double)M_p) -> count[i],  d1 = M_p - d0 -> count[i + 1].
+ *   Counts.     SIGNED 64-bit sums of the above (64-bit integer atomic adds; two's-complement wrap is exact).  A count
+ *               is reported as it is, also when a remainder of -1 falls on a node nothing else reaches.
+ *   Frame.      frames[j, i, k] = (double)count[j, i] * unit  at node frame_nodes[k]; sum(count) = sum_p M_p in every frame.
+ * l1[k] = mean over the ny * nx nodes of |frames[:, :, k] - rho(:, :, frame_nodes[k])|, rho as dotsocp_recover_outputs
+ *   writes it; summed in the fixed order of dotsocp_solution_report's layer sums, so two calls and any slab split give the
+ *   same bits.
+ * The deposit is built without contraction of a * b + c: advect.push_forward restates it in numpy with the same bits.
+ *
+ * Valid where dotsocp_advect_particles is (after finish(); all loops, weighted, 1-D; one slab, `nslabs` slabs,
+ * dotsocp_create_multi: the slab that owns a frame's node deposits it into a plane on its own device, the planes are
+ * gathered on the host).  DOTSOCP_EINVAL: what dotsocp_advect_particles refuses, a NULL mass / frame_nodes / frames,
+ * nf < 1, frame_nodes not strictly ascending in [0, nt), a mass that is negative or not finite, all masses zero. */
+typedef struct { dotsocp_i64 n; int nsub; int direction; double rho_floor; dotsocp_i64 nf; } dotsocp_push_opts;
+/* x, y: as for dotsocp_advect_particles (in: seeds, out: final positions; y NULL for 1-D).  mass: n doubles.
+ * frame_nodes: nf node indices.  frames: ny x nx x nf doubles, y fastest (1-D: nx x nf).  n_clamped, unit (1 double),
+ * l1 (nf doubles) may be NULL. */
+int dotsocp_push_mass(dotsocp_ctx *ctx, const double *rho0, const double *rho1, const dotsocp_push_opts *o,
+                      double *x, double *y, const double *mass, const dotsocp_i64 *frame_nodes, double *frames,
+                      dotsocp_i64 *n_clamped, double *unit, double *l1);
+
 /* Multilevel transfer on the device: socp/dot2d/utils/jump_nextLevel.m:5-16 with
  * interpolate.m:20-84, between the finished context `coarse` and the context `fine` of the next level (created
  * from the fine level's InitialScaling scalars, c and weight uploaded, begin() not yet called; grid
@@ -436,7 +475,8 @@ int dotsocp_get_history(dotsocp_ctx *ctx, double *kkt, double *time, double *ite
  * "cone_fused_b", "materialise", "comm", "interp", "acc_cone", "acc_gather", "qstep_first", "transpose", "cone_carry"
  * (the cone passes that read gamma and no q^{k-1}; "cone_fused_b" keeps the passes that move 8 (20 Nz + 3 Nq) bytes),
  * "qcone" (a q-step with the next iteration's gamma-reading cone pass in the same kernel: counted here alone),
- * "velocity_layer", "advect" (the launches of dotsocp_recover_velocity / dotsocp_advect_particles on the first slab). */
+ * "velocity_layer", "advect" (the launches of dotsocp_recover_velocity / dotsocp_advect_particles on the first slab),
+ * "deposit", "frame_l1" (the per-frame launches of dotsocp_push_mass on the first slab). */
 int dotsocp_set_profiling(dotsocp_ctx *ctx, int on);
 int dotsocp_kernel_time(dotsocp_ctx *ctx, const char *name, double *avg_ms, dotsocp_i64 *launches);
 

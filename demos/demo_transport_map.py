@@ -9,7 +9,11 @@ much, and a particle in the far corner has nowhere to go.  Printed: the deviatio
 over all particles, weighted by the mass rho0 they stand for, and over the seeds within 0.1 of the start centre.
 After the particles, the mass itself (push= of the drivers): rho0 carried by a particle on every node and deposited on the
 grid -- the displacement interpolant next to the Eulerian rho layers -- with its mean distance l1 to rho at t = 1 (the
-defect of the map) and half-way, and the check that every frame holds exactly the same number of mass units."""
+defect of the map) and half-way, and the check that every frame holds exactly the same number of mass units.
+Last, the judgement of the map itself (map_report= and report= of the drivers): what the map realised by the flow costs
+(the mass-weighted mean of |end - start|^2), beside the mean squared path length and the kinetic action of the same
+particles -- equal for straight paths at constant speed, as an optimal map gives them -- and beside the Eulerian cost of
+the solution report."""
 import os
 import sys
 
@@ -24,7 +28,8 @@ floor = D.default_rho_floor(rho0, rho1)
 x0, y0 = D.seeds_on_nodes(nx, nx, stride=4, mask=rho0 > floor)
 output, timeML, runHistML, runHist = D.solver_dotsocp2d(rho0, rho1, nt, levelN, dict(tol=tol, maxit=3000), "inPALM",
                                                         advect=dict(x=x0, y=y0, nsub=2, trajectories=True),
-                                                        push=dict(stride=1, frames=[0, nt // 2, nt - 1], nsub=2))
+                                                        push=dict(stride=1, frames=[0, nt // 2, nt - 1], nsub=2),
+                                                        map_report=dict(stride=1, nsub=2), report=True)
 adv = output["advect"]
 dev = np.hypot(adv["x"] - x0 - (-0.5), adv["y"] - y0 - 0.5)
 print(f"{x0.size} particles (every 4th node with rho0 > {floor:.3g}), {adv['n_clamped']} clamped at the boundary")
@@ -46,3 +51,12 @@ print(f"pushed rho0 ({push['x'].size} particles, {push['n_clamped']} clamped): l
 units = push["counts"].sum(axis=(0, 1))
 print(f"units of 2^{int(np.log2(push['unit']))} per frame: {units.tolist()}; all equal to the particles' {push['total_units']}: "
       f"{bool(np.all(units == push['total_units']))}")
+# how good the map is as a transport map, beside l1 (does it reach rho1?) and the Eulerian cost of the same solve
+mr = output["map_report"]
+print(f"map report ({mr['n']} particles, mass rho0): cost_map {mr['cost_map']:.6f} <= cost_length {mr['cost_length']:.6f} <= "
+      f"cost_action {mr['cost_action']:.6f}; Eulerian cost (solution report) {output['report']['cost']:.6f}")
+print(f"  paths: length / displacement - 1 = {mr['cost_length'] / mr['cost_map'] - 1:.2e} in the mean square, worst detour "
+      f"{mr['detour_max']:.3e}, {mr['detour_over']} particles more than 10 % longer than straight, {mr['n_still']} never moved; "
+      f"speed: action / length^2 - 1 = {mr['cost_action'] / mr['cost_length'] - 1:.2e}")
+print(f"  mean displacement {mr['disp_mean']:.4f}, mean path length {mr['len_mean']:.4f}, longest {mr['len_max']:.4f}; "
+      f"l1 at t = 1 beside it: {push['l1'][-1]:.4e}")

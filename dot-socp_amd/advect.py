@@ -7,6 +7,8 @@ The velocity is the one utils/show_movement_2d.m draws: arrows of E, masked wher
 push_forward is the twin of dotsocp_push_mass: the masses the particles carry, deposited on the grid at chosen time nodes
 in whole units (int64 planes, np.add.at), so that every frame conserves the mass exactly and no bit depends on the order
 of the particles; InPALMContext.push_forward() returns the same bits.
+map_report is the twin of dotsocp_map_report: displacement, path length and kinetic action of every particle and their
+mass-weighted means, added in the device's order; InPALMContext.map_report() returns the same bits.
 
 Coordinates: the unit square and t in [0, 1]; x runs along the SECOND array index of the outputs (nx columns, node i at
 i / (nx - 1)), y along the first (ny rows); 1-D outputs (nx, nt) have x alone.  E = +rho v.
@@ -79,6 +81,13 @@ def advect(out, x, y=None, nsub=1, direction=+1, rho_floor=None, trajectories=Fa
     default_rho_floor of the first and last layer of rho (which are rho0 and rho1).  Returns dict(x, y, traj_x, traj_y,
     n_clamped): final positions; with trajectories=True the (n, nt) positions at every time node, indexed by node in
     both directions (else None); the number of particles that the clamp at the end of some step moved."""
+    return _march(out, x, y, nsub, direction, rho_floor, trajectories, False)
+
+
+def _march(out, x, y, nsub, direction, rho_floor, trajectories, path):
+    """advect(); path=True (map_report): the result also holds x0, y0 (the clamped seeds), sq and len -- the sums of
+    |step|^2 and |step| over all steps, each step taken between the position before it and the one after its end clamp --
+    and steps = (nt - 1) * nsub"""
     rho = np.asarray(out["rho"], dtype=np.float64)
     one_d = "Ey" not in out
     if one_d != (y is None):
@@ -114,6 +123,8 @@ def advect(out, x, y=None, nsub=1, direction=+1, rho_floor=None, trajectories=Fa
                 ty[:, node] = y
 
     record(0 if direction > 0 else nt - 1)
+    x0, y0 = x, y
+    sq, length = np.zeros(x.size), np.zeros(x.size)
     for it in range(nt - 1):
         k = it if direction > 0 else nt - 2 - it
         for s in range(nsub):
@@ -123,6 +134,7 @@ def advect(out, x, y=None, nsub=1, direction=+1, rho_floor=None, trajectories=Fa
             k2x, k2y = V(step(x, hh, k1x), step(y, hh, k1y), k, b1)
             k3x, k3y = V(step(x, hh, k2x), step(y, hh, k2y), k, b1)
             k4x, k4y = V(step(x, dt, k3x), step(y, dt, k3y), k, b2)
+            xo, yo = x, y
             ux = final(x, k1x, k2x, k3x, k4x)
             moved |= (ux < 0.0) | (ux > 1.0)
             x = _clamp(ux)
@@ -130,8 +142,89 @@ def advect(out, x, y=None, nsub=1, direction=+1, rho_floor=None, trajectories=Fa
                 uy = final(y, k1y, k2y, k3y, k4y)
                 moved |= (uy < 0.0) | (uy > 1.0)
                 y = _clamp(uy)
+            if path:
+                ex = x - xo
+                s2 = ex * ex if one_d else ex * ex + (y - yo) * (y - yo)
+                sq = sq + s2
+                length = length + np.sqrt(s2)
         record(k + 1 if direction > 0 else k)
-    return dict(x=x, y=y, traj_x=tx, traj_y=ty, n_clamped=int(np.count_nonzero(moved)))
+    r = dict(x=x, y=y, traj_x=tx, traj_y=ty, n_clamped=int(np.count_nonzero(moved)))
+    if path:
+        r.update(x0=x0, y0=y0, sq=sq, len=length, steps=(nt - 1) * nsub)
+    return r
+
+
+def _tree_sum(t):
+    """The sum of the terms t (all >= 0) in the order dotsocp_map_report adds them (include/dotsocp.h, "Sums"): blocks of 256
+    consecutive particles, padded with +0.0; in a block the four wavefronts of 64 by the halving tree, then ((w0 + w1) + w2)
+    + w3; the blocks by k_report_final's tree: 256 running sums over every 256th block, then the halving tree."""
+    t = np.asarray(t, dtype=np.float64)
+    blocks = -(-t.size // 256)
+    v = np.zeros(blocks * 256)
+    v[:t.size] = t
+    v = v.reshape(blocks, 4, 64)
+    off = 32
+    while off >= 1:
+        v = v[..., :off] + v[..., off:2 * off]
+        off //= 2
+    w = v[..., 0]
+    part = ((w[:, 0] + w[:, 1]) + w[:, 2]) + w[:, 3]
+    rows = -(-blocks // 256)
+    p = np.zeros(rows * 256)
+    p[:blocks] = part
+    p = p.reshape(rows, 256)
+    red = np.zeros(256)
+    for k in range(rows):
+        red = red + p[k]
+    off = 128
+    while off >= 1:
+        red = red[:off] + red[off:2 * off]
+        off //= 2
+    return float(red[0])
+
+
+def map_report(out, x, y=None, mass=None, nsub=1, direction=+1, rho_floor=None, per_particle=False):
+    """Twin of dotsocp_map_report on the outputs dict: how good the flow of v = E / rho is as a transport map.  The particles
+    of advect() (same seeds, nsub, direction, rho_floor: same trajectories) each give the displacement disp = |end - start|,
+    the path length len = sum |step| and the kinetic action = sum |step|^2 / |dt|; over the march of total time 1,
+    disp^2 <= len^2 <= action, with equality iff the path is straight resp. the speed constant.  mass: one per particle,
+    finite, >= 0, not all zero; None: all 1.  Returns dict(n, n_clamped, n_still, mass, cost_map, cost_length, cost_action,
+    disp_mean, len_mean, disp_max, len_max, detour_max, detour_hist, detour_over, x, y, disp, len, action): the
+    mass-weighted means of disp^2, len^2, action, disp, len (summed in the device's order, which depends on n alone: the same
+    bits); maxima over all particles; detour = 1 - disp / len (0 for a particle that did not move) counted over the edges
+    of report.report_edges() with the solution report's bin rule, detour_over = the count above the last edge (0.1);
+    n_still = particles with len == 0; final positions; the per-particle arrays with per_particle=True, else None."""
+    from .report import _bin_counts, report_edges
+    n = np.asarray(x).size
+    if mass is None:
+        m = np.ones(n)
+    else:
+        m = np.array(mass, dtype=np.float64).ravel()
+        if m.size != n:
+            raise ValueError("map_report(): one mass per seed")
+        if not np.all(np.isfinite(m)) or np.any(m < 0.0):
+            raise ValueError("map_report(): a mass is negative or not finite")
+        if not np.any(m > 0.0):
+            raise ValueError("map_report(): all masses are zero")
+    r = _march(out, x, y, nsub, direction, rho_floor, False, True)
+    dx = r["x"] - r["x0"]
+    disp2 = dx * dx if r["y"] is None else dx * dx + (r["y"] - r["y0"]) * (r["y"] - r["y0"])
+    disp, length = np.sqrt(disp2), r["len"]
+    action = r["sq"] * float(r["steps"])
+    len2 = length * length
+    with np.errstate(invalid="ignore", divide="ignore"):
+        q = 1.0 - disp / length
+        detour = np.where((length > 0.0) & (q > 0.0), q, 0.0)
+    edges = report_edges()
+    hist = _bin_counts(detour, edges)
+    total = _tree_sum(m)
+    mean = lambda t: _tree_sum(m * t) / total                               # noqa: E731
+    return dict(n=int(n), n_clamped=r["n_clamped"], n_still=int(np.count_nonzero(length == 0.0)), mass=total,
+                cost_map=mean(disp2), cost_length=mean(len2), cost_action=mean(action), disp_mean=mean(disp),
+                len_mean=mean(length), disp_max=float(disp.max()), len_max=float(length.max()),
+                detour_max=float(detour.max()), detour_hist=hist, detour_over=int(np.count_nonzero(detour > edges[-1])),
+                x=r["x"], y=r["y"], disp=disp if per_particle else None, len=length if per_particle else None,
+                action=action if per_particle else None)
 
 
 def mass_unit(n, mass_max):

@@ -67,6 +67,14 @@ class PushOpts(ctypes.Structure):
     _fields_ = [("n", i64), ("nsub", ctypes.c_int), ("direction", ctypes.c_int), ("rho_floor", dbl), ("nf", i64)]
 
 
+class MapReport(ctypes.Structure):
+    """dotsocp_map_report_t"""
+    _fields_ = [("n", i64), ("n_clamped", i64), ("n_still", i64), ("mass", dbl),
+                ("cost_map", dbl), ("cost_length", dbl), ("cost_action", dbl), ("disp_mean", dbl), ("len_mean", dbl),
+                ("disp_max", dbl), ("len_max", dbl), ("detour_max", dbl),
+                ("detour_hist", i64 * REPORT_BINS), ("detour_over", i64)]
+
+
 METHOD_INPALM, METHOD_PALM, METHOD_ACCADMM = 0, 1, 2
 
 
@@ -115,6 +123,8 @@ SYMBOLS = {
     "dotsocp_advect_particles": (ctypes.c_int, [vp, vp, vp, ctypes.POINTER(AdvectOpts), vp, vp, vp, vp, ctypes.POINTER(i64)]),
     "dotsocp_push_mass": (ctypes.c_int, [vp, vp, vp, ctypes.POINTER(PushOpts), vp, vp, vp, vp, vp, ctypes.POINTER(i64),
                                          ctypes.POINTER(dbl), vp]),
+    "dotsocp_map_report": (ctypes.c_int, [vp, vp, vp, ctypes.POINTER(AdvectOpts), vp, vp, vp, ctypes.POINTER(MapReport),
+                                          vp, vp, vp]),
     "dotsocp_jump_next_level": (ctypes.c_int, [vp, vp]),
     "dotsocp_finish": (ctypes.c_int, [vp, ctypes.POINTER(Result)]),
     "dotsocp_get_history": (ctypes.c_int, [vp, vp, vp, vp, vp]),

@@ -1,6 +1,6 @@
 // Particle transport along the solved flow: the velocity v = E / rho of the Benamou-Brenier solution at the nodes
 // (the arrows of utils/show_movement_2d.m, without the plot) and its characteristics, the Monge map, by classical RK4.
-// Semantics: include/dotsocp.h (dotsocp_recover_velocity, dotsocp_advect_particles, dotsocp_push_mass); the numpy twin dot-socp_amd/advect.py
+// Semantics: include/dotsocp.h (dotsocp_recover_velocity, dotsocp_advect_particles, dotsocp_push_mass, dotsocp_map_report); the numpy twin dot-socp_amd/advect.py
 // follows the kernels below operation by operation, and this file is built without contraction (Makefile), so the two
 // agree bit for bit.
 //   k_velocity_layer  one node layer of (vX, vY) from alpha: rho, Ex, Ey are the expressions of outputs_node.h, i.e. the
@@ -10,6 +10,8 @@
 //   k_deposit         one thread per particle, once per requested frame: the particle's mass units split over the corners of
 //                     its cell and added to a plane of 64-bit counts by four returnless integer atomics
 //   k_frame_l1        counts -> frame (in place) and the tile sums of |frame - rho| against the node layer, in the report's order
+//   k_advect<., true> the same march, adding up |step|^2 and |step| per particle (dotsocp_map_report)
+//   k_map_final       displacement, path length, action and detour of every particle; sums, maxima and the detour histogram
 // Index conventions as everywhere: y fastest (rows `py` apart); X = the component / coordinate along the second array
 // index, Y = along the first.  1-D problems live in the Y slot (ny = nx1d, nx = 1): their kernels touch Y alone.
 #include "device_utils.h"
@@ -106,6 +108,7 @@ struct AdvectArgs {
     double dt, hh, h6;                      // dir / ((nt - 1) nsub), dt / 2, dt / 6
     double *px, *py_;                       // positions, SoA
     unsigned int *flag;                     // sticky: the clamp at the end of some step moved this particle
+    double *sq, *len;                       // k_advect<., true>: sum of |step|^2 and of |step| so far, per particle
 };
 
 // cell index and weight along one axis of n nodes: u in [0, 1]
@@ -137,11 +140,15 @@ __device__ __forceinline__ void adv_velocity(const AdvectArgs &A, double x, doub
     vy = (1.0 - b) * adv_layer<DIM>(A.vY0, A.py, i, a, j, c) + b * adv_layer<DIM>(A.vY1, A.py, i, a, j, c);
 }
 
-template <int DIM>
+// ACC (dotsocp_map_report): the march also adds up what every step actually moved the particle -- between the position
+// before the step and the one after its end clamp -- as |step|^2 and |step|, in march order
+template <int DIM, bool ACC>
 __global__ void __launch_bounds__(ADV_BLOCK) k_advect(AdvectArgs A) {
     const i64 p = (i64)blockIdx.x * ADV_BLOCK + threadIdx.x;
     if (p >= A.n) return;
     double x = DIM == 2 ? A.px[p] : 0.0, y = A.py_[p];
+    double sq = 0.0, len = 0.0;
+    if (ACC) { sq = A.sq[p]; len = A.len[p]; }
     bool moved = false;
     const double den = (double)(2 * A.nsub);
     for (int s = 0; s < A.nsub; ++s) {
@@ -156,12 +163,20 @@ __global__ void __launch_bounds__(ADV_BLOCK) k_advect(AdvectArgs A) {
         const double ux = x + A.h6 * (((k1x + 2.0 * k2x) + 2.0 * k3x) + k4x);
         const double uy = y + A.h6 * (((k1y + 2.0 * k2y) + 2.0 * k3y) + k4y);
         moved = moved || ux < 0.0 || ux > 1.0 || uy < 0.0 || uy > 1.0;
+        const double xo = x, yo = y;
         x = adv_clamp(ux);
         y = adv_clamp(uy);
+        if (ACC) {
+            const double ex = x - xo, ey = y - yo;
+            const double s2 = DIM == 2 ? ex * ex + ey * ey : ey * ey;
+            sq = sq + s2;
+            len = len + sqrt(s2);
+        }
     }
     if (DIM == 2) A.px[p] = x;
     A.py_[p] = y;
     if (moved) A.flag[p] = 1u;
+    if (ACC) { A.sq[p] = sq; A.len[p] = len; }
 }
 
 // *count += number of set flags
@@ -185,12 +200,17 @@ int launch_advect_seed(bool dim1, i64 n, double *px, double *py, unsigned int *f
 
 int launch_advect(bool dim1, i64 ny, i64 nx, i64 py, const double *vX0, const double *vY0, const double *vX1,
                   const double *vY1, i64 n, int nsub, int dir, double dt, double *px, double *py_, unsigned int *flag,
-                  hipStream_t st) {
+                  hipStream_t st, double *sq, double *len) {
     if (n <= 0) return 0;
-    AdvectArgs A{vX0, vY0, vX1, vY1, ny, nx, py, n, nsub, dir, dt, 0.5 * dt, dt / 6.0, px, py_, flag};
+    AdvectArgs A{vX0, vY0, vX1, vY1, ny, nx, py, n, nsub, dir, dt, 0.5 * dt, dt / 6.0, px, py_, flag, sq, len};
     const dim3 grid((unsigned)launch_blocks(n, ADV_BLOCK, (i64)1 << 30));
-    if (dim1) DS_KLAUNCH(k_advect<1>, grid, dim3(ADV_BLOCK), 0, st, A);
-    else DS_KLAUNCH(k_advect<2>, grid, dim3(ADV_BLOCK), 0, st, A);
+    if (sq && len) {
+        if (dim1) DS_KLAUNCH((k_advect<1, true>), grid, dim3(ADV_BLOCK), 0, st, A);
+        else DS_KLAUNCH((k_advect<2, true>), grid, dim3(ADV_BLOCK), 0, st, A);
+    } else {
+        if (dim1) DS_KLAUNCH((k_advect<1, false>), grid, dim3(ADV_BLOCK), 0, st, A);
+        else DS_KLAUNCH((k_advect<2, false>), grid, dim3(ADV_BLOCK), 0, st, A);
+    }
     DS_HIP(hipGetLastError());
     return 0;
 }
@@ -297,6 +317,125 @@ int launch_frame_l1(const Grid &g, const double *alpha, const double *weight, co
     else DS_KLAUNCH(k_frame_l1<false>, grid, block, 0, st, g, o, tl, unit, frame, partials);
     DS_HIP(hipGetLastError());
     return launch_report_rows(partials, report_tiles(g), 1, sum, st);
+}
+
+// ---------------------------------------------------------------------------------------
+// judgement of the map (dotsocp_map_report): displacement, path length and action of every particle, their mass-weighted sums
+// ---------------------------------------------------------------------------------------
+// One thread per particle, after the last interval: the per-particle values from the end position, the seed (clamped as
+// k_advect_seed clamps it) and the two sums of k_advect<., true>.  Sums: the 64 lanes of a wavefront by shuffles, the four
+// wavefronts in index order through LDS, one row of MS_COUNT partial sums per workgroup; launch_report_rows adds the
+// workgroups by k_report_final's tree, so the order depends on n alone.  Threads behind the last particle add +0.0 (every
+// term is >= 0: no bit changes).  Histogram, counts and maxima (the bit patterns of non-negative doubles order as unsigned
+// integers) go through LDS counters and are flushed with one 64-bit integer atomic per slot and workgroup.
+struct MapArgs {
+    i64 n;
+    const double *px, *py_, *sq, *len;      // end positions and path sums (the particle block)
+    const double *sx, *sy;                  // seeds as given
+    const double *mass;                     // or nullptr: every mass is 1.0
+    const double *edges;                    // DOTSOCP_REPORT_BINS + 1 doubles
+    double steps;                           // (double)((nt - 1) nsub) = 1 / |dt|
+    double *disp, *action;                  // per-particle outputs or nullptr (len is there already)
+    double *partials;                       // [MS_COUNT][workgroups]
+    unsigned long long *counts;             // [MC_COUNT]
+};
+
+template <int DIM>
+__global__ void __launch_bounds__(ADV_BLOCK) k_map_final(MapArgs a) {
+    __shared__ double s_edges[DOTSOCP_REPORT_BINS + 1];
+    __shared__ unsigned int s_cnt[DOTSOCP_REPORT_BINS + 2];               // MC_HIST .. MC_STILL
+    __shared__ unsigned long long s_key[3];
+    __shared__ double s_red[ADV_BLOCK / 64][MS_COUNT];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    if (tid < DOTSOCP_REPORT_BINS + 1) s_edges[tid] = a.edges[tid];
+    if (tid < DOTSOCP_REPORT_BINS + 2) s_cnt[tid] = 0;
+    if (tid < 3) s_key[tid] = 0;
+    __syncthreads();
+    const i64 p = (i64)blockIdx.x * ADV_BLOCK + tid;
+    double v[MS_COUNT];
+#pragma unroll
+    for (int i = 0; i < MS_COUNT; ++i) v[i] = 0.0;
+    double disp = 0.0, len = 0.0, detour = 0.0;
+    bool over = false, still = false;
+    if (p < a.n) {
+        const double dy = a.py_[p] - adv_clamp(a.sy[p]);
+        double disp2 = dy * dy;
+        if (DIM == 2) {
+            const double dx = a.px[p] - adv_clamp(a.sx[p]);
+            disp2 = dx * dx + dy * dy;
+        }
+        disp = sqrt(disp2);
+        len = a.len[p];
+        const double action = a.sq[p] * a.steps, len2 = len * len;
+        const double r = 1.0 - disp / len;
+        detour = (len > 0.0 && r > 0.0) ? r : 0.0;
+        if (a.disp) a.disp[p] = disp;
+        if (a.action) a.action[p] = action;
+        const double m = a.mass ? a.mass[p] : 1.0;
+        v[MS_MASS] = m;
+        v[MS_DISP2] = m * disp2;
+        v[MS_LEN2] = m * len2;
+        v[MS_ACTION] = m * action;
+        v[MS_DISP] = m * disp;
+        v[MS_LEN] = m * len;
+        const int j = report_bin(s_edges, detour);
+        if (j >= 0) atomicAdd(&s_cnt[MC_HIST + j], 1u);
+        over = detour > s_edges[DOTSOCP_REPORT_BINS];
+        still = len == 0.0;
+    }
+    // the two counts a rough flow sends most particles to: one LDS atomic per wavefront instead of one per lane
+    const unsigned long long b_over = __ballot(over), b_still = __ballot(still);
+    if (lane == 0) {
+        if (b_over) atomicAdd(&s_cnt[MC_OVER], (unsigned int)__popcll(b_over));
+        if (b_still) atomicAdd(&s_cnt[MC_STILL], (unsigned int)__popcll(b_still));
+    }
+    unsigned long long key[3] = {(unsigned long long)__double_as_longlong(disp), (unsigned long long)__double_as_longlong(len),
+                                 (unsigned long long)__double_as_longlong(detour)};
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        unsigned long long k = key[i];
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) {
+            const unsigned long long o = __shfl_down(k, off, 64);
+            k = o > k ? o : k;
+        }
+        if (lane == 0 && k) atomicMax(&s_key[i], k);
+    }
+#pragma unroll
+    for (int i = 0; i < MS_COUNT; ++i) {
+        double s = v[i];
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) s += __shfl_down(s, off, 64);
+        if (lane == 0) s_red[wv][i] = s;
+    }
+    __syncthreads();
+    if (tid < MS_COUNT) {
+        double s = s_red[0][tid];
+#pragma unroll
+        for (int w = 1; w < ADV_BLOCK / 64; ++w) s += s_red[w][tid];
+        a.partials[(i64)tid * gridDim.x + blockIdx.x] = s;
+    }
+    if (tid < DOTSOCP_REPORT_BINS + 2) {
+        if (s_cnt[tid]) atomicAdd(&a.counts[tid], (unsigned long long)s_cnt[tid]);
+    } else if (tid < DOTSOCP_REPORT_BINS + 5) {
+        const int k = tid - (DOTSOCP_REPORT_BINS + 2);
+        if (s_key[k]) atomicMax(&a.counts[MC_DISP_MAX + k], s_key[k]);
+    }
+}
+
+i64 map_blocks(i64 n) { return (n + ADV_BLOCK - 1) / ADV_BLOCK; }
+
+int launch_map_final(bool dim1, i64 n, const double *px, const double *py_, const double *sq, const double *len, const double *sx,
+                     const double *sy, const double *mass, const double *edges, double steps, double *disp, double *action,
+                     double *partials, double *sums, unsigned long long *counts, hipStream_t st) {
+    if (n <= 0) return 0;
+    MapArgs a{n, px, py_, sq, len, sx, sy, mass, edges, steps, disp, action, partials, counts};
+    const i64 blocks = map_blocks(n);
+    if (blocks > ((i64)1 << 30)) { set_error("invalid argument: map_report() serves up to 2^38 particles"); return DOTSOCP_EINVAL; }
+    if (dim1) DS_KLAUNCH(k_map_final<1>, dim3((unsigned)blocks), dim3(ADV_BLOCK), 0, st, a);
+    else DS_KLAUNCH(k_map_final<2>, dim3((unsigned)blocks), dim3(ADV_BLOCK), 0, st, a);
+    DS_HIP(hipGetLastError());
+    return launch_report_rows(partials, blocks, MS_COUNT, sums, st);
 }
 
 }  // namespace dotsocp

@@ -383,6 +383,14 @@ int dotsocp_push_mass(dotsocp_ctx *ctx, const double *rho0, const double *rho1, 
     return ctx->s.push_mass(rho0, rho1, o, x, y, mass, frame_nodes, frames, n_clamped, unit, l1);
 }
 
+int dotsocp_map_report(dotsocp_ctx *ctx, const double *rho0, const double *rho1, const dotsocp_advect_opts *o, double *x, double *y,
+                       const double *mass, dotsocp_map_report_t *rep, double *disp, double *len, double *action) {
+    CTX_OR_FAIL();
+    if (ctx->s.prob.dim == 1)
+        return ctx->s.map_report(rho0, rho1, o, nullptr, x, mass, rep, disp, len, action);
+    return ctx->s.map_report(rho0, rho1, o, x, y, mass, rep, disp, len, action);
+}
+
 int dotsocp_jump_next_level(dotsocp_ctx *coarse, dotsocp_ctx *fine) {
     if (!coarse || !fine) { set_error("context is NULL"); return DOTSOCP_EINVAL; }
     return fine->s.jump_from(coarse->s);
@@ -416,7 +424,7 @@ int dotsocp_kernel_time(dotsocp_ctx *ctx, const char *name, double *avg_ms, dots
     static const char *names[PH_COUNT] = {"rhs", "poisson", "cone_proj", "qstep", "beta", "kkt",
                                           "cone_fused_a", "cone_fused_b", "materialise", "comm",
                                           "interp", "acc_cone", "acc_gather", "qstep_first", "transpose", "cone_carry", "qcone",
-                                          "velocity_layer", "advect", "deposit", "frame_l1"};
+                                          "velocity_layer", "advect", "deposit", "frame_l1", "advect_path", "map_final"};
     for (int i = 0; i < PH_COUNT; ++i)
         if (strcmp(name, names[i]) == 0) {
             const i64 n = ctx->s.phase_launches[i];

@@ -34,6 +34,19 @@ __device__ __forceinline__ BlockId block_id(bool remap) {
     return b;
 }
 
+// bin of v over the DOTSOCP_REPORT_BINS + 1 edges e of dotsocp_report_edges (report.hip, advect.hip): the j with
+// e[j] <= v < e[j + 1], the last bin closed on the right; -1 outside [e[0], e[last]] and for a NaN
+__device__ __forceinline__ int report_bin(const double *e, double v) {
+    if (!(v >= e[0]) || !(v <= e[DOTSOCP_REPORT_BINS])) return -1;
+    int lo = 0, hi = DOTSOCP_REPORT_BINS;          // e[lo] <= v, and v < e[hi] or hi is the last edge
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (e[mid] <= v) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
 // Workgroup barrier that leaves the vector-memory counter alone: LDS hand-off only.  The pipelined kernels keep LDS-DMA
 // loads and global stores in flight across barriers (counted s_waitcnt vmcnt(N) of their own), which a fence would drain.
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }

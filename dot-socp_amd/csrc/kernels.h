@@ -170,10 +170,11 @@ int launch_velocity_layer(const Grid &g, const double *alpha, const double *weig
 // particles: positions SoA (px along the second array index, py along the first; 1-D: py alone), one sticky flag each
 int launch_advect_seed(bool dim1, i64 n, double *px, double *py, unsigned int *flag, hipStream_t st);     // clamp to [0, 1], flags <- 0
 // the nsub RK4 steps of one time interval between the velocity layers (vX0, vY0) of node k and (vX1, vY1) of node k + 1;
-// dt = dir / ((nt - 1) nsub)
+// dt = dir / ((nt - 1) nsub).  sq, len (n doubles each, or both nullptr): the accumulating march of dotsocp_map_report --
+// sq[p] += |step|^2, len[p] += |step| of every step, between the position before it and the one after its end clamp
 int launch_advect(bool dim1, i64 ny, i64 nx, i64 py, const double *vX0, const double *vY0, const double *vX1,
                   const double *vY1, i64 n, int nsub, int dir, double dt, double *px, double *py_, unsigned int *flag,
-                  hipStream_t st);
+                  hipStream_t st, double *sq = nullptr, double *len = nullptr);
 int launch_advect_count(const unsigned int *flag, i64 n, unsigned long long *count, hipStream_t st);       // *count += set flags
 // dotsocp_push_mass: cnt (ny x nx 64-bit counts, rows py apart, zeroed by the caller) += the bilinear split of every
 // particle's units[p] over the corners of its cell, by integer atomics (include/dotsocp.h states the rounding)
@@ -185,6 +186,18 @@ int launch_deposit(bool dim1, i64 ny, i64 nx, i64 py, i64 n, const double *px, c
 int launch_frame_l1(const Grid &g, const double *alpha, const double *weight, const double *rho0, const double *rho1,
                     const double *a_prev, double sig, double cD, i64 tl, double unit, double *frame, double *partials,
                     double *sum, hipStream_t st);
+// dotsocp_map_report, after the last interval: rows of the partial sums (mass and the mass-weighted disp^2, len^2, action,
+// disp, len) and slots of the 64-bit counters (zeroed before the launch): detour histogram, detour > last edge, len == 0,
+// and the maxima of disp, len, detour as the bit patterns of these non-negative doubles
+enum { MS_MASS = 0, MS_DISP2, MS_LEN2, MS_ACTION, MS_DISP, MS_LEN, MS_COUNT };
+enum { MC_HIST = 0, MC_OVER = DOTSOCP_REPORT_BINS, MC_STILL, MC_DISP_MAX, MC_LEN_MAX, MC_DETOUR_MAX, MC_COUNT };
+i64 map_blocks(i64 n);              // workgroups of the launch: partials holds MS_COUNT * map_blocks(n) doubles
+// px, py_, sq, len: the particle block after the march; sx, sy: the seeds as given (clamped here); mass: n doubles or nullptr
+// (all 1.0); edges: DOTSOCP_REPORT_BINS + 1 doubles; steps = (nt - 1) nsub; disp, action: n doubles each or nullptr;
+// sums[MS_COUNT] <- the totals, added by the fixed tree of launch_report_rows over the workgroups
+int launch_map_final(bool dim1, i64 n, const double *px, const double *py_, const double *sq, const double *len, const double *sx,
+                     const double *sy, const double *mass, const double *edges, double steps, double *disp, double *action,
+                     double *partials, double *sums, unsigned long long *counts, hipStream_t st);
 
 // ---------------- report.hip: the solution report (mass, negativity, f(q) histograms) in one pass over alpha and q ----------------
 // Slots of the 64-bit counters one report accumulates (device array, zeroed before the launch): the two histograms, three

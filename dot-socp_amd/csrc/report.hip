@@ -47,18 +47,6 @@ double report_key_decode(unsigned long long key, bool inverted, double none) {
     return v;
 }
 
-// bin of v: the j with e[j] <= v < e[j + 1], the last bin closed on the right; -1 outside [e[0], e[last]] and for a NaN
-__device__ __forceinline__ int report_bin(const double *e, double v) {
-    if (!(v >= e[0]) || !(v <= e[DOTSOCP_REPORT_BINS])) return -1;
-    int lo = 0, hi = DOTSOCP_REPORT_BINS;          // e[lo] <= v, and v < e[hi] or hi is the last edge
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (e[mid] <= v) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
-
 #define REP_GROUPS 16384            // workgroups a launch aims at (256 CUs x 8 resident x 8 rounds)
 
 struct ReportArgs {

@@ -135,7 +135,7 @@ bool if_adjust_sigma(double iter, double last_iter);   // IfAdjustSigma (solver_
 
 enum Phase { PH_RHS = 0, PH_POISSON, PH_PROJ, PH_QSTEP, PH_BETA, PH_KKT, PH_FUSED_A, PH_FUSED_B, PH_MATERIALISE,
              PH_COMM, PH_INTERP, PH_ACC_CONE, PH_ACC_GATHER, PH_QSTEP0, PH_TRANSPOSE, PH_CONE_CARRY, PH_QCONE, PH_VELOCITY, PH_ADVECT,
-             PH_DEPOSIT, PH_FRAME_L1, PH_COUNT };
+             PH_DEPOSIT, PH_FRAME_L1, PH_ADVECT_PATH, PH_MAP_FINAL, PH_COUNT };
 
 // The schedule of the gamma form (fused.hip, Solver::step): pure host arithmetic, also behind the C ABI.
 // rescale_due: the rescale block of iteration `it` takes its norms or rescales (solver_socp_inPALM.m:138-151), given the
@@ -297,8 +297,16 @@ struct Solver {
     };
     int push_mass(const double *rho0, const double *rho1, const dotsocp_push_opts *o, double *x, double *y, const double *mass,
                   const i64 *frame_nodes, double *frames, i64 *n_clamped, double *unit, double *l1);
+    // how good the map is (dotsocp_map_report): the same march with the path sums carried along and one reduction at its end
+    struct MapIO {
+        const double *mass;        // host: n or NULL (all 1.0)
+        dotsocp_map_report_t *rep;
+        double *disp, *len, *action;   // host: n each or NULL
+    };
+    int map_report(const double *rho0, const double *rho1, const dotsocp_advect_opts *o, double *x, double *y, const double *mass,
+                   dotsocp_map_report_t *rep, double *disp, double *len, double *action);
     int march_particles(const double *rho0, const double *rho1, i64 n, int nsub, int dir, double floor, double *x, double *y,
-                        double *traj_x, double *traj_y, i64 *n_clamped, const PushIO *push);
+                        double *traj_x, double *traj_y, i64 *n_clamped, const PushIO *push, const MapIO *map = nullptr);
 
     // ================ the inPALM loop and its profiling: solver.hip ================
     // ---- loop state (mirrors solver_socp_inPALM.m:11-135) ----

@@ -297,18 +297,51 @@ int Solver::push_mass(const double *rho0, const double *rho1, const dotsocp_push
     return march_particles(rho0, rho1, n, o->nsub, o->direction, o->rho_floor, x, y, nullptr, nullptr, n_clamped, &io);
 }
 
+// dotsocp_map_report: the march of advect_particles with the path sums carried along and one reduction at its end.  The
+// checks name this call; the masses follow the rules of push_mass.
+int Solver::map_report(const double *rho0, const double *rho1, const dotsocp_advect_opts *o, double *x, double *y, const double *mass,
+                       dotsocp_map_report_t *rep, double *disp, double *len, double *action) {
+    const bool dim1 = prob.dim == 1;
+    DS_ARG(rho0 != nullptr && rho1 != nullptr && o != nullptr && y != nullptr && (dim1 || x != nullptr),
+           "map_report() needs rho0, rho1, opts and x (2-D: y too); one of them is NULL");
+    DS_ARG(rep != nullptr, "map_report() needs rep; it is NULL");
+    DS_ARG(o->n >= 1, "map_report() needs n >= 1 particles");
+    DS_ARG(o->nsub >= 1, "map_report() needs nsub >= 1 steps per time interval");
+    DS_ARG(o->direction == 1 || o->direction == -1, "map_report() runs in direction +1 or -1");
+    DS_ARG(!remote(), "map_report() serves the slabs of one process; contexts with an RCCL communicator are not served");
+    const i64 n = o->n;
+    double mmax = mass ? 0.0 : 1.0;
+    for (i64 p = 0; p < n; ++p) {
+        DS_ARG(std::isfinite(y[p]) && (dim1 || std::isfinite(x[p])), "map_report(): a seed is not finite");
+        if (!mass) continue;
+        DS_ARG(std::isfinite(mass[p]) && mass[p] >= 0.0, "map_report(): a mass is negative or not finite");
+        mmax = mass[p] > mmax ? mass[p] : mmax;
+    }
+    DS_ARG(mmax > 0.0, "map_report(): all masses are zero");
+    if (!finished) { set_error("map_report() needs finish()"); return DOTSOCP_ESTATE; }
+    DS_CHECK(need_beta_form("map_report"));
+    DS_ARG(ny >= 2 && (dim1 || nx >= 2), "map_report() needs two nodes along every axis");
+    MapIO io{mass, rep, disp, len, action};
+    return march_particles(rho0, rho1, n, o->nsub, o->direction, o->rho_floor, x, y, nullptr, nullptr, nullptr, nullptr, &io);
+}
+
+// map != NULL: the block also carries the path sums [.. | sq (n) | len (n) | ..] (zeroed with the block), the march is
+// k_advect<., true>, and the slab that holds the block after the last interval gets one more buffer
+//   [seeds x (n) | seeds y (n) | mass (n, if given) | disp (n, if asked for) | action (n, if asked for) | edges | sums (MS_COUNT) |
+//    counters (MC_COUNT x 64 bit) | workgroup sums (MS_COUNT x map_blocks(n))]
+// and runs k_map_final on it.
 // push != NULL: the block of a slab also carries the units [.. | units (n x 64 bit) | ..] from slab to slab, and every slab
 // has [count plane / frame (plane) | tile sums (report_tiles) | l1 sums (nf)].  A frame is deposited by the slab that OWNS
 // its node (whose rho layer the comparison needs): going forward the particles are handed to the right neighbour before
 // the deposit at a slab's first node instead of before the interval behind it -- the same copy, one step earlier.  One
 // plane per slab serves all its frames: zeroing, deposit, conversion and download follow each other on the slab's stream.
 int Solver::march_particles(const double *rho0, const double *rho1, i64 n, int nsub, int dir, double floor, double *x, double *y,
-                            double *traj_x, double *traj_y, i64 *n_clamped, const PushIO *push) {
+                            double *traj_x, double *traj_y, i64 *n_clamped, const PushIO *push, const MapIO *map) {
     const bool dim1 = prob.dim == 1;
     DS_CHECK(velocity_stage(rho0, rho1));
     const double dt = (double)dir / (double)((nt - 1) * (i64)nsub);
     const size_t nb = sizeof(double) * (size_t)n;
-    const i64 nflag = (n + 1) / 2, nunit = push ? n : 0, PB = 2 * n + nunit + nflag + 1;
+    const i64 nflag = (n + 1) / 2, nunit = push ? n : 0, npath = map ? 2 * n : 0, PB = 2 * n + nunit + npath + nflag + 1;
     const size_t S = slabs.size();
     const i64 plane = slabs[0].g.plane, tiles = report_tiles(slabs[0].g), nf = push ? push->nf : 0;
     std::vector<double> l1_host((size_t)(nf * (i64)S));     // host side of the copies: outlives the blocks' last sync
@@ -326,11 +359,33 @@ int Solver::march_particles(const double *rho0, const double *rho1, i64 n, int n
             blocks.bufs.push_back(b);
         }
     }
+    // map: bufs[S] on the slab that runs the last interval; host side of its copies: outlives the last sync
+    const size_t fin = dir > 0 ? S - 1 : 0;
+    const i64 mblocks = map_blocks(n), m_mass = 2 * n, m_disp = m_mass + (map && map->mass ? n : 0),
+              m_act = m_disp + (map && map->disp ? n : 0), m_edges = m_act + (map && map->action ? n : 0),
+              m_sums = m_edges + DOTSOCP_REPORT_BINS + 1, m_counts = m_sums + MS_COUNT, m_part = m_counts + MC_COUNT;
+    double edges[DOTSOCP_REPORT_BINS + 1], msums[MS_COUNT] = {0};
+    unsigned long long mcounts[MC_COUNT] = {0};
+    if (map) {
+        Slab &s = slabs[fin];
+        DS_CHECK(use(s));
+        double *b = nullptr;
+        DS_CHECK(dmalloc(&b, m_part + MS_COUNT * mblocks));
+        blocks.bufs.push_back(b);
+        report_edges_host(edges);
+        if (!dim1) DS_HIP(ds_memcpy_async(b, x, nb, hipMemcpyHostToDevice, s.st));
+        DS_HIP(ds_memcpy_async(b + n, y, nb, hipMemcpyHostToDevice, s.st));
+        if (map->mass) DS_HIP(ds_memcpy_async(b + m_mass, map->mass, nb, hipMemcpyHostToDevice, s.st));
+        DS_HIP(ds_memcpy_async(b + m_edges, edges, sizeof edges, hipMemcpyHostToDevice, s.st));
+        DS_HIP(ds_memset_async(b + m_counts, 0, sizeof(unsigned long long) * MC_COUNT, s.st));
+    }
     auto PX = [&](size_t k) { return blocks.bufs[k]; };
     auto PY = [&](size_t k) { return blocks.bufs[k] + n; };
     auto UN = [&](size_t k) { return (i64 *)(blocks.bufs[k] + 2 * n); };
-    auto FL = [&](size_t k) { return (unsigned int *)(blocks.bufs[k] + 2 * n + nunit); };
-    auto CT = [&](size_t k) { return (unsigned long long *)(blocks.bufs[k] + 2 * n + nunit + nflag); };
+    auto SQ = [&](size_t k) { return map ? blocks.bufs[k] + 2 * n + nunit : nullptr; };
+    auto LN = [&](size_t k) { return map ? blocks.bufs[k] + 3 * n + nunit : nullptr; };
+    auto FL = [&](size_t k) { return (unsigned int *)(blocks.bufs[k] + 2 * n + nunit + npath); };
+    auto CT = [&](size_t k) { return (unsigned long long *)(blocks.bufs[k] + 2 * n + nunit + npath + nflag); };
     auto FR = [&](size_t k) { return blocks.bufs[S + k]; };
     const i64 hplane = ny * nx;
     // positions of slab `k` -> column `node` of the trajectories
@@ -390,10 +445,11 @@ int Solver::march_particles(const double *rho0, const double *rho1, i64 n, int n
         DS_CHECK(use(s));
         const double *L0 = s.adv_vel + 2 * s.g.plane * (k & 1), *L1 = s.adv_vel + 2 * s.g.plane * ((k + 1) & 1);
         const bool prof = cur == 0;
-        if (prof) prof_begin(PH_ADVECT);
+        const int ph = map ? PH_ADVECT_PATH : PH_ADVECT;
+        if (prof) prof_begin(ph);
         DS_CHECK(launch_advect(dim1, ny, nx, s.g.py, L0, L0 + s.g.plane, L1, L1 + s.g.plane, n, nsub, dir, dt, PX(cur), PY(cur),
-                               FL(cur), s.st));
-        if (prof) prof_end(PH_ADVECT);
+                               FL(cur), s.st, SQ(cur), LN(cur)));
+        if (prof) prof_end(ph);
         DS_CHECK(record(cur, dir > 0 ? k + 1 : k));
         DS_CHECK(frame_at(dir > 0 ? k + 1 : k));
     }
@@ -402,6 +458,22 @@ int Solver::march_particles(const double *rho0, const double *rho1, i64 n, int n
         Slab &s = slabs[cur];
         DS_CHECK(use(s));
         DS_CHECK(launch_advect_count(FL(cur), n, CT(cur), s.st));
+        if (map) {
+            if (cur != fin) { set_error("internal: the particles ended on slab %zu, the seeds wait on slab %zu", cur, fin); return DOTSOCP_ESTATE; }
+            double *b = blocks.bufs[S];
+            const bool prof = cur == 0;
+            if (prof) prof_begin(PH_MAP_FINAL);
+            DS_CHECK(launch_map_final(dim1, n, PX(cur), PY(cur), SQ(cur), LN(cur), b, b + n, map->mass ? b + m_mass : nullptr,
+                                      b + m_edges, (double)((nt - 1) * (i64)nsub), map->disp ? b + m_disp : nullptr,
+                                      map->action ? b + m_act : nullptr, b + m_part, b + m_sums,
+                                      (unsigned long long *)(b + m_counts), s.st));
+            if (prof) prof_end(PH_MAP_FINAL);
+            if (map->disp) DS_HIP(ds_memcpy_async(map->disp, b + m_disp, nb, hipMemcpyDeviceToHost, s.st));
+            if (map->len) DS_HIP(ds_memcpy_async(map->len, LN(cur), nb, hipMemcpyDeviceToHost, s.st));
+            if (map->action) DS_HIP(ds_memcpy_async(map->action, b + m_act, nb, hipMemcpyDeviceToHost, s.st));
+            DS_HIP(ds_memcpy_async(msums, b + m_sums, sizeof msums, hipMemcpyDeviceToHost, s.st));
+            DS_HIP(ds_memcpy_async(mcounts, b + m_counts, sizeof mcounts, hipMemcpyDeviceToHost, s.st));
+        }
         if (!dim1) DS_HIP(ds_memcpy_async(x, PX(cur), nb, hipMemcpyDeviceToHost, s.st));
         DS_HIP(ds_memcpy_async(y, PY(cur), nb, hipMemcpyDeviceToHost, s.st));
         DS_HIP(ds_memcpy_async(&count, CT(cur), sizeof count, hipMemcpyDeviceToHost, s.st));
@@ -420,6 +492,25 @@ int Solver::march_particles(const double *rho0, const double *rho1, i64 n, int n
     DS_CHECK(prof_flush());
     DS_CHECK(canary_after(*this));
     if (n_clamped) *n_clamped = (i64)count;
+    if (map) {
+        dotsocp_map_report_t *r = map->rep;
+        memset(r, 0, sizeof *r);
+        auto dbl = [&](int slot) { double v; memcpy(&v, &mcounts[slot], sizeof v); return v; };
+        r->n = n;
+        r->n_clamped = (i64)count;
+        r->n_still = (i64)mcounts[MC_STILL];
+        r->mass = msums[MS_MASS];
+        r->cost_map = msums[MS_DISP2] / r->mass;
+        r->cost_length = msums[MS_LEN2] / r->mass;
+        r->cost_action = msums[MS_ACTION] / r->mass;
+        r->disp_mean = msums[MS_DISP] / r->mass;
+        r->len_mean = msums[MS_LEN] / r->mass;
+        r->disp_max = dbl(MC_DISP_MAX);
+        r->len_max = dbl(MC_LEN_MAX);
+        r->detour_max = dbl(MC_DETOUR_MAX);
+        for (int j = 0; j < DOTSOCP_REPORT_BINS; ++j) r->detour_hist[j] = (i64)mcounts[MC_HIST + j];
+        r->detour_over = (i64)mcounts[MC_OVER];
+    }
     if (push && push->l1)
         for (i64 f = 0; f < nf; ++f) push->l1[f] = l1_host[(size_t)(nf * (i64)owner[(size_t)f] + f)] / (double)hplane;
     return 0;

@@ -307,6 +307,45 @@ class InPALMContext:
         return self.push_forward(x, y, mass=masses_on_nodes(dens, stride=stride), frames=frames, nsub=nsub, direction=direction,
                                  rho_floor=rho_floor)
 
+    def map_report(self, x, y=None, mass=None, nsub=1, direction=+1, rho_floor=None, per_particle=False):
+        """How good the flow is as a transport map, on the device (dotsocp_map_report; advect.py): the particles of
+        advect() each give their displacement, path length and kinetic action (disp^2 <= len^2 <= action, equal for
+        straight paths at constant speed); returned are their mass-weighted means (mass None: all 1), maxima, the
+        histogram of the detour 1 - disp / len, the final positions and -- per_particle=True -- the three arrays.  Same
+        keys and same bits as advect.map_report(self.outputs(), ...).  Call after finish()."""
+        m = self.model
+        one_d = not hasattr(m, "ny")
+        if one_d != (y is None):
+            raise ValueError("map_report(): y is given on a 2-D context and only there")
+        px = np.array(x, dtype=np.float64).ravel()
+        py = None if one_d else np.array(y, dtype=np.float64).ravel()
+        ms = None if mass is None else np.array(mass, dtype=np.float64).ravel()
+        if (py is not None and py.size != px.size) or (ms is not None and ms.size != px.size):
+            raise ValueError("map_report(): x, y and mass hold one entry per seed")
+        o = capi.AdvectOpts()
+        o.n, o.nsub, o.direction, o.rho_floor = int(px.size), int(nsub), int(direction), self._rho_floor(rho_floor)
+        arr = [np.empty(px.size) if per_particle else None for _ in range(3)]
+        ptr = lambda a: None if a is None else capi.fptr(a)                 # noqa: E731
+        r0, r1 = self._rho_ends()
+        rep = capi.MapReport()
+        capi.check(capi.lib().dotsocp_map_report(self._ctx, capi.fptr(r0), capi.fptr(r1), ctypes.byref(o), ptr(px), ptr(py),
+                                                 ptr(ms), ctypes.byref(rep), ptr(arr[0]), ptr(arr[1]), ptr(arr[2])))
+        out = {k: (int if t is capi.i64 else float)(getattr(rep, k)) for k, t in capi.MapReport._fields_ if k != "detour_hist"}
+        out.update(detour_hist=np.array(rep.detour_hist[:], dtype=np.int64), x=px, y=py, disp=arr[0], len=arr[1], action=arr[2])
+        return out
+
+    def map_report_from_nodes(self, stride=1, nsub=1, direction=+1, rho_floor=None, per_particle=False):
+        """map_report() of the given density itself: a particle on every stride-th node (advect.seeds_on_nodes) with the
+        value of rho0 there as its mass (direction=-1: of rho1, carried back from t = 1), as push_from_nodes() seeds
+        them: cost_map is then the cost of the map the flow realises, to set beside report()["cost"]."""
+        from .advect import masses_on_nodes, seeds_on_nodes
+        m = self.model
+        one_d = not hasattr(m, "ny")
+        dens = np.asarray(m.rho0 if int(direction) > 0 else m.rho1, dtype=np.float64)
+        x, y = seeds_on_nodes(int(m.nx), None if one_d else int(m.ny), stride=stride)
+        return self.map_report(x, y, mass=masses_on_nodes(dens, stride=stride), nsub=nsub, direction=direction,
+                               rho_floor=rho_floor, per_particle=per_particle)
+
     def close(self):
         if getattr(self, "_ctx", None):
             capi.lib().dotsocp_destroy(self._ctx)
@@ -402,7 +441,7 @@ def _weights_mode(weight, weights, transfer, weighted=True):
 
 
 def _solve_levels(rho0, rho1, nt, levelN, opts, method, dim, weighted, device, barrier=None, transfer="device",
-                  weights=None, report=False, advect=None, push=None):
+                  weights=None, report=False, advect=None, push=None, map_report=None):
     """The level loop of solver_dotsocp2d.m:154-250 (dot1d / wdot2d twins): restrict the data to
     levelN grids, solve coarse to fine with warm starts; every solve runs on the device.
     transfer = "device": the state never leaves the GPU -- jump_nextLevel and the output recovery run there
@@ -421,7 +460,10 @@ def _solve_levels(rho0, rho1, nt, levelN, opts, method, dim, weighted, device, b
     result.  Needs transfer="device".
     push = dict(stride=..., frames=..., nsub=..., direction=..., rho_floor=...): the keyword arguments of
     InPALMContext.push_from_nodes() -- the given density carried along the solved flow and deposited at the frame nodes --
-    asked of the last level's context; output["push"] holds its result.  Needs transfer="device"."""
+    asked of the last level's context; output["push"] holds its result.  Needs transfer="device".
+    map_report = dict(stride=..., nsub=..., direction=..., rho_floor=...): the keyword arguments of
+    InPALMContext.map_report_from_nodes() -- what the map realised by the flow costs and how straight and steady its paths
+    are -- asked of the last level's context; output["map_report"] holds its result.  Needs transfer="device"."""
     from . import multilevel as ML
     from .examples import ensure_barrier_validity
     if not (isinstance(levelN, (int, np.integer)) and levelN >= 1):
@@ -434,6 +476,8 @@ def _solve_levels(rho0, rho1, nt, levelN, opts, method, dim, weighted, device, b
         raise ValueError("advect= needs transfer='device' (the particles move through the device-resident state)")
     if push is not None and transfer != "device":
         raise ValueError("push= needs transfer='device' (the mass moves through the device-resident state)")
+    if map_report is not None and transfer != "device":
+        raise ValueError("map_report= needs transfer='device' (the particles move through the device-resident state)")
     wopt = _get(opts, "weight") if weighted else None
     weights = _weights_mode(wopt, weights, transfer, weighted)
     wdev = weights == "device"
@@ -518,6 +562,8 @@ def _solve_levels(rho0, rho1, nt, levelN, opts, method, dim, weighted, device, b
                     output["advect"] = ctx.advect(**advect)
                 if push is not None:
                     output["push"] = ctx.push_from_nodes(**push)
+                if map_report is not None:
+                    output["map_report"] = ctx.map_report_from_nodes(**map_report)
             if not on_device:
                 ctx.close()
                 recoverOrgVar(var)
@@ -553,35 +599,36 @@ def _solve_levels(rho0, rho1, nt, levelN, opts, method, dim, weighted, device, b
 
 
 def solver_dotsocp2d(rho0, rho1, nt, levelN, opts, method="inPALM", device=0, transfer="device", report=False,
-                     advect=None, push=None):
+                     advect=None, push=None, map_report=None):
     """[output, timeML, runHistML, runHist] = solver_dotsocp2d(rho0, rho1, nt, levelN, opts, method)
     socp/dot2d/solver_dotsocp2d.m:1.  report=True: output["report"] = the device-side solution report; advect=dict(x=..., y=...,
     ...): output["advect"] = the particles carried along the solved flow; push=dict(stride=..., frames=..., ...):
-    output["push"] = the given density carried along it and deposited at the frame nodes (all three: _solve_levels)."""
+    output["push"] = the given density carried along it and deposited at the frame nodes; map_report=dict(stride=..., ...):
+    output["map_report"] = cost, straightness and steadiness of the map the flow realises (all four: _solve_levels)."""
     output, timeML, runHistML, runHist = _solve_levels(rho0, rho1, nt, levelN, opts, method, 2, False, device,
-                                                       transfer=transfer, report=report, advect=advect, push=push)
+                                                       transfer=transfer, report=report, advect=advect, push=push, map_report=map_report)
     if not check_massConservation(output["rho"], 1e-2):
         print("Warning: The mass conservation constraint violation exceeds 0.01")
     return output, timeML, runHistML, runHist
 
 
 def solver_dotsocp1d(rho0, rho1, nt, levelN, opts, method="inPALM", device=0, transfer="device", report=False,
-                     advect=None, push=None):
-    """socp/dot1d/solver_dotsocp1d.m:1.  report, advect, push: as for solver_dotsocp2d."""
+                     advect=None, push=None, map_report=None):
+    """socp/dot1d/solver_dotsocp1d.m:1.  report, advect, push, map_report: as for solver_dotsocp2d."""
     output, timeML, runHistML, runHist = _solve_levels(rho0, rho1, nt, levelN, opts, method, 1, False, device,
-                                                       transfer=transfer, report=report, advect=advect, push=push)
+                                                       transfer=transfer, report=report, advect=advect, push=push, map_report=map_report)
     if not check_massConservation(output["rho"], 1e-2):
         print("Warning: The mass conservation constraint violation exceeds 0.01")
     return output, timeML, runHistML, runHist
 
 
 def solver_wdotsocp2d(rho0, rho1, nt, levelN, opts, method="inPALM", barrier=None, device=0, transfer="device",
-                      weights=None, report=False, advect=None, push=None):
+                      weights=None, report=False, advect=None, push=None, map_report=None):
     """socp/wdot2d/solver_wdotsocp2d.m:1.  opts["weight"]: the Nq array, or a SpaceWeight (examples.py); weights:
-    where the levels' weights are made, "host" or "device" (_solve_levels); report, advect, push: as for solver_dotsocp2d."""
+    where the levels' weights are made, "host" or "device" (_solve_levels); report, advect, push, map_report: as for solver_dotsocp2d."""
     output, timeML, runHistML, runHist = _solve_levels(rho0, rho1, nt, levelN, opts, method, 2, True, device,
                                                        barrier=barrier, transfer=transfer, weights=weights, report=report,
-                                                       advect=advect, push=push)
+                                                       advect=advect, push=push, map_report=map_report)
     if not check_massConservation(output["rho"], 1e-2):
         print("Warning: The tolerance of mass conservation constraint is under 0.01")
     return output, timeML, runHistML, runHist

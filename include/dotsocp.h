@@ -412,6 +412,63 @@ int dotsocp_push_mass(dotsocp_ctx *ctx, const double *rho0, const double *rho1, 
                       double *x, double *y, const double *mass, const dotsocp_i64 *frame_nodes, double *frames,
                       dotsocp_i64 *n_clamped, double *unit, double *l1);
 
+/* How good the map is as a transport map: what it costs, whether the particles travel straight lines at constant speed,
+ * and how that compares with the Eulerian `cost` of dotsocp_solution_report -- three numbers per particle from the march
+ * of dotsocp_advect_particles, reduced on the device.  Over the whole march (total time 1) exact arithmetic gives
+ * disp^2 <= len^2 <= action, the first with equality iff the path is straight, the second iff the speed is constant; for
+ * the optimal map all three are |T(x) - x|^2 and their mass-weighted mean is W2^2.
+ *
+ * Trajectories.  Exactly those of dotsocp_advect_particles with the same rho0, rho1, n, nsub, direction, rho_floor and
+ *   seeds: final x / y and n_clamped carry the same bits.
+ * Per particle (no contraction of a * b + c; positions after the seed clamp and after the clamp at the END of a step, so
+ *   a particle pressed against a wall adds only what it actually moved):
+ *     start:      x0 = clamp(seed_x);  y0 = clamp(seed_y);  sq = 0.0;  len = 0.0
+ *     every RK4 step, (xo, yo) the position before it and (x, y) the one after its end clamp, in march order (across
+ *     intervals and slabs):
+ *                 ex = x - xo;  ey = y - yo;  s2 = ex * ex + ey * ey  (1-D: s2 = ex * ex);
+ *                 sq = sq + s2;  len = len + sqrt(s2)
+ *     end:        dx = x - x0;  dy = y - y0;  disp2 = dx * dx + dy * dy  (1-D: dx * dx);  disp = sqrt(disp2);
+ *                 action = sq * (double)((nt - 1) * nsub);  len2 = len * len;
+ *                 r = 1.0 - disp / len;  detour = (len > 0.0 && r > 0.0) ? r : 0.0
+ *   sqrt is the correctly rounded IEEE square root.
+ * Masses.  One per particle, finite, >= 0, not all zero (the rules of dotsocp_push_mass); mass == NULL: every m_p = 1.0.
+ * Sums.  S[q] = sum_p t_p with t_p = m_p, m_p * disp2_p, m_p * len2_p, m_p * action_p, m_p * disp_p, m_p * len_p, each added
+ *   by the same tree, which depends on n alone (two calls and any slab split give the same bits):
+ *     1. the particles are padded with terms +0.0 to a multiple of 256; block B holds particles 256 B .. 256 B + 255, its
+ *        wavefront w the 64 of them from 64 w on;
+ *     2. wavefront: for off = 32, 16, 8, 4, 2, 1:  t[l] = t[l] + t[l + off] for l < off;  the wavefront's sum is t[0];
+ *     3. block: ((w0 + w1) + w2) + w3;
+ *     4. blocks: thread u = 0 .. 255 adds  v_u = 0.0;  v_u = v_u + block[u + 256 k], k = 0, 1, ..  while u + 256 k is a
+ *        block;  then for off = 128, 64, .., 1:  v[u] = v[u] + v[u + off] for u < off;  the total is v[0]
+ *        (the tree of dotsocp_solution_report's layer sums over its tiles).
+ *   mass = S[0];  cost_map = S[1] / mass;  cost_length = S[2] / mass;  cost_action = S[3] / mass;  disp_mean = S[4] / mass;
+ *   len_mean = S[5] / mass.  No floating-point atomic anywhere.
+ * Order-free (integer atomics): disp_max, len_max, detour_max over ALL n particles (geometry, not mass); n_still = particles
+ *   with len == 0.0; detour_hist = counts of detour_p over the edges of dotsocp_report_edges with the bin rule of
+ *   dotsocp_solution_report (edges[j] <= y < edges[j+1], the last bin also y == edges[last], values below edges[0] -- a
+ *   straight path's 0 among them -- in no bin); detour_over = count of detour_p > edges[last] = 0.1: paths more than
+ *   about 10 % longer than straight.
+ * advect.map_report restates all of it in numpy with the same bits.
+ *
+ * Valid where dotsocp_advect_particles is (after finish(); all loops, weighted, 1-D; one slab, `nslabs` slabs,
+ * dotsocp_create_multi: sq and len travel with the particles, the slab that holds them after the last interval receives
+ * the seeds and masses and reduces).  DOTSOCP_EINVAL: what dotsocp_advect_particles refuses, a NULL rep, a mass that is
+ * negative or not finite, all masses zero. */
+typedef struct {
+    dotsocp_i64 n, n_clamped, n_still;
+    double mass;                                 /* sum of the masses */
+    double cost_map, cost_length, cost_action;   /* mass-weighted means of disp^2 <= len^2 <= action */
+    double disp_mean, len_mean;                  /* mass-weighted means of disp, len */
+    double disp_max, len_max, detour_max;        /* over all n particles */
+    dotsocp_i64 detour_hist[DOTSOCP_REPORT_BINS];
+    dotsocp_i64 detour_over;
+} dotsocp_map_report_t;
+/* o, x, y: as for dotsocp_advect_particles (x, y in: seeds, out: final positions; y NULL for 1-D).  mass: n doubles or NULL.
+ * disp, len, action: n doubles each, the per-particle values; each may be NULL. */
+int dotsocp_map_report(dotsocp_ctx *ctx, const double *rho0, const double *rho1, const dotsocp_advect_opts *o,
+                       double *x, double *y, const double *mass, dotsocp_map_report_t *rep, double *disp, double *len,
+                       double *action);
+
 /* Multilevel transfer on the device: socp/dot2d/utils/jump_nextLevel.m:5-16 with
  * interpolate.m:20-84, between the finished context `coarse` and the context `fine` of the next level (created
  * from the fine level's InitialScaling scalars, c and weight uploaded, begin() not yet called; grid
@@ -476,7 +533,9 @@ int dotsocp_get_history(dotsocp_ctx *ctx, double *kkt, double *time, double *ite
  * (the cone passes that read gamma and no q^{k-1}; "cone_fused_b" keeps the passes that move 8 (20 Nz + 3 Nq) bytes),
  * "qcone" (a q-step with the next iteration's gamma-reading cone pass in the same kernel: counted here alone),
  * "velocity_layer", "advect" (the launches of dotsocp_recover_velocity / dotsocp_advect_particles on the first slab),
- * "deposit", "frame_l1" (the per-frame launches of dotsocp_push_mass on the first slab). */
+ * "deposit", "frame_l1" (the per-frame launches of dotsocp_push_mass on the first slab), "advect_path" (the accumulating
+ * march of dotsocp_map_report on the first slab: counted here, not under "advect"), "map_final" (its one reduction, when
+ * the first slab runs it: one slab, or direction -1). */
 int dotsocp_set_profiling(dotsocp_ctx *ctx, int on);
 int dotsocp_kernel_time(dotsocp_ctx *ctx, const char *name, double *avg_ms, dotsocp_i64 *launches);
 

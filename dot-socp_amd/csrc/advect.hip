@@ -20,13 +20,6 @@
 
 namespace dotsocp {
 
-// a(.) of outputs_node.h with the weight's presence known at compile time (as report.hip's rep_a)
-template <bool WEIGHTED>
-__device__ __forceinline__ double vel_a(const OutArgs &o, i64 k) {
-    const double v = o.cD * (o.sig * o.alpha[k]);
-    return WEIGHTED ? o.weight[k] * v : v;
-}
-
 // v = E / rho where rho > floor and the quotient is finite, else 0: the field is finite everywhere (a NaN density fails
 // the comparison)
 __device__ __forceinline__ double vel_quot(double E, double rho, double floor) {
@@ -43,23 +36,20 @@ __global__ void __launch_bounds__(TILE_Y *TILE_X) k_velocity_layer(Grid g, OutAr
     if (y >= g.ny || x >= g.nx) return;
     const i64 tg = g.t0 + tl, col = y + g.py * x, node = col + g.plane * tl;
     const bool ends = (tg == 0 || tg == g.nt - 1);
-    double rho;
-    if (tg == 0) rho = o.rho0[col];
-    else if (tg == g.nt - 1) rho = o.rho1[col];
-    else rho = out_mean2(tl == 0 ? o.a_prev[col] : vel_a<WEIGHTED>(o, node - g.plane), vel_a<WEIGHTED>(o, node));
+    const double rho = out_rho<WEIGHTED>(g, o, tg, tl, col, node);
     const double f = ends ? 2.0 : 1.0;
     if (DIM == 2) {
         double Ex = 0.0;
         if (x >= 1 && x <= g.nx - 2) {
             const i64 e = out_edge_x(g, y, x, tl);
-            Ex = out_flux(vel_a<WEIGHTED>(o, e - g.py), vel_a<WEIGHTED>(o, e), f);
+            Ex = out_flux(out_a<WEIGHTED>(o, e - g.py), out_a<WEIGHTED>(o, e), f);
         }
         vX[col] = vel_quot(Ex, rho, floor);
     }
     double Ey = 0.0;
     if (y >= 1 && y <= g.ny - 2) {
         const i64 e = out_edge_y(g, y, x, tl);
-        Ey = out_flux(vel_a<WEIGHTED>(o, e - 1), vel_a<WEIGHTED>(o, e), f);
+        Ey = out_flux(out_a<WEIGHTED>(o, e - 1), out_a<WEIGHTED>(o, e), f);
     }
     vY[col] = vel_quot(Ey, rho, floor);
 }
@@ -287,10 +277,7 @@ __global__ void __launch_bounds__(TILE_Y *TILE_X) k_frame_l1(Grid g, OutArgs o, 
     double v = 0.0;
     if (y < g.ny && x < g.nx) {
         const i64 tg = g.t0 + tl, col = y + g.py * x, node = col + g.plane * tl;
-        double rho;
-        if (tg == 0) rho = o.rho0[col];
-        else if (tg == g.nt - 1) rho = o.rho1[col];
-        else rho = out_mean2(tl == 0 ? o.a_prev[col] : vel_a<WEIGHTED>(o, node - g.plane), vel_a<WEIGHTED>(o, node));
+        const double rho = out_rho<WEIGHTED>(g, o, tg, tl, col, node);
         const double f = (double)__double_as_longlong(frame[col]) * unit;
         frame[col] = f;
         v = fabs(f - rho);

@@ -2,6 +2,7 @@
 #pragma once
 #include "common.h"
 #include "defer.h"
+#include "particle_block.h"
 
 namespace dotsocp {
 
@@ -189,8 +190,7 @@ int launch_frame_l1(const Grid &g, const double *alpha, const double *weight, co
 // dotsocp_map_report, after the last interval: rows of the partial sums (mass and the mass-weighted disp^2, len^2, action,
 // disp, len) and slots of the 64-bit counters (zeroed before the launch): detour histogram, detour > last edge, len == 0,
 // and the maxima of disp, len, detour as the bit patterns of these non-negative doubles
-enum { MS_MASS = 0, MS_DISP2, MS_LEN2, MS_ACTION, MS_DISP, MS_LEN, MS_COUNT };
-enum { MC_HIST = 0, MC_OVER = DOTSOCP_REPORT_BINS, MC_STILL, MC_DISP_MAX, MC_LEN_MAX, MC_DETOUR_MAX, MC_COUNT };
+// (MS_* rows, MC_* slots: particle_block.h)
 i64 map_blocks(i64 n);              // workgroups of the launch: partials holds MS_COUNT * map_blocks(n) doubles
 // px, py_, sq, len: the particle block after the march; sx, sy: the seeds as given (clamped here); mass: n doubles or nullptr
 // (all 1.0); edges: DOTSOCP_REPORT_BINS + 1 doubles; steps = (nt - 1) nsub; disp, action: n doubles each or nullptr;

@@ -1,6 +1,6 @@
 // The per-node / per-cell expressions of the driver outputs (recover_RhoE.m:14-25, recover_q.m:12-22 after recoverOrgVar),
-// shared by k_outputs (transfer.hip), which stores them, and k_report (report.hip), which only judges them: both must
-// produce the same bits, so every factor and every average is stated once, here.
+// shared by k_outputs (transfer.hip), which stores them, k_report (report.hip), which only judges them, and the velocity and
+// frame kernels of advect.hip: all must produce the same bits, so every factor and every average is stated once, here.
 //   a(k) = [w(k) *] (cD * (sig * alpha(k)))   sigma of finish(), cScale * D of recoverOrgVar, weight of wdot2d/utils/recover_RhoE.m:11
 //   b(k) = dD * q(k)
 #pragma once
@@ -20,10 +20,26 @@ __device__ __forceinline__ double out_a(const OutArgs &a, i64 k) {
     return a.weight ? a.weight[k] * v : v;
 }
 
+// ... with the weight's presence known at compile time: no branch between the loads of a layer
+template <bool WEIGHTED>
+__device__ __forceinline__ double out_a(const OutArgs &a, i64 k) {
+    const double v = a.cD * (a.sig * a.alpha[k]);
+    return WEIGHTED ? a.weight[k] * v : v;
+}
+
 __device__ __forceinline__ double out_b(const OutArgs &a, i64 k) { return a.dD * a.q[k]; }
 
 // rho between two cells, the x / y average of two edge values of q, and the t average of two such averages
 __device__ __forceinline__ double out_mean2(double lo, double hi) { return (lo + hi) / 2; }
+
+// rho at node `node` = col + g.plane * tl of the slab (global layer tg): the given ends, else the mean of the cell below
+// (on the slab's first layer: a_prev) and the cell here
+template <bool WEIGHTED>
+__device__ __forceinline__ double out_rho(const Grid &g, const OutArgs &o, i64 tg, i64 tl, i64 col, i64 node) {
+    if (tg == 0) return o.rho0[col];
+    if (tg == g.nt - 1) return o.rho1[col];
+    return out_mean2(tl == 0 ? o.a_prev[col] : out_a<WEIGHTED>(o, node - g.plane), out_a<WEIGHTED>(o, node));
+}
 
 // Ex / Ey at a node from the two edges around it; f = 2 on the first and last time layer, else 1
 __device__ __forceinline__ double out_flux(double lo, double hi, double f) { return (lo * f + hi * f) / 2; }

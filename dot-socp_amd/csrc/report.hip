@@ -59,13 +59,6 @@ struct ReportArgs {
     unsigned long long *counts;     // [RC_COUNT]
 };
 
-// a(.) / b(.) of outputs_node.h with the weight's presence known at compile time: no branch between the loads of a layer
-template <bool WEIGHTED>
-__device__ __forceinline__ double rep_a(const OutArgs &o, i64 k) {
-    const double v = o.cD * (o.sig * o.alpha[k]);
-    return WEIGHTED ? o.weight[k] * v : v;
-}
-
 template <bool WEIGHTED>
 __global__ void __launch_bounds__(TILE_Y *TILE_X) k_report(Grid g, ReportArgs a) {
     __shared__ double s_edges[REP_EDGES];
@@ -96,7 +89,7 @@ __global__ void __launch_bounds__(TILE_Y *TILE_X) k_report(Grid g, ReportArgs a)
     {
         const bool head = tbeg < g.ncl;             // the chunk starts on a cell layer
         const i64 ex = head ? ex0 + exs * tbeg : safe, ey = head ? ey0 + eys * tbeg : safe;
-        const double ab = rep_a<WEIGHTED>(o, tbeg > 0 ? col + g.plane * (tbeg - 1) : safe);
+        const double ab = out_a<WEIGHTED>(o, tbeg > 0 ? col + g.plane * (tbeg - 1) : safe);
         const double ap = g.first ? 0.0 : o.a_prev[col];
         const double bxl = out_b(o, ex - (head ? exd : 0)), bxh = out_b(o, ex);
         const double byl = out_b(o, ey - (head ? eyd : 0)), byh = out_b(o, ey);
@@ -115,9 +108,9 @@ __global__ void __launch_bounds__(TILE_Y *TILE_X) k_report(Grid g, ReportArgs a)
         const i64 ax = ex0 + exs * tl, ay = ey0 + eys * tl;                 // alpha edges of node layer tl (always owned)
         const i64 qx = cell ? ex0 + exs * (tl + 1) : safe, qy = cell ? ey0 + eys * (tl + 1) : safe;   // b edges of layer tl + 1
         const i64 qxd = cell ? exd : 0, qyd = cell ? eyd : 0;
-        const double a_here = rep_a<WEIGHTED>(o, node);
-        const double axl = rep_a<WEIGHTED>(o, ax - exd), axh = rep_a<WEIGHTED>(o, ax);
-        const double ayl = rep_a<WEIGHTED>(o, ay - eyd), ayh = rep_a<WEIGHTED>(o, ay);
+        const double a_here = out_a<WEIGHTED>(o, node);
+        const double axl = out_a<WEIGHTED>(o, ax - exd), axh = out_a<WEIGHTED>(o, ax);
+        const double ayl = out_a<WEIGHTED>(o, ay - eyd), ayh = out_a<WEIGHTED>(o, ay);
         const double q0 = out_b(o, node);
         const double bxl = out_b(o, qx - qxd), bxh = out_b(o, qx);
         const double byl = out_b(o, qy - qyd), byh = out_b(o, qy);

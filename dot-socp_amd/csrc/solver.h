@@ -258,7 +258,7 @@ struct Solver {
     int tri_exchange(bool back);
     int poisson_t_tridiag(const PhiHooks *hooks);
 
-    // ================ host <-> device fields, driver steps on the device: solver_io.hip ================
+    // ================ host <-> device fields, outputs, report, multilevel transfer: solver_io.hip ================
     i64 field_len(int field) const;
     // rows of `rowlen` doubles between a device array with rows `pitch` apart and an array in the reference layout: a host
     // array (dir = ROWS_DOWN / ROWS_UP; `false` / `true` of the callers), or one on device `src_dev` that is read
@@ -274,12 +274,18 @@ struct Solver {
     // c is zero off its two end layers (model.c of initialize.m:42-50): the q-step, k_rhs and the sigma fix skip the rest
     bool c_ends_on = true;       // DOTSOCP_C_ENDS=0: load all of c
     int detect_c_ends();
+    // what every reader of the node density stages (outputs, report, velocity)
+    int stage_left_tail();
+    int stage_rho_ends(Slab &s, const double *rho0, const double *rho1);
+    int canary_after();          // DOTSOCP_CANARY=1: the guard bands, checked while the buffers of a call are live
     int recover_outputs(const double *rho0, const double *rho1, double *rho, double *Ex, double *Ey, double *q0,
                         double *bx, double *by);
     int jump_from(Solver &coarse);
     // mass / negativity / f(q) histograms / cost of the finished solve in one pass over alpha and q (report.hip);
     // layer_mass, layer_neg: nt doubles each or NULL
     int solution_report(const double *rho0, const double *rho1, dotsocp_report *rep, double *layer_mass, double *layer_neg);
+
+    // ================ velocity and particles along it: solver_particles.hip ================
     // v = E / rho at the nodes and particles along it (advect.hip).  Coordinates of the engine: X along the second array
     // index, Y along the first; a 1-D problem lives in Y (capi.hip hands its x over as y).
     int velocity_stage(const double *rho0, const double *rho1);          // rho0 / rho1 / a_prev in place, rings empty
@@ -287,26 +293,11 @@ struct Solver {
     int recover_velocity(const double *rho0, const double *rho1, double floor, double *vX, double *vY);
     int advect_particles(const double *rho0, const double *rho1, const dotsocp_advect_opts *o, double *x, double *y,
                          double *traj_x, double *traj_y, i64 *n_clamped);
-    // the mass the particles carry, deposited at the requested nodes (dotsocp_push_mass): the same march with frames
-    struct PushIO {
-        const i64 *units;          // n: units per particle (host)
-        const i64 *nodes;          // nf ascending frame nodes
-        i64 nf;
-        double unit;
-        double *frames, *l1;       // host: ny x nx x nf; nf or NULL
-    };
+    // the same march with the particles' mass deposited at the requested nodes, or with the path sums and one reduction at its end
     int push_mass(const double *rho0, const double *rho1, const dotsocp_push_opts *o, double *x, double *y, const double *mass,
                   const i64 *frame_nodes, double *frames, i64 *n_clamped, double *unit, double *l1);
-    // how good the map is (dotsocp_map_report): the same march with the path sums carried along and one reduction at its end
-    struct MapIO {
-        const double *mass;        // host: n or NULL (all 1.0)
-        dotsocp_map_report_t *rep;
-        double *disp, *len, *action;   // host: n each or NULL
-    };
     int map_report(const double *rho0, const double *rho1, const dotsocp_advect_opts *o, double *x, double *y, const double *mass,
                    dotsocp_map_report_t *rep, double *disp, double *len, double *action);
-    int march_particles(const double *rho0, const double *rho1, i64 n, int nsub, int dir, double floor, double *x, double *y,
-                        double *traj_x, double *traj_y, i64 *n_clamped, const PushIO *push, const MapIO *map = nullptr);
 
     // ================ the inPALM loop and its profiling: solver.hip ================
     // ---- loop state (mirrors solver_socp_inPALM.m:11-135) ----
@@ -436,6 +427,20 @@ struct Solver {
     bool palm_p_valid = false; // p2 / sxp / syp hold the second gather of the last cone pass
     int palm_begin();
     int palm_step(bool *brk);
+};
+
+// Device scratch of one call: released once every stream of the context is idle, on the error paths too
+struct DeviceScratch {
+    Solver &S;
+    std::vector<double *> bufs;
+    explicit DeviceScratch(Solver &s) : S(s) {}
+    int alloc(double **p, i64 n) { DS_CHECK(dmalloc(p, n)); bufs.push_back(*p); return 0; }      // on the current device
+    ~DeviceScratch() {
+        if (bufs.empty()) return;
+        S.cur_dev = -1;
+        (void)S.sync_all();
+        for (double *b : bufs) dfree(b);
+    }
 };
 
 }  // namespace dotsocp

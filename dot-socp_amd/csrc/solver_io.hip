@@ -1,7 +1,8 @@
-// Device-side driver steps around the loop: the multilevel transfer
-// jump_nextLevel (+ recoverOrgVar of the coarse level, InitialScaling of the fine one) and the outputs
-// recover_RhoE / recover_q.  Kernels: transfer.hip.  Both work on in-process time slabs (dotsocp_create_multi).
-// Below them: the fields between host and device (upload, upload_layers, download, the zero test of c at begin()).
+// Driver steps on the device around the loop and the fields between host and device, on in-process time slabs too:
+//   * the outputs recover_RhoE / recover_q (kernels: transfer.hip) and the solution report
+//     (report.hip), with the staging of the density's ends that they share with the velocity (solver_particles.hip);
+//   * the multilevel transfer jump_nextLevel (+ recoverOrgVar of the coarse level, InitialScaling of the fine one; row 2);
+//   * upload, upload_layers, download, the zero test of c at begin().
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -9,6 +10,32 @@
 #include "solver.h"
 
 namespace dotsocp {
+
+// Time slabs: a(.) of every slab's last cell, for the density at the right neighbour's first node (k_out_tail -> a0_prev)
+int Solver::stage_left_tail() {
+    if (!multi()) return 0;
+    const double cD = cScale * D;                          // recoverOrgVar (solver_dotsocp2d.m:368-386)
+    FOR_SLABS(s)
+        if (!s.g.last) DS_CHECK(launch_out_tail(s.g, s.alpha, s.weight, sigma, cD, s.send_plane, s.st));
+    return shift(+1, [](Slab &s) { return s.send_plane; }, [](Slab &s) { return s.a0_prev; }, slabs[0].g.plane);
+}
+
+// rho0 / rho1 -> the first / second layer of w1 (w1 holds at least two layers: nt >= 2 per slab)
+int Solver::stage_rho_ends(Slab &s, const double *rho0, const double *rho1) {
+    const Grid &g = slabs[0].g;
+    if (s.g.first) DS_CHECK(copy_rows(s.w1, const_cast<double *>(rho0), ny, g.py, nx, true, s.st));
+    if (s.g.last) DS_CHECK(copy_rows(s.w1 + g.plane, const_cast<double *>(rho1), ny, g.py, nx, true, s.st));
+    return 0;
+}
+
+int Solver::canary_after() {
+    if (!canary_enabled()) return 0;
+    std::string what;
+    const int bad = canary_check(&what);
+    cur_dev = -1;
+    if (bad) set_error("canary: %d device buffer(s) written out of bounds: %s", bad, what.c_str());
+    return bad ? DOTSOCP_EHIP : 0;
+}
 
 // solver_dotsocp2d.m:262-281 on the device; call after finish().  Any output pointer may be NULL.  Time slabs: every
 // slab produces its own layers (the density at its first node needs the left neighbour's last cell: one ny x nx layer
@@ -25,11 +52,7 @@ int Solver::recover_outputs(const double *rho0, const double *rho1, double *rho,
     const i64 hplane = ny * nx;                            // host layers (reference layout)
     const i64 py = slabs[0].g.py;
     const double cD = cScale * D, dD = dScale / D;         // recoverOrgVar (solver_dotsocp2d.m:368-386)
-    if (rho && multi()) {
-        FOR_SLABS(s)
-            if (!s.g.last) DS_CHECK(launch_out_tail(s.g, s.alpha, s.weight, sigma, cD, s.send_plane, s.st));
-        DS_CHECK(shift(+1, [](Slab &s) { return s.send_plane; }, [](Slab &s) { return s.a0_prev; }, plane));
-    }
+    if (rho) DS_CHECK(stage_left_tail());
     double *outs[6] = {rho, Ex, Ey, q0, bx, by};
     for (int which = 0; which < 6; ++which) {
         if (!outs[which]) continue;
@@ -40,13 +63,9 @@ int Solver::recover_outputs(const double *rho0, const double *rho1, double *rho,
         }
         FOR_SLABS(s) {
             const Grid &g = s.g;
-            double *d_r0 = s.w1, *d_r1 = s.w1 + plane;     // w1 holds at least two layers (nt >= 2 per slab)
-            if (which == 0) {
-                if (g.first) DS_CHECK(copy_rows(d_r0, const_cast<double *>(rho0), ny, py, nx, true, s.st));
-                if (g.last) DS_CHECK(copy_rows(d_r1, const_cast<double *>(rho1), ny, py, nx, true, s.st));
-            }
+            if (which == 0) DS_CHECK(stage_rho_ends(s, rho0, rho1));
             const i64 layers = (which >= 3) ? g.ncl : g.ntl;
-            DS_CHECK(launch_outputs(g, s.q, s.alpha, s.weight, d_r0, d_r1, s.a0_prev, sigma, cD, dD, which, s.w0, s.st));
+            DS_CHECK(launch_outputs(g, s.q, s.alpha, s.weight, s.w1, s.w1 + plane, s.a0_prev, sigma, cD, dD, which, s.w0, s.st));
             double *h = outs[which] + (remote() ? 0 : hplane * g.t0);
             if (layers > 0) DS_CHECK(copy_rows(s.w0, h, ny, py, nx * layers, false, s.st));
         }
@@ -67,13 +86,9 @@ int Solver::solution_report(const double *rho0, const double *rho1, dotsocp_repo
     DS_CHECK(need_q("solution_report"));
     cur_dev = -1;
     DS_CHECK(use_dev(device));
-    const i64 plane = slabs[0].g.plane, py = slabs[0].g.py;
+    const i64 plane = slabs[0].g.plane;
     const double cD = cScale * D, dD = dScale / D;         // recoverOrgVar (solver_dotsocp2d.m:368-386)
-    if (multi()) {
-        FOR_SLABS(s)
-            if (!s.g.last) DS_CHECK(launch_out_tail(s.g, s.alpha, s.weight, sigma, cD, s.send_plane, s.st));
-        DS_CHECK(shift(+1, [](Slab &s) { return s.send_plane; }, [](Slab &s) { return s.a0_prev; }, plane));
-    }
+    DS_CHECK(stage_left_tail());
     // host side of the copies: lives until the sync_all() below
     double edges[DOTSOCP_REPORT_BINS + 1];
     report_edges_host(edges);
@@ -88,27 +103,17 @@ int Solver::solution_report(const double *rho0, const double *rho1, dotsocp_repo
             DS_CHECK(s.alloc(&s.rep_sums, 3 * g.ntl));
             DS_CHECK(s.alloc(&s.rep_counts, RC_COUNT));
         }
-        double *d_r0 = s.w1, *d_r1 = s.w1 + plane;         // w1 holds at least two layers (nt >= 2 per slab)
-        if (g.first) DS_CHECK(copy_rows(d_r0, const_cast<double *>(rho0), ny, py, nx, true, s.st));
-        if (g.last) DS_CHECK(copy_rows(d_r1, const_cast<double *>(rho1), ny, py, nx, true, s.st));
+        DS_CHECK(stage_rho_ends(s, rho0, rho1));
         DS_HIP(ds_memcpy_async(s.rep_edges, edges, sizeof edges, hipMemcpyHostToDevice, s.st));
         DS_HIP(ds_memset_async(s.rep_counts, 0, sizeof(unsigned long long) * RC_COUNT, s.st));
-        DS_CHECK(launch_report(g, s.q, s.alpha, s.weight, d_r0, d_r1, s.a0_prev, sigma, cD, dD, prob.dim == 1, s.rep_edges,
+        DS_CHECK(launch_report(g, s.q, s.alpha, s.weight, s.w1, s.w1 + plane, s.a0_prev, sigma, cD, dD, prob.dim == 1, s.rep_edges,
                                s.rep_part, s.rep_sums, s.rep_counts, s.st));
         DS_HIP(ds_memcpy_async(sums.data() + 3 * g.t0, s.rep_sums, sizeof(double) * 3 * g.ntl, hipMemcpyDeviceToHost, s.st));
         DS_HIP(ds_memcpy_async(counts.data() + RC_COUNT * k++, s.rep_counts, sizeof(unsigned long long) * RC_COUNT,
                                hipMemcpyDeviceToHost, s.st));
     }
     DS_CHECK(sync_all());
-    if (canary_enabled()) {        // DOTSOCP_CANARY=1: the report's kernels wrote inside their buffers
-        std::string what;
-        const int bad = canary_check(&what);
-        cur_dev = -1;
-        if (bad) {
-            set_error("canary: %d device buffer(s) written out of bounds: %s", bad, what.c_str());
-            return DOTSOCP_EHIP;
-        }
-    }
+    DS_CHECK(canary_after());                   // the report's kernels wrote inside their buffers
     memset(rep, 0, sizeof *rep);
     const i64 hplane = ny * nx;
     rep->n_nodes = hplane * nt;
@@ -140,379 +145,6 @@ int Solver::solution_report(const double *rho0, const double *rho1, dotsocp_repo
     }
     rep->rho_min = report_key_decode(kmin, true, INFINITY);
     rep->fq_max = report_key_decode(kmax, false, -INFINITY);
-    return 0;
-}
-
-// --------------------------------------------------------------------------------------
-// Velocity v = E / rho and particles along it (advect.hip; semantics: include/dotsocp.h).  The velocity exists one node
-// layer at a time: every slab keeps a ring of two layers, slot (global node & 1), filled by k_velocity_layer from the
-// slab's own alpha -- or, for the node behind a slab's last cell, by its right neighbour, which owns that node, and copied
-// over.  Staging as for solution_report: rho0 / rho1 in w1, the left neighbour's last cell through k_out_tail / shift.
-// --------------------------------------------------------------------------------------
-int Solver::velocity_stage(const double *rho0, const double *rho1) {
-    cur_dev = -1;
-    DS_CHECK(use_dev(device));
-    const i64 plane = slabs[0].g.plane, py = slabs[0].g.py;
-    const double cD = cScale * D;                          // recoverOrgVar (solver_dotsocp2d.m:368-386)
-    if (multi()) {
-        FOR_SLABS(s)
-            if (!s.g.last) DS_CHECK(launch_out_tail(s.g, s.alpha, s.weight, sigma, cD, s.send_plane, s.st));
-        DS_CHECK(shift(+1, [](Slab &s) { return s.send_plane; }, [](Slab &s) { return s.a0_prev; }, plane));
-    }
-    FOR_SLABS(s) {
-        if (!s.adv_vel) DS_CHECK(s.zalloc(&s.adv_vel, 4 * plane));
-        s.adv_have[0] = s.adv_have[1] = -1;
-        if (s.g.first) DS_CHECK(copy_rows(s.w1, const_cast<double *>(rho0), ny, py, nx, true, s.st));
-        if (s.g.last) DS_CHECK(copy_rows(s.w1 + plane, const_cast<double *>(rho1), ny, py, nx, true, s.st));
-    }
-    return 0;
-}
-
-int Solver::velocity_layer(Slab &s, i64 tg, double floor) {
-    const int slot = (int)(tg & 1);
-    if (s.adv_have[slot] == tg) return 0;
-    const Grid &g = s.g;
-    const i64 plane = g.plane;
-    double *dst = s.adv_vel + 2 * plane * slot;
-    if (tg >= g.t0 && tg < g.t0 + g.ntl) {
-        DS_CHECK(use(s));
-        const bool prof = &s == &slabs[0];
-        if (prof) prof_begin(PH_VELOCITY);
-        DS_CHECK(launch_velocity_layer(g, s.alpha, s.weight, s.w1, s.w1 + plane, s.a0_prev, sigma, cScale * D, prob.dim == 1,
-                                       tg - g.t0, floor, dst, dst + plane, s.st));
-        if (prof) prof_end(PH_VELOCITY);
-    } else {
-        const size_t r = (size_t)(&s - slabs.data()) + 1;
-        if (tg != g.t0 + g.ntl || r >= slabs.size()) { set_error("internal: velocity layer %lld is not this slab's", tg); return DOTSOCP_ESTATE; }
-        DS_CHECK(velocity_layer(slabs[r], tg, floor));
-        DS_CHECK(xcopy(slabs[r], slabs[r].adv_vel + 2 * plane * slot, s, dst, 2 * plane));
-    }
-    s.adv_have[slot] = tg;
-    return 0;
-}
-
-// the guard bands of DOTSOCP_CANARY=1, checked while the buffers of the call are live
-static int canary_after(Solver &S) {
-    if (!canary_enabled()) return 0;
-    std::string what;
-    const int bad = canary_check(&what);
-    S.cur_dev = -1;
-    if (bad) {
-        set_error("canary: %d device buffer(s) written out of bounds: %s", bad, what.c_str());
-        return DOTSOCP_EHIP;
-    }
-    return 0;
-}
-
-int Solver::recover_velocity(const double *rho0, const double *rho1, double floor, double *vX, double *vY) {
-    DS_ARG(rho0 != nullptr && rho1 != nullptr, "recover_velocity() needs rho0 and rho1 (one of them is NULL)");
-    DS_ARG(!remote(), "recover_velocity() serves the slabs of one process; contexts with an RCCL communicator are not served");
-    if (!finished) { set_error("recover_velocity() needs finish()"); return DOTSOCP_ESTATE; }
-    DS_CHECK(need_beta_form("recover_velocity"));
-    DS_CHECK(velocity_stage(rho0, rho1));
-    const i64 hplane = ny * nx;
-    FOR_SLABS(s) {
-        const Grid &g = s.g;
-        for (i64 tl = 0; tl < g.ntl; ++tl) {
-            const i64 tg = g.t0 + tl;
-            DS_CHECK(velocity_layer(s, tg, floor));
-            double *d = s.adv_vel + 2 * g.plane * (tg & 1);
-            if (vX) DS_CHECK(copy_rows(d, vX + hplane * tg, ny, g.py, nx, false, s.st));
-            if (vY) DS_CHECK(copy_rows(d + g.plane, vY + hplane * tg, ny, g.py, nx, false, s.st));
-        }
-    }
-    DS_CHECK(sync_all());
-    DS_CHECK(prof_flush());
-    return canary_after(*this);
-}
-
-// particle block of one slab: [px (n) | py (n) | flags (n x 32 bit) | count (64 bit)], in doubles
-struct ParticleBlocks {
-    Solver &S;
-    std::vector<double *> bufs;
-    explicit ParticleBlocks(Solver &s) : S(s) {}
-    ~ParticleBlocks() {
-        if (bufs.empty()) return;
-        S.cur_dev = -1;
-        (void)S.sync_all();
-        for (double *b : bufs) dfree(b);
-    }
-};
-
-int Solver::advect_particles(const double *rho0, const double *rho1, const dotsocp_advect_opts *o, double *x, double *y,
-                             double *traj_x, double *traj_y, i64 *n_clamped) {
-    const bool dim1 = prob.dim == 1;
-    DS_ARG(rho0 != nullptr && rho1 != nullptr && o != nullptr && y != nullptr && (dim1 || x != nullptr),
-           "advect_particles() needs rho0, rho1, opts and x (2-D: y too); one of them is NULL");
-    DS_ARG(o->n >= 1, "advect_particles() needs n >= 1 particles");
-    DS_ARG(o->nsub >= 1, "advect_particles() needs nsub >= 1 steps per time interval");
-    DS_ARG(o->direction == 1 || o->direction == -1, "advect_particles() runs in direction +1 or -1");
-    DS_ARG(!remote(), "advect_particles() serves the slabs of one process; contexts with an RCCL communicator are not served");
-    const i64 n = o->n;
-    for (i64 p = 0; p < n; ++p)
-        DS_ARG(std::isfinite(y[p]) && (dim1 || std::isfinite(x[p])), "advect_particles(): a seed is not finite");
-    if (!finished) { set_error("advect_particles() needs finish()"); return DOTSOCP_ESTATE; }
-    DS_CHECK(need_beta_form("advect_particles"));
-    DS_ARG(ny >= 2 && (dim1 || nx >= 2), "advect_particles() needs two nodes along every axis");
-    return march_particles(rho0, rho1, n, o->nsub, o->direction, o->rho_floor, x, y, traj_x, traj_y, n_clamped, nullptr);
-}
-
-// dotsocp_push_mass: the march of advect_particles with a deposit at the requested nodes.  The checks name this call; the
-// units per particle are formed here, on the host (one division by a power of two and one rounding each).
-int Solver::push_mass(const double *rho0, const double *rho1, const dotsocp_push_opts *o, double *x, double *y,
-                      const double *mass, const i64 *frame_nodes, double *frames, i64 *n_clamped, double *unit, double *l1) {
-    const bool dim1 = prob.dim == 1;
-    DS_ARG(rho0 != nullptr && rho1 != nullptr && o != nullptr && y != nullptr && (dim1 || x != nullptr),
-           "push_mass() needs rho0, rho1, opts and x (2-D: y too); one of them is NULL");
-    DS_ARG(mass != nullptr && frame_nodes != nullptr && frames != nullptr,
-           "push_mass() needs mass, frame_nodes and frames; one of them is NULL");
-    DS_ARG(o->n >= 1, "push_mass() needs n >= 1 particles");
-    DS_ARG(o->nsub >= 1, "push_mass() needs nsub >= 1 steps per time interval");
-    DS_ARG(o->direction == 1 || o->direction == -1, "push_mass() runs in direction +1 or -1");
-    DS_ARG(o->nf >= 1, "push_mass() needs nf >= 1 frame nodes");
-    DS_ARG(!remote(), "push_mass() serves the slabs of one process; contexts with an RCCL communicator are not served");
-    for (i64 k = 0; k < o->nf; ++k)
-        DS_ARG(frame_nodes[k] >= 0 && frame_nodes[k] < nt && (k == 0 || frame_nodes[k] > frame_nodes[k - 1]),
-               "push_mass(): frame_nodes must be strictly ascending node indices in [0, nt)");
-    const i64 n = o->n;
-    double mmax = 0.0;
-    for (i64 p = 0; p < n; ++p) {
-        DS_ARG(std::isfinite(y[p]) && (dim1 || std::isfinite(x[p])), "push_mass(): a seed is not finite");
-        DS_ARG(std::isfinite(mass[p]) && mass[p] >= 0.0, "push_mass(): a mass is negative or not finite");
-        mmax = mass[p] > mmax ? mass[p] : mmax;
-    }
-    DS_ARG(mmax > 0.0, "push_mass(): all masses are zero");
-    const double top = (double)n * mmax;
-    int e = 0;
-    (void)frexp(top, &e);
-    const double u = ldexp(1.0, e - 50);
-    DS_ARG(std::isfinite(top) && u >= 2.2250738585072014e-308, "push_mass(): n * max(mass) overflows, or its unit 2^(e-50) is not a normal double");
-    if (!finished) { set_error("push_mass() needs finish()"); return DOTSOCP_ESTATE; }
-    DS_CHECK(need_beta_form("push_mass"));
-    DS_ARG(ny >= 2 && (dim1 || nx >= 2), "push_mass() needs two nodes along every axis");
-    std::vector<i64> units((size_t)n);
-    for (i64 p = 0; p < n; ++p) units[(size_t)p] = llrint(mass[p] / u);
-    PushIO io{units.data(), frame_nodes, o->nf, u, frames, l1};
-    if (unit) *unit = u;
-    return march_particles(rho0, rho1, n, o->nsub, o->direction, o->rho_floor, x, y, nullptr, nullptr, n_clamped, &io);
-}
-
-// dotsocp_map_report: the march of advect_particles with the path sums carried along and one reduction at its end.  The
-// checks name this call; the masses follow the rules of push_mass.
-int Solver::map_report(const double *rho0, const double *rho1, const dotsocp_advect_opts *o, double *x, double *y, const double *mass,
-                       dotsocp_map_report_t *rep, double *disp, double *len, double *action) {
-    const bool dim1 = prob.dim == 1;
-    DS_ARG(rho0 != nullptr && rho1 != nullptr && o != nullptr && y != nullptr && (dim1 || x != nullptr),
-           "map_report() needs rho0, rho1, opts and x (2-D: y too); one of them is NULL");
-    DS_ARG(rep != nullptr, "map_report() needs rep; it is NULL");
-    DS_ARG(o->n >= 1, "map_report() needs n >= 1 particles");
-    DS_ARG(o->nsub >= 1, "map_report() needs nsub >= 1 steps per time interval");
-    DS_ARG(o->direction == 1 || o->direction == -1, "map_report() runs in direction +1 or -1");
-    DS_ARG(!remote(), "map_report() serves the slabs of one process; contexts with an RCCL communicator are not served");
-    const i64 n = o->n;
-    double mmax = mass ? 0.0 : 1.0;
-    for (i64 p = 0; p < n; ++p) {
-        DS_ARG(std::isfinite(y[p]) && (dim1 || std::isfinite(x[p])), "map_report(): a seed is not finite");
-        if (!mass) continue;
-        DS_ARG(std::isfinite(mass[p]) && mass[p] >= 0.0, "map_report(): a mass is negative or not finite");
-        mmax = mass[p] > mmax ? mass[p] : mmax;
-    }
-    DS_ARG(mmax > 0.0, "map_report(): all masses are zero");
-    if (!finished) { set_error("map_report() needs finish()"); return DOTSOCP_ESTATE; }
-    DS_CHECK(need_beta_form("map_report"));
-    DS_ARG(ny >= 2 && (dim1 || nx >= 2), "map_report() needs two nodes along every axis");
-    MapIO io{mass, rep, disp, len, action};
-    return march_particles(rho0, rho1, n, o->nsub, o->direction, o->rho_floor, x, y, nullptr, nullptr, nullptr, nullptr, &io);
-}
-
-// map != NULL: the block also carries the path sums [.. | sq (n) | len (n) | ..] (zeroed with the block), the march is
-// k_advect<., true>, and the slab that holds the block after the last interval gets one more buffer
-//   [seeds x (n) | seeds y (n) | mass (n, if given) | disp (n, if asked for) | action (n, if asked for) | edges | sums (MS_COUNT) |
-//    counters (MC_COUNT x 64 bit) | workgroup sums (MS_COUNT x map_blocks(n))]
-// and runs k_map_final on it.
-// push != NULL: the block of a slab also carries the units [.. | units (n x 64 bit) | ..] from slab to slab, and every slab
-// has [count plane / frame (plane) | tile sums (report_tiles) | l1 sums (nf)].  A frame is deposited by the slab that OWNS
-// its node (whose rho layer the comparison needs): going forward the particles are handed to the right neighbour before
-// the deposit at a slab's first node instead of before the interval behind it -- the same copy, one step earlier.  One
-// plane per slab serves all its frames: zeroing, deposit, conversion and download follow each other on the slab's stream.
-int Solver::march_particles(const double *rho0, const double *rho1, i64 n, int nsub, int dir, double floor, double *x, double *y,
-                            double *traj_x, double *traj_y, i64 *n_clamped, const PushIO *push, const MapIO *map) {
-    const bool dim1 = prob.dim == 1;
-    DS_CHECK(velocity_stage(rho0, rho1));
-    const double dt = (double)dir / (double)((nt - 1) * (i64)nsub);
-    const size_t nb = sizeof(double) * (size_t)n;
-    const i64 nflag = (n + 1) / 2, nunit = push ? n : 0, npath = map ? 2 * n : 0, PB = 2 * n + nunit + npath + nflag + 1;
-    const size_t S = slabs.size();
-    const i64 plane = slabs[0].g.plane, tiles = report_tiles(slabs[0].g), nf = push ? push->nf : 0;
-    std::vector<double> l1_host((size_t)(nf * (i64)S));     // host side of the copies: outlives the blocks' last sync
-    std::vector<size_t> owner((size_t)nf);
-    ParticleBlocks blocks(*this);
-    FOR_SLABS(s) {
-        double *b = nullptr;
-        DS_CHECK(dmalloc(&b, PB));
-        blocks.bufs.push_back(b);
-    }
-    if (push) {                     // bufs[S + k]: the frame buffers of slab k
-        FOR_SLABS(s) {
-            double *b = nullptr;
-            DS_CHECK(dmalloc(&b, plane + tiles + nf));
-            blocks.bufs.push_back(b);
-        }
-    }
-    // map: bufs[S] on the slab that runs the last interval; host side of its copies: outlives the last sync
-    const size_t fin = dir > 0 ? S - 1 : 0;
-    const i64 mblocks = map_blocks(n), m_mass = 2 * n, m_disp = m_mass + (map && map->mass ? n : 0),
-              m_act = m_disp + (map && map->disp ? n : 0), m_edges = m_act + (map && map->action ? n : 0),
-              m_sums = m_edges + DOTSOCP_REPORT_BINS + 1, m_counts = m_sums + MS_COUNT, m_part = m_counts + MC_COUNT;
-    double edges[DOTSOCP_REPORT_BINS + 1], msums[MS_COUNT] = {0};
-    unsigned long long mcounts[MC_COUNT] = {0};
-    if (map) {
-        Slab &s = slabs[fin];
-        DS_CHECK(use(s));
-        double *b = nullptr;
-        DS_CHECK(dmalloc(&b, m_part + MS_COUNT * mblocks));
-        blocks.bufs.push_back(b);
-        report_edges_host(edges);
-        if (!dim1) DS_HIP(ds_memcpy_async(b, x, nb, hipMemcpyHostToDevice, s.st));
-        DS_HIP(ds_memcpy_async(b + n, y, nb, hipMemcpyHostToDevice, s.st));
-        if (map->mass) DS_HIP(ds_memcpy_async(b + m_mass, map->mass, nb, hipMemcpyHostToDevice, s.st));
-        DS_HIP(ds_memcpy_async(b + m_edges, edges, sizeof edges, hipMemcpyHostToDevice, s.st));
-        DS_HIP(ds_memset_async(b + m_counts, 0, sizeof(unsigned long long) * MC_COUNT, s.st));
-    }
-    auto PX = [&](size_t k) { return blocks.bufs[k]; };
-    auto PY = [&](size_t k) { return blocks.bufs[k] + n; };
-    auto UN = [&](size_t k) { return (i64 *)(blocks.bufs[k] + 2 * n); };
-    auto SQ = [&](size_t k) { return map ? blocks.bufs[k] + 2 * n + nunit : nullptr; };
-    auto LN = [&](size_t k) { return map ? blocks.bufs[k] + 3 * n + nunit : nullptr; };
-    auto FL = [&](size_t k) { return (unsigned int *)(blocks.bufs[k] + 2 * n + nunit + npath); };
-    auto CT = [&](size_t k) { return (unsigned long long *)(blocks.bufs[k] + 2 * n + nunit + npath + nflag); };
-    auto FR = [&](size_t k) { return blocks.bufs[S + k]; };
-    const i64 hplane = ny * nx;
-    // positions of slab `k` -> column `node` of the trajectories
-    auto record = [&](size_t k, i64 node) -> int {
-        if (traj_x && !dim1) DS_HIP(ds_memcpy_async(traj_x + n * node, PX(k), nb, hipMemcpyDeviceToHost, slabs[k].st));
-        if (traj_y) DS_HIP(ds_memcpy_async(traj_y + n * node, PY(k), nb, hipMemcpyDeviceToHost, slabs[k].st));
-        return 0;
-    };
-    size_t cur = dir > 0 ? 0 : slabs.size() - 1;
-    auto hand_over = [&]() -> int {
-        const size_t nxt = dir > 0 ? cur + 1 : cur - 1;
-        if (nxt >= slabs.size()) { set_error("internal: the particles left the last slab"); return DOTSOCP_ESTATE; }
-        DS_CHECK(xcopy(slabs[cur], PX(cur), slabs[nxt], PX(nxt), PB));
-        cur = nxt;
-        return 0;
-    };
-    // the particles stand at `node`: if it is the next requested frame, deposit, convert, compare and download it
-    i64 fi = dir > 0 ? 0 : nf - 1;
-    auto frame_at = [&](i64 node) -> int {
-        if (!push || fi < 0 || fi >= nf || push->nodes[fi] != node) return 0;
-        while (dir > 0 && node >= slabs[cur].g.t0 + slabs[cur].g.ntl) DS_CHECK(hand_over());
-        Slab &s = slabs[cur];
-        const Grid &g = s.g;
-        if (node < g.t0 || node >= g.t0 + g.ntl) { set_error("internal: frame node %lld is not this slab's", node); return DOTSOCP_ESTATE; }
-        DS_CHECK(use(s));
-        double *F = FR(cur);
-        const bool prof = cur == 0;
-        DS_HIP(ds_memset_async(F, 0, sizeof(double) * (size_t)plane, s.st));
-        if (prof) prof_begin(PH_DEPOSIT);
-        DS_CHECK(launch_deposit(dim1, ny, nx, g.py, n, PX(cur), PY(cur), UN(cur), (unsigned long long *)F, s.st));
-        if (prof) { prof_end(PH_DEPOSIT); prof_begin(PH_FRAME_L1); }
-        DS_CHECK(launch_frame_l1(g, s.alpha, s.weight, s.w1, s.w1 + plane, s.a0_prev, sigma, cScale * D, node - g.t0, push->unit, F,
-                                 F + plane, F + plane + tiles + fi, s.st));
-        if (prof) prof_end(PH_FRAME_L1);
-        DS_CHECK(copy_rows(F, push->frames + hplane * fi, ny, g.py, nx, false, s.st));
-        owner[(size_t)fi] = cur;
-        fi += dir;
-        return 0;
-    };
-    {
-        Slab &s = slabs[cur];
-        DS_CHECK(use(s));
-        DS_HIP(ds_memset_async(PX(cur), 0, sizeof(double) * (size_t)PB, s.st));
-        if (!dim1) DS_HIP(ds_memcpy_async(PX(cur), x, nb, hipMemcpyHostToDevice, s.st));
-        DS_HIP(ds_memcpy_async(PY(cur), y, nb, hipMemcpyHostToDevice, s.st));
-        if (push) DS_HIP(ds_memcpy_async(UN(cur), push->units, nb, hipMemcpyHostToDevice, s.st));
-        DS_CHECK(launch_advect_seed(dim1, n, PX(cur), PY(cur), FL(cur), s.st));
-        DS_CHECK(record(cur, dir > 0 ? 0 : nt - 1));
-        DS_CHECK(frame_at(dir > 0 ? 0 : nt - 1));
-    }
-    for (i64 step = 0; step < nt - 1; ++step) {
-        const i64 k = dir > 0 ? step : nt - 2 - step;      // the interval between nodes k and k + 1: run by the slab that owns cell k
-        while (k < slabs[cur].g.t0 || k >= slabs[cur].g.t0 + slabs[cur].g.ncl) DS_CHECK(hand_over());
-        Slab &s = slabs[cur];
-        DS_CHECK(velocity_layer(s, k, floor));
-        DS_CHECK(velocity_layer(s, k + 1, floor));
-        DS_CHECK(use(s));
-        const double *L0 = s.adv_vel + 2 * s.g.plane * (k & 1), *L1 = s.adv_vel + 2 * s.g.plane * ((k + 1) & 1);
-        const bool prof = cur == 0;
-        const int ph = map ? PH_ADVECT_PATH : PH_ADVECT;
-        if (prof) prof_begin(ph);
-        DS_CHECK(launch_advect(dim1, ny, nx, s.g.py, L0, L0 + s.g.plane, L1, L1 + s.g.plane, n, nsub, dir, dt, PX(cur), PY(cur),
-                               FL(cur), s.st, SQ(cur), LN(cur)));
-        if (prof) prof_end(ph);
-        DS_CHECK(record(cur, dir > 0 ? k + 1 : k));
-        DS_CHECK(frame_at(dir > 0 ? k + 1 : k));
-    }
-    unsigned long long count = 0;
-    {
-        Slab &s = slabs[cur];
-        DS_CHECK(use(s));
-        DS_CHECK(launch_advect_count(FL(cur), n, CT(cur), s.st));
-        if (map) {
-            if (cur != fin) { set_error("internal: the particles ended on slab %zu, the seeds wait on slab %zu", cur, fin); return DOTSOCP_ESTATE; }
-            double *b = blocks.bufs[S];
-            const bool prof = cur == 0;
-            if (prof) prof_begin(PH_MAP_FINAL);
-            DS_CHECK(launch_map_final(dim1, n, PX(cur), PY(cur), SQ(cur), LN(cur), b, b + n, map->mass ? b + m_mass : nullptr,
-                                      b + m_edges, (double)((nt - 1) * (i64)nsub), map->disp ? b + m_disp : nullptr,
-                                      map->action ? b + m_act : nullptr, b + m_part, b + m_sums,
-                                      (unsigned long long *)(b + m_counts), s.st));
-            if (prof) prof_end(PH_MAP_FINAL);
-            if (map->disp) DS_HIP(ds_memcpy_async(map->disp, b + m_disp, nb, hipMemcpyDeviceToHost, s.st));
-            if (map->len) DS_HIP(ds_memcpy_async(map->len, LN(cur), nb, hipMemcpyDeviceToHost, s.st));
-            if (map->action) DS_HIP(ds_memcpy_async(map->action, b + m_act, nb, hipMemcpyDeviceToHost, s.st));
-            DS_HIP(ds_memcpy_async(msums, b + m_sums, sizeof msums, hipMemcpyDeviceToHost, s.st));
-            DS_HIP(ds_memcpy_async(mcounts, b + m_counts, sizeof mcounts, hipMemcpyDeviceToHost, s.st));
-        }
-        if (!dim1) DS_HIP(ds_memcpy_async(x, PX(cur), nb, hipMemcpyDeviceToHost, s.st));
-        DS_HIP(ds_memcpy_async(y, PY(cur), nb, hipMemcpyDeviceToHost, s.st));
-        DS_HIP(ds_memcpy_async(&count, CT(cur), sizeof count, hipMemcpyDeviceToHost, s.st));
-    }
-    if (push && push->l1) {
-        size_t k = 0;
-        FOR_SLABS(s) {
-            bool mine = false;
-            for (i64 f = 0; f < nf; ++f) mine = mine || owner[(size_t)f] == k;
-            if (mine) DS_HIP(ds_memcpy_async(l1_host.data() + nf * (i64)k, FR(k) + plane + tiles, sizeof(double) * (size_t)nf,
-                                             hipMemcpyDeviceToHost, s.st));
-            ++k;
-        }
-    }
-    DS_CHECK(sync_all());
-    DS_CHECK(prof_flush());
-    DS_CHECK(canary_after(*this));
-    if (n_clamped) *n_clamped = (i64)count;
-    if (map) {
-        dotsocp_map_report_t *r = map->rep;
-        memset(r, 0, sizeof *r);
-        auto dbl = [&](int slot) { double v; memcpy(&v, &mcounts[slot], sizeof v); return v; };
-        r->n = n;
-        r->n_clamped = (i64)count;
-        r->n_still = (i64)mcounts[MC_STILL];
-        r->mass = msums[MS_MASS];
-        r->cost_map = msums[MS_DISP2] / r->mass;
-        r->cost_length = msums[MS_LEN2] / r->mass;
-        r->cost_action = msums[MS_ACTION] / r->mass;
-        r->disp_mean = msums[MS_DISP] / r->mass;
-        r->len_mean = msums[MS_LEN] / r->mass;
-        r->disp_max = dbl(MC_DISP_MAX);
-        r->len_max = dbl(MC_LEN_MAX);
-        r->detour_max = dbl(MC_DETOUR_MAX);
-        for (int j = 0; j < DOTSOCP_REPORT_BINS; ++j) r->detour_hist[j] = (i64)mcounts[MC_HIST + j];
-        r->detour_over = (i64)mcounts[MC_OVER];
-    }
-    if (push && push->l1)
-        for (i64 f = 0; f < nf; ++f) push->l1[f] = l1_host[(size_t)(nf * (i64)owner[(size_t)f] + f)] / (double)hplane;
     return 0;
 }
 
@@ -675,25 +307,12 @@ static bool weight_stage_forced() {
     return e && atoi(e) != 0;
 }
 
-// Staging buffers of copy_field: released once every stream of the context is idle, on the error paths too
-struct StagedBuffers {
-    Solver &S;
-    std::vector<double *> bufs;
-    explicit StagedBuffers(Solver &s) : S(s) {}
-    ~StagedBuffers() {
-        if (bufs.empty()) return;
-        S.cur_dev = -1;
-        (void)S.sync_all();
-        for (double *b : bufs) dfree(b);
-    }
-};
-
 // `host`: the global field in the reference layout -- on the host (dir = ROWS_DOWN / ROWS_UP), or on device `src_dev`
 // (ROWS_FROM_DEV: read from there).  A slab with pitched rows on ANOTHER device than the source cannot take its rows one
 // by one (copy_rows): its three contiguous layer ranges of [q0; bx; by] travel as peer copies into a staging buffer on
 // the slab's device and the rows are spread from there.
 static int copy_field(Solver &S, int field, double *host, int up, int src_dev = -1) {
-    StagedBuffers staged(S);
+    DeviceScratch staged(S);               // staging buffers: released once every stream of the context is idle
     const i64 ny = S.ny, nx = S.nx;
     i64 ntn = S.nt, ntc = S.nt - 1;
     if (S.remote()) { ntn = S.slabs[0].g.ntl; ntc = S.slabs[0].g.ncl; }
@@ -718,8 +337,7 @@ static int copy_field(Solver &S, int field, double *host, int up, int src_dev = 
                 int from = src_dev;
                 if (up == Solver::ROWS_FROM_DEV && ((s.dev != src_dev && g.py > ny) || weight_stage_forced())) {
                     double *buf = nullptr;
-                    DS_CHECK(dmalloc(&buf, count[0] + count[1] + count[2]));
-                    staged.bufs.push_back(buf);
+                    DS_CHECK(staged.alloc(&buf, count[0] + count[1] + count[2]));
                     for (int k = 0; k < 3; ++k) {
                         if (count[k] > 0)
                             DS_HIP(ds_memcpy_peer_async(buf, s.dev, part[k], src_dev, sizeof(double) * (size_t)count[k], cur));

@@ -44,6 +44,10 @@ def _has(opts, name):
     return (name in opts) if isinstance(opts, dict) else hasattr(opts, name)
 
 
+def _ptr(a):
+    return None if a is None else capi.fptr(a)
+
+
 class InPALMContext:
     """Stateful handle on one device-resident loop (create -> upload -> begin -> run* -> finish)."""
 
@@ -235,29 +239,36 @@ class InPALMContext:
                                                        capi.fptr(v["vx"]), None if one_d else capi.fptr(v["vy"])))
         return v
 
+    def _march_inputs(self, who, x, y, mass, nsub, direction, rho_floor):
+        """What advect(), push_forward() and map_report() (`who`, named in every ValueError) hand to the library alike: one_d,
+        the seed arrays (copies: the end positions are written there), the masses or None, the opts, rho0 / rho1."""
+        one_d = not hasattr(self.model, "ny")
+        if one_d != (y is None):
+            raise ValueError("%s(): y is given on a 2-D context and only there" % who)
+        if who == "push_forward" and mass is None:
+            raise ValueError("%s(): mass is needed" % who)
+        px = np.array(x, dtype=np.float64).ravel()
+        py = None if one_d else np.array(y, dtype=np.float64).ravel()
+        ms = None if mass is None else np.array(mass, dtype=np.float64).ravel()
+        if (py is not None and py.size != px.size) or (ms is not None and ms.size != px.size):
+            raise ValueError("%s(): %s" % (who, "x and y hold the same number of seeds" if who == "advect" else
+                                           "x, y and mass hold one entry per seed"))
+        o = capi.PushOpts() if who == "push_forward" else capi.AdvectOpts()
+        o.n, o.nsub, o.direction, o.rho_floor = int(px.size), int(nsub), int(direction), self._rho_floor(rho_floor)
+        return (one_d, px, py, ms, o) + tuple(capi.fptr(r) for r in self._rho_ends())
+
     def advect(self, x, y=None, nsub=1, direction=+1, rho_floor=None, trajectories=False):
         """Particles along the solved flow on the device (dotsocp_advect_particles; advect.py): RK4 along v = E / rho from
         the seeds x, y (y None on a 1-D context) over t = 0 -> 1 (direction=+1) or 1 -> 0 (-1), nsub steps per time
         interval.  Returns dict(x, y, traj_x, traj_y, n_clamped) as advect.advect does, with the same bits as
         advect.advect(self.outputs(), ...).  Call after finish()."""
-        m = self.model
-        one_d = not hasattr(m, "ny")
-        if one_d != (y is None):
-            raise ValueError("advect(): y is given on a 2-D context and only there")
-        px = np.array(x, dtype=np.float64).ravel()
-        py = None if one_d else np.array(y, dtype=np.float64).ravel()
-        if py is not None and py.size != px.size:
-            raise ValueError("advect(): x and y hold the same number of seeds")
-        o = capi.AdvectOpts()
-        o.n, o.nsub, o.direction, o.rho_floor = int(px.size), int(nsub), int(direction), self._rho_floor(rho_floor)
-        nt = int(m.nt)
+        one_d, px, py, _, o, r0, r1 = self._march_inputs("advect", x, y, None, nsub, direction, rho_floor)
+        nt = int(self.model.nt)
         tx = np.empty((px.size, nt), order="F") if trajectories else None
         ty = np.empty((px.size, nt), order="F") if trajectories and not one_d else None
-        ptr = lambda a: None if a is None else capi.fptr(a)                 # noqa: E731
-        r0, r1 = self._rho_ends()
         nc = capi.i64()
-        capi.check(capi.lib().dotsocp_advect_particles(self._ctx, capi.fptr(r0), capi.fptr(r1), ctypes.byref(o), ptr(px), ptr(py),
-                                                       ptr(tx), ptr(ty), ctypes.byref(nc)))
+        capi.check(capi.lib().dotsocp_advect_particles(self._ctx, r0, r1, ctypes.byref(o), _ptr(px), _ptr(py), _ptr(tx), _ptr(ty),
+                                                       ctypes.byref(nc)))
         return dict(x=px, y=py, traj_x=tx, traj_y=ty, n_clamped=int(nc.value))
 
     def push_forward(self, x, y=None, mass=None, frames=None, nsub=1, direction=+1, rho_floor=None):
@@ -266,46 +277,35 @@ class InPALMContext:
         accumulation -- exact conservation, the same bits for any particle order and slab split.  Returns dict(frames,
         counts, nodes, unit, l1, x, y, n_clamped, total_units) as advect.push_forward does, with the same bits as
         advect.push_forward(self.outputs(), ...) (l1: to rounding; identical between two calls).  Call after finish()."""
+        one_d, px, py, ms, o, r0, r1 = self._march_inputs("push_forward", x, y, mass, nsub, direction, rho_floor)
         m = self.model
-        one_d = not hasattr(m, "ny")
-        if one_d != (y is None):
-            raise ValueError("push_forward(): y is given on a 2-D context and only there")
-        if mass is None:
-            raise ValueError("push_forward(): mass is needed")
-        px = np.array(x, dtype=np.float64).ravel()
-        py = None if one_d else np.array(y, dtype=np.float64).ravel()
-        ms = np.array(mass, dtype=np.float64).ravel()
-        if (py is not None and py.size != px.size) or ms.size != px.size:
-            raise ValueError("push_forward(): x, y and mass hold one entry per seed")
-        nt = int(m.nt)
-        nodes = np.arange(nt, dtype=np.int64) if frames is None else np.array(frames, dtype=np.int64).ravel()
-        o = capi.PushOpts()
-        o.n, o.nsub, o.direction, o.rho_floor, o.nf = int(px.size), int(nsub), int(direction), self._rho_floor(rho_floor), int(nodes.size)
+        nodes = np.arange(int(m.nt), dtype=np.int64) if frames is None else np.array(frames, dtype=np.int64).ravel()
+        o.nf = int(nodes.size)
         shp = (int(m.nx),) if one_d else (int(m.ny), int(m.nx))
         fr = np.empty(shp + (nodes.size,), order="F")
         l1 = np.empty(nodes.size)
-        ptr = lambda a: None if a is None else capi.fptr(a)                 # noqa: E731
-        r0, r1 = self._rho_ends()
         nc, unit = capi.i64(), capi.dbl()
-        capi.check(capi.lib().dotsocp_push_mass(self._ctx, capi.fptr(r0), capi.fptr(r1), ctypes.byref(o), ptr(px), ptr(py),
-                                                capi.fptr(ms), nodes.ctypes.data, capi.fptr(fr), ctypes.byref(nc),
-                                                ctypes.byref(unit), capi.fptr(l1)))
+        capi.check(capi.lib().dotsocp_push_mass(self._ctx, r0, r1, ctypes.byref(o), _ptr(px), _ptr(py), capi.fptr(ms),
+                                                nodes.ctypes.data, capi.fptr(fr), ctypes.byref(nc), ctypes.byref(unit), capi.fptr(l1)))
         u = unit.value
         counts = (fr / u).astype(np.int64)                 # exact: the frames are whole multiples of a power of two
         return dict(frames=fr, counts=counts, nodes=nodes, unit=u, l1=l1, x=px, y=py, n_clamped=int(nc.value),
                     total_units=int(np.rint(ms / u).astype(np.int64).sum()))
 
-    def push_from_nodes(self, stride=1, frames=None, nsub=1, direction=+1, rho_floor=None):
-        """push_forward() of the given density itself: a particle on every stride-th node (advect.seeds_on_nodes) with the
-        value of rho0 there as its mass (direction=-1: of rho1, carried back from t = 1).  With stride=1, l1 at the far end
-        is the defect of the transport map: how far the pushed rho0 is from rho1."""
+    def _node_particles(self, stride, direction):
+        """x, y, mass of the given density itself: a particle on every stride-th node (advect.seeds_on_nodes) with the value
+        of rho0 there as its mass (direction=-1: of rho1, carried back from t = 1)"""
         from .advect import masses_on_nodes, seeds_on_nodes
         m = self.model
-        one_d = not hasattr(m, "ny")
         dens = np.asarray(m.rho0 if int(direction) > 0 else m.rho1, dtype=np.float64)
-        x, y = seeds_on_nodes(int(m.nx), None if one_d else int(m.ny), stride=stride)
-        return self.push_forward(x, y, mass=masses_on_nodes(dens, stride=stride), frames=frames, nsub=nsub, direction=direction,
-                                 rho_floor=rho_floor)
+        x, y = seeds_on_nodes(int(m.nx), int(m.ny) if hasattr(m, "ny") else None, stride=stride)
+        return x, y, masses_on_nodes(dens, stride=stride)
+
+    def push_from_nodes(self, stride=1, frames=None, nsub=1, direction=+1, rho_floor=None):
+        """push_forward() of the given density itself (_node_particles).  With stride=1, l1 at the far end is the defect of
+        the transport map: how far the pushed rho0 is from rho1."""
+        x, y, mass = self._node_particles(stride, direction)
+        return self.push_forward(x, y, mass=mass, frames=frames, nsub=nsub, direction=direction, rho_floor=rho_floor)
 
     def map_report(self, x, y=None, mass=None, nsub=1, direction=+1, rho_floor=None, per_particle=False):
         """How good the flow is as a transport map, on the device (dotsocp_map_report; advect.py): the particles of
@@ -313,38 +313,20 @@ class InPALMContext:
         straight paths at constant speed); returned are their mass-weighted means (mass None: all 1), maxima, the
         histogram of the detour 1 - disp / len, the final positions and -- per_particle=True -- the three arrays.  Same
         keys and same bits as advect.map_report(self.outputs(), ...).  Call after finish()."""
-        m = self.model
-        one_d = not hasattr(m, "ny")
-        if one_d != (y is None):
-            raise ValueError("map_report(): y is given on a 2-D context and only there")
-        px = np.array(x, dtype=np.float64).ravel()
-        py = None if one_d else np.array(y, dtype=np.float64).ravel()
-        ms = None if mass is None else np.array(mass, dtype=np.float64).ravel()
-        if (py is not None and py.size != px.size) or (ms is not None and ms.size != px.size):
-            raise ValueError("map_report(): x, y and mass hold one entry per seed")
-        o = capi.AdvectOpts()
-        o.n, o.nsub, o.direction, o.rho_floor = int(px.size), int(nsub), int(direction), self._rho_floor(rho_floor)
+        _, px, py, ms, o, r0, r1 = self._march_inputs("map_report", x, y, mass, nsub, direction, rho_floor)
         arr = [np.empty(px.size) if per_particle else None for _ in range(3)]
-        ptr = lambda a: None if a is None else capi.fptr(a)                 # noqa: E731
-        r0, r1 = self._rho_ends()
         rep = capi.MapReport()
-        capi.check(capi.lib().dotsocp_map_report(self._ctx, capi.fptr(r0), capi.fptr(r1), ctypes.byref(o), ptr(px), ptr(py),
-                                                 ptr(ms), ctypes.byref(rep), ptr(arr[0]), ptr(arr[1]), ptr(arr[2])))
+        capi.check(capi.lib().dotsocp_map_report(self._ctx, r0, r1, ctypes.byref(o), _ptr(px), _ptr(py), _ptr(ms), ctypes.byref(rep),
+                                                 _ptr(arr[0]), _ptr(arr[1]), _ptr(arr[2])))
         out = {k: (int if t is capi.i64 else float)(getattr(rep, k)) for k, t in capi.MapReport._fields_ if k != "detour_hist"}
         out.update(detour_hist=np.array(rep.detour_hist[:], dtype=np.int64), x=px, y=py, disp=arr[0], len=arr[1], action=arr[2])
         return out
 
     def map_report_from_nodes(self, stride=1, nsub=1, direction=+1, rho_floor=None, per_particle=False):
-        """map_report() of the given density itself: a particle on every stride-th node (advect.seeds_on_nodes) with the
-        value of rho0 there as its mass (direction=-1: of rho1, carried back from t = 1), as push_from_nodes() seeds
-        them: cost_map is then the cost of the map the flow realises, to set beside report()["cost"]."""
-        from .advect import masses_on_nodes, seeds_on_nodes
-        m = self.model
-        one_d = not hasattr(m, "ny")
-        dens = np.asarray(m.rho0 if int(direction) > 0 else m.rho1, dtype=np.float64)
-        x, y = seeds_on_nodes(int(m.nx), None if one_d else int(m.ny), stride=stride)
-        return self.map_report(x, y, mass=masses_on_nodes(dens, stride=stride), nsub=nsub, direction=direction,
-                               rho_floor=rho_floor, per_particle=per_particle)
+        """map_report() of the given density itself, seeded as push_from_nodes() seeds it (_node_particles): cost_map is then
+        the cost of the map the flow realises, to set beside report()["cost"]."""
+        x, y, mass = self._node_particles(stride, direction)
+        return self.map_report(x, y, mass=mass, nsub=nsub, direction=direction, rho_floor=rho_floor, per_particle=per_particle)
 
     def close(self):
         if getattr(self, "_ctx", None):

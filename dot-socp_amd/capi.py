@@ -75,6 +75,18 @@ class MapReport(ctypes.Structure):
                 ("detour_hist", i64 * REPORT_BINS), ("detour_over", i64)]
 
 
+class RenderOpts(ctypes.Structure):
+    """dotsocp_render_opts"""
+    _fields_ = [("mode", ctypes.c_int), ("channels", ctypes.c_int), ("nf", i64), ("nlevels", ctypes.c_int),
+                ("barrier_index", ctypes.c_int), ("vmax", dbl), ("skip_y", i64), ("skip_x", i64), ("mask_frac", dbl)]
+
+
+class RenderInfo(ctypes.Structure):
+    """dotsocp_render_info"""
+    _fields_ = [("vmax", dbl), ("rho_min", dbl), ("nonfinite", i64), ("masked", i64), ("my", i64), ("mx", i64)]
+
+
+RENDER_LINEAR, RENDER_INVERTED, RENDER_LEVELS = 0, 1, 2        # DOTSOCP_RENDER_*
 METHOD_INPALM, METHOD_PALM, METHOD_ACCADMM = 0, 1, 2
 
 
@@ -125,6 +137,8 @@ SYMBOLS = {
                                          ctypes.POINTER(dbl), vp]),
     "dotsocp_map_report": (ctypes.c_int, [vp, vp, vp, ctypes.POINTER(AdvectOpts), vp, vp, vp, ctypes.POINTER(MapReport),
                                           vp, vp, vp]),
+    "dotsocp_render_evolution": (ctypes.c_int, [vp, vp, vp, ctypes.POINTER(RenderOpts), vp, vp, vp, vp, vp, vp, vp,
+                                                ctypes.POINTER(RenderInfo)]),
     "dotsocp_jump_next_level": (ctypes.c_int, [vp, vp]),
     "dotsocp_finish": (ctypes.c_int, [vp, ctypes.POINTER(Result)]),
     "dotsocp_get_history": (ctypes.c_int, [vp, vp, vp, vp, vp]),

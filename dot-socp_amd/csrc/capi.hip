@@ -391,6 +391,26 @@ int dotsocp_map_report(dotsocp_ctx *ctx, const double *rho0, const double *rho1,
     return ctx->s.map_report(rho0, rho1, o, x, y, mass, rep, disp, len, action);
 }
 
+int dotsocp_render_evolution(dotsocp_ctx *ctx, const double *rho0, const double *rho1, const dotsocp_render_opts *opts,
+                             const dotsocp_i64 *frame_nodes, const double *levels, const unsigned char *lut,
+                             const unsigned char *barrier, unsigned char *image, double *mvx, double *mvy,
+                             dotsocp_render_info *info) {
+    CTX_OR_FAIL();
+    if (ctx->s.prob.dim != 1 || !opts)
+        return ctx->s.render_evolution(rho0, rho1, opts, frame_nodes, levels, lut, barrier, image, mvx, mvy, info);
+    // 1-D problems live in the y slot of the engine: the stride along the axis and the one component go there
+    dotsocp_render_opts o = *opts;
+    if (o.skip_y >= 1 && o.skip_x >= 1) { o.skip_y = o.skip_x; o.skip_x = 1; }
+    dotsocp_render_info got{};
+    const int rc = ctx->s.render_evolution(rho0, rho1, &o, frame_nodes, levels, lut, barrier, image, nullptr, mvx, &got);
+    if (rc == 0 && info) {
+        *info = got;
+        info->mx = got.my;
+        info->my = got.my > 0 ? 1 : 0;
+    }
+    return rc;
+}
+
 int dotsocp_jump_next_level(dotsocp_ctx *coarse, dotsocp_ctx *fine) {
     if (!coarse || !fine) { set_error("context is NULL"); return DOTSOCP_EINVAL; }
     return fine->s.jump_from(coarse->s);

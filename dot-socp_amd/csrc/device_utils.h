@@ -47,6 +47,14 @@ __device__ __forceinline__ int report_bin(const double *e, double v) {
     return lo;
 }
 
+// doubles <-> unsigned integers of the same order (negative values: all bits flipped, others: the sign bit set).  Keys of
+// finite values lie strictly between those of -Inf (> 0) and +Inf (< 2^64 - 2^52), so neither a key nor its complement
+// is 0: a zeroed slot means "no value yet" under atomicMax (report.hip, render.hip; host side: report_key_decode).
+__device__ __forceinline__ unsigned long long report_key(double v) {
+    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
+    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+
 // Workgroup barrier that leaves the vector-memory counter alone: LDS hand-off only.  The pipelined kernels keep LDS-DMA
 // loads and global stores in flight across barriers (counted s_waitcnt vmcnt(N) of their own), which a fence would drain.
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }

@@ -217,6 +217,29 @@ int launch_report(const Grid &g, const double *q, const double *alpha, const dou
                   const double *rho1, const double *a_prev, double sig, double cD, double dD, bool dim1, const double *edges,
                   double *partials, double *sums, unsigned long long *counts, hipStream_t st);
 
+// ---------------- render.hip: pictures of the density evolution (dotsocp_render_evolution) ----------------
+// Slots of the 64-bit counters of the range pass (zeroed before the launch): max / min of the finite unmasked rho as the
+// keys of the report (max: report_key_decode(k, false, .), min: (k, true, .); 0: no value), then two plain counts
+enum { RR_MAX = 0, RR_MIN, RR_NONFINITE, RR_MASKED, RR_COUNT };
+#define RND_LEVELS 255              // slots of k_render's level table in LDS: nlevels <= 254, the rest +Inf
+// one slab: counts[RR_COUNT] += this slab's share.  rho0 / rho1 / a_prev as for launch_outputs; barrier: ny x nx bytes on
+// the device, y fastest, non-zero = masked, or nullptr
+int launch_rho_range(const Grid &g, const double *alpha, const double *weight, const double *rho0, const double *rho1,
+                     const double *a_prev, double sig, double cD, const unsigned char *barrier, unsigned long long *counts,
+                     hipStream_t st);
+// node layer `tl` of the slab -> image [ny][nx][channels] (device, x fastest): the index of include/dotsocp.h for `mode`
+// (DOTSOCP_RENDER_*), through the 256 x 3 table `lut` when channels = 3; levels: nlevels ascending doubles on the device
+// (LEVELS mode)
+int launch_render(const Grid &g, const double *alpha, const double *weight, const double *rho0, const double *rho1,
+                  const double *a_prev, double sig, double cD, i64 tl, int mode, int channels, const unsigned char *barrier,
+                  const double *levels, int nlevels, const unsigned char *lut, int barrier_index, double vmax,
+                  unsigned char *image, hipStream_t st);
+// node layer `tl` -> mvX, mvY [mx][my] (device, y fastest; mvX nullptr: 1-D): Ex, Ey at the nodes (jy * skip_y, jx * skip_x),
+// +0.0 where rho < thr
+int launch_movement(const Grid &g, const double *alpha, const double *weight, const double *rho0, const double *rho1,
+                    const double *a_prev, double sig, double cD, i64 tl, i64 skip_y, i64 skip_x, i64 my, i64 mx, double thr,
+                    double *mvX, double *mvY, hipStream_t st);
+
 // ---------------- qstep_march.hip: the q-step as one march through the time layers (march step: qstep_tile.h) ----------------
 // q-step + alpha update (alpha_in -> alpha_out, distinct buffers) + rhs of the next iteration's phi-step
 // ex (optional): a scaling of alpha_in that is still pending in memory (applied on load), and -- partials != nullptr, one

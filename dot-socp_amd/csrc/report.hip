@@ -30,14 +30,7 @@ void report_edges_host(double edges[REP_EDGES]) {
     for (int j = 0; j < REP_EDGES; ++j) edges[j] = pow(10.0, j == DOTSOCP_REPORT_BINS ? stop : j * step + start);
 }
 
-// doubles <-> unsigned integers of the same order (negative values: all bits flipped, others: the sign bit set).  Keys of
-// finite values lie strictly between those of -Inf (> 0) and +Inf (< 2^64 - 2^52), so neither a key nor its complement
-// is 0: a zeroed slot means "no value yet" under atomicMax.
-__device__ __forceinline__ unsigned long long report_key(double v) {
-    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-
+// the inverse of report_key (device_utils.h); `none`: what a zeroed slot stands for
 double report_key_decode(unsigned long long key, bool inverted, double none) {
     if (key == 0) return none;
     if (inverted) key = ~key;

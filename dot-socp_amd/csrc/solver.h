@@ -284,6 +284,11 @@ struct Solver {
     // mass / negativity / f(q) histograms / cost of the finished solve in one pass over alpha and q (report.hip);
     // layer_mass, layer_neg: nt doubles each or NULL
     int solution_report(const double *rho0, const double *rho1, dotsocp_report *rep, double *layer_mass, double *layer_neg);
+    // frames (and arrows) of the density evolution (render.hip).  Engine coordinates: mvX is the component along the second
+    // array index, mvY along the first; a 1-D problem lives in Y (capi.hip hands its mvx over as mvY, its skip_x as skip_y)
+    int render_evolution(const double *rho0, const double *rho1, const dotsocp_render_opts *o, const i64 *frame_nodes,
+                         const double *levels, const unsigned char *lut, const unsigned char *barrier, unsigned char *image,
+                         double *mvX, double *mvY, dotsocp_render_info *info);
 
     // ================ velocity and particles along it: solver_particles.hip ================
     // v = E / rho at the nodes and particles along it (advect.hip).  Coordinates of the engine: X along the second array

@@ -1,6 +1,7 @@
 // Driver steps on the device around the loop and the fields between host and device, on in-process time slabs too:
 //   * the outputs recover_RhoE / recover_q (kernels: transfer.hip) and the solution report
-//     (report.hip), with the staging of the density's ends that they share with the velocity (solver_particles.hip);
+//     (report.hip) and the pictures of the evolution (render.hip), with the staging of the density's ends that they share
+//     with the velocity (solver_particles.hip);
 //   * the multilevel transfer jump_nextLevel (+ recoverOrgVar of the coarse level, InitialScaling of the fine one; row 2);
 //   * upload, upload_layers, download, the zero test of c at begin().
 #include <algorithm>
@@ -145,6 +146,117 @@ int Solver::solution_report(const double *rho0, const double *rho1, dotsocp_repo
     }
     rep->rho_min = report_key_decode(kmin, true, INFINITY);
     rep->fq_max = report_key_decode(kmax, false, -INFINITY);
+    return 0;
+}
+
+// The looking half of the reference's demos (show_evolution_2d, show_movement_2d, export_evolution_2d) from the
+// device-resident alpha, staged like solution_report.  Two rounds: launch_rho_range per slab, combined here (the scale must
+// be known, and judged, before a byte is written); then one launch_render (and launch_movement) per requested frame on the
+// slab that owns its node, into that slab's scratch, and from there to the frame's place in the caller's arrays.
+int Solver::render_evolution(const double *rho0, const double *rho1, const dotsocp_render_opts *o, const i64 *frame_nodes,
+                             const double *levels, const unsigned char *lut, const unsigned char *barrier, unsigned char *image,
+                             double *mvX, double *mvY, dotsocp_render_info *info) {
+    DS_ARG(rho0 != nullptr && rho1 != nullptr && o != nullptr && frame_nodes != nullptr && image != nullptr,
+           "render_evolution() needs rho0, rho1, opts, frame_nodes and image (one of them is NULL)");
+    DS_ARG(!remote(), "render_evolution() serves the slabs of one process; contexts with an RCCL communicator are not rendered");
+    DS_ARG(o->nf >= 1, "render_evolution() needs nf >= 1 frame nodes");
+    for (i64 f = 0; f < o->nf; ++f)
+        DS_ARG(frame_nodes[f] >= 0 && frame_nodes[f] < nt, "render_evolution(): a frame node lies outside [0, nt)");
+    DS_ARG(o->mode == DOTSOCP_RENDER_LINEAR || o->mode == DOTSOCP_RENDER_INVERTED || o->mode == DOTSOCP_RENDER_LEVELS,
+           "render_evolution(): unknown mode");
+    const bool lev = o->mode == DOTSOCP_RENDER_LEVELS;
+    if (lev) {
+        DS_ARG(o->nlevels >= 1 && o->nlevels <= 254, "render_evolution() takes 1 to 254 levels");
+        DS_ARG(levels != nullptr, "render_evolution() needs the levels in LEVELS mode");
+        for (int j = 0; j < o->nlevels; ++j)
+            DS_ARG(levels[j] == levels[j] && (j == 0 || levels[j] > levels[j - 1]), "render_evolution(): the levels must be strictly ascending");
+    }
+    DS_ARG(o->channels == 1 || o->channels == 3, "render_evolution() writes 1 or 3 channels");
+    DS_ARG(o->channels == 1 || lut != nullptr, "render_evolution() needs a 256 x 3 table for 3 channels");
+    DS_ARG(o->barrier_index >= 0 && o->barrier_index <= 255, "render_evolution(): barrier_index outside 0 .. 255");
+    DS_ARG(o->skip_y >= 0 && o->skip_x >= 0, "render_evolution(): a skip is negative");
+    DS_ARG((o->skip_y == 0) == (o->skip_x == 0), "render_evolution(): arrows need both skips >= 1 (exactly one is zero)");
+    const bool arrows = o->skip_y >= 1;
+    const bool dim1 = prob.dim == 1;
+    DS_ARG(!arrows || (mvY != nullptr && (dim1 || mvX != nullptr)), "render_evolution(): arrows are asked for without their arrays");
+    if (!finished) { set_error("render_evolution() needs finish()"); return DOTSOCP_ESTATE; }
+    DS_CHECK(need_beta_form("render_evolution"));
+    DS_CHECK(need_q("render_evolution"));
+    cur_dev = -1;
+    DS_CHECK(use_dev(device));
+    const i64 plane = slabs[0].g.plane, hplane = ny * nx;
+    const double cD = cScale * D;                          // recoverOrgVar (solver_dotsocp2d.m:368-386)
+    const int ch = o->channels;
+    const i64 my = arrows ? (ny + o->skip_y - 1) / o->skip_y : 0, mx = arrows ? (nx + o->skip_x - 1) / o->skip_x : 0;
+    const size_t img_bytes = (size_t)hplane * ch, mv_bytes = sizeof(double) * (size_t)(my * mx);
+    auto owner = [&](i64 node) -> size_t {
+        for (size_t k = 0; k < slabs.size(); ++k)
+            if (node >= slabs[k].g.t0 && node < slabs[k].g.t0 + slabs[k].g.ntl) return k;
+        return 0;
+    };
+    // host side of the copies: lives until the scratch below has waited for every stream
+    std::vector<unsigned long long> counts((size_t)RR_COUNT * slabs.size());
+    DeviceScratch scratch(*this);
+    // per slab, one buffer: [counters | levels | barrier | lut | pictures of its frames | arrows of its frames], in doubles
+    auto dbl = [](size_t bytes) { return (i64)((bytes + 7) / 8); };
+    const i64 off_lev = RR_COUNT, off_bar = off_lev + RND_LEVELS, off_lut = off_bar + dbl((size_t)hplane);
+    const i64 off_img = off_lut + dbl(768);
+    std::vector<i64> mine(slabs.size(), 0);      // frames of the request per owning slab
+    for (i64 f = 0; f < o->nf; ++f) ++mine[owner(frame_nodes[f])];
+    DS_CHECK(stage_left_tail());
+    size_t k = 0;
+    FOR_SLABS(s) {
+        double *buf = nullptr;
+        const i64 nimg = mine[k] * dbl(img_bytes);
+        DS_CHECK(scratch.alloc(&buf, off_img + nimg + mine[k] * (dim1 ? 1 : 2) * my * mx));
+        DS_CHECK(stage_rho_ends(s, rho0, rho1));
+        DS_HIP(ds_memset_async(buf, 0, sizeof(unsigned long long) * RR_COUNT, s.st));
+        if (lev) DS_HIP(ds_memcpy_async(buf + off_lev, levels, sizeof(double) * (size_t)o->nlevels, hipMemcpyHostToDevice, s.st));
+        if (barrier) DS_HIP(ds_memcpy_async(buf + off_bar, barrier, (size_t)hplane, hipMemcpyHostToDevice, s.st));
+        if (ch == 3) DS_HIP(ds_memcpy_async(buf + off_lut, lut, 768, hipMemcpyHostToDevice, s.st));
+        DS_CHECK(launch_rho_range(s.g, s.alpha, s.weight, s.w1, s.w1 + plane, s.a0_prev, sigma, cD,
+                                  barrier ? (const unsigned char *)(buf + off_bar) : nullptr, (unsigned long long *)buf, s.st));
+        DS_HIP(ds_memcpy_async(counts.data() + RR_COUNT * k++, buf, sizeof(unsigned long long) * RR_COUNT, hipMemcpyDeviceToHost, s.st));
+    }
+    DS_CHECK(sync_all());
+    dotsocp_render_info res{};
+    unsigned long long kmax = 0, kmin = 0;
+    for (size_t j = 0; j < slabs.size(); ++j) {
+        const unsigned long long *c = counts.data() + RR_COUNT * j;
+        kmax = std::max(kmax, c[RR_MAX]);
+        kmin = std::max(kmin, c[RR_MIN]);
+        res.nonfinite += (i64)c[RR_NONFINITE];
+        res.masked += (i64)c[RR_MASKED];
+    }
+    res.vmax = o->vmax > 0.0 ? o->vmax : report_key_decode(kmax, false, -INFINITY);
+    res.rho_min = report_key_decode(kmin, true, INFINITY);
+    res.my = my;
+    res.mx = mx;
+    DS_ARG(res.vmax > 0.0 && std::isfinite(res.vmax), "render_evolution(): the scale (the largest finite density, or opts.vmax) is not a positive finite number");
+    const double thr = res.vmax * o->mask_frac;
+    std::vector<i64> used(slabs.size(), 0);      // frames a slab has rendered so far: the slot of the next one
+    for (i64 f = 0; f < o->nf; ++f) {
+        const size_t j = owner(frame_nodes[f]);
+        Slab &s = slabs[j];
+        DS_CHECK(use(s));
+        double *buf = scratch.bufs[j];
+        const i64 slot = used[j]++;
+        unsigned char *img = (unsigned char *)(buf + off_img + slot * dbl(img_bytes));
+        DS_CHECK(launch_render(s.g, s.alpha, s.weight, s.w1, s.w1 + plane, s.a0_prev, sigma, cD, frame_nodes[f] - s.g.t0, o->mode, ch,
+                               barrier ? (const unsigned char *)(buf + off_bar) : nullptr, buf + off_lev, o->nlevels,
+                               (const unsigned char *)(buf + off_lut), o->barrier_index, res.vmax, img, s.st));
+        DS_HIP(ds_memcpy_async(image + img_bytes * (size_t)f, img, img_bytes, hipMemcpyDeviceToHost, s.st));
+        if (!arrows) continue;
+        double *mv = buf + off_img + mine[j] * dbl(img_bytes) + slot * (dim1 ? 1 : 2) * my * mx;      // behind the slab's pictures
+        double *dX = dim1 ? nullptr : mv, *dY = dim1 ? mv : mv + my * mx;
+        DS_CHECK(launch_movement(s.g, s.alpha, s.weight, s.w1, s.w1 + plane, s.a0_prev, sigma, cD, frame_nodes[f] - s.g.t0, o->skip_y,
+                                 o->skip_x, my, mx, thr, dX, dY, s.st));
+        if (dX) DS_HIP(ds_memcpy_async(mvX + my * mx * f, dX, mv_bytes, hipMemcpyDeviceToHost, s.st));
+        DS_HIP(ds_memcpy_async(mvY + my * mx * f, dY, mv_bytes, hipMemcpyDeviceToHost, s.st));
+    }
+    DS_CHECK(sync_all());
+    DS_CHECK(canary_after());                   // the kernels wrote inside their buffers
+    if (info) *info = res;
     return 0;
 }
 

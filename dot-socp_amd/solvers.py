@@ -222,6 +222,59 @@ class InPALMContext:
                                                       capi.fptr(mass), capi.fptr(neg)))
         return from_struct(rep, mass, neg)
 
+    def render(self, frames=None, num_frame=6, mode="imshow", nlevels=128, lut=None, barrier=None, vmax=None, arrows=False,
+               barrier_index=255, levels=None):
+        """Pictures of the density evolution on the device (dotsocp_render_evolution; render.py): uint8 frames at the nodes
+        `frames` (any order, repeats allowed; None: render.frame_nodes(nt, num_frame)) in mode "imshow", "inverted" or
+        "levels" (nlevels log-spaced levels, or `levels`), as indices or -- lut: a (256, 3) uint8 table -- as RGB; barrier:
+        a mask (ny, nx) or a barrier function of the examples; vmax > 0 fixes the scale.  arrows: False, True (the reference's
+        skips, render.movement_skips, and mask 0.01) or dict(skip_y=, skip_x=, mask_frac=).  Returns dict(image, nodes, vmax,
+        rho_min, nonfinite, masked[, Ex[, Ey]]): image (nf, ny, nx[, 3]) C-ordered (1-D: (nf, nx[, 3])), Ex / Ey
+        (my, mx, nf) Fortran-ordered (1-D: Ex (mx, nf)); the same bytes as render.render / render.movement of
+        self.outputs().  Call after finish(); only the pictures cross PCIe."""
+        from . import render as R
+        m = self.model
+        one_d = not hasattr(m, "ny")
+        nt = int(m.nt)
+        shp = (int(m.nx),) if one_d else (int(m.ny), int(m.nx))
+        if mode not in R.MODES:
+            raise ValueError("render(): mode must be one of %s" % sorted(R.MODES))
+        nodes = R.frame_nodes(nt, num_frame) if frames is None else np.array(frames, dtype=np.int64).ravel()
+        o = capi.RenderOpts()
+        o.mode, o.channels, o.nf = R.MODES[mode], 1 if lut is None else 3, int(nodes.size)
+        o.barrier_index, o.vmax = int(barrier_index), float(vmax) if vmax is not None else 0.0
+        lv = None
+        if mode == "levels":
+            lv = np.ascontiguousarray(R.log_levels(nlevels) if levels is None else levels, dtype=np.float64).ravel()
+            o.nlevels = int(lv.size)
+        table = None if lut is None else R.check_lut(lut)
+        b = R.barrier_mask(barrier, shp)
+        mask = None if b is None else np.asfortranarray(b, dtype=np.uint8)
+        Ex = Ey = None
+        if arrows:
+            a = dict(arrows) if isinstance(arrows, dict) else {}
+            sy, sx = R.movement_skips(1 if one_d else shp[0], shp[-1])
+            o.skip_y, o.skip_x = (1 if one_d else int(a.get("skip_y", sy))), int(a.get("skip_x", sx))
+            o.mask_frac = float(a.get("mask_frac", R.MASK_FRAC))
+            if o.skip_y >= 1 and o.skip_x >= 1:
+                cut = tuple(-(-n // s) for n, s in zip(shp, (o.skip_x,) if one_d else (o.skip_y, o.skip_x)))
+                Ex = np.empty(cut + (nodes.size,), order="F")
+                Ey = None if one_d else np.empty(cut + (nodes.size,), order="F")
+        image = np.empty((nodes.size,) + shp + (() if lut is None else (3,)), dtype=np.uint8)
+        info = capi.RenderInfo()
+        r0, r1 = self._rho_ends()
+        ptr = lambda a: None if a is None else a.ctypes.data         # noqa: E731
+        capi.check(capi.lib().dotsocp_render_evolution(self._ctx, capi.fptr(r0), capi.fptr(r1), ctypes.byref(o), nodes.ctypes.data,
+                                                       ptr(lv), ptr(table), ptr(mask), image.ctypes.data, ptr(Ex), ptr(Ey),
+                                                       ctypes.byref(info)))
+        out = dict(image=image, nodes=nodes, vmax=float(info.vmax), rho_min=float(info.rho_min), nonfinite=int(info.nonfinite),
+                   masked=int(info.masked))
+        if Ex is not None:
+            out["Ex"] = Ex
+        if Ey is not None:
+            out["Ey"] = Ey
+        return out
+
     def _rho_floor(self, rho_floor):
         from .advect import default_rho_floor
         return default_rho_floor(self.model.rho0, self.model.rho1) if rho_floor is None else float(rho_floor)
@@ -423,7 +476,7 @@ def _weights_mode(weight, weights, transfer, weighted=True):
 
 
 def _solve_levels(rho0, rho1, nt, levelN, opts, method, dim, weighted, device, barrier=None, transfer="device",
-                  weights=None, report=False, advect=None, push=None, map_report=None):
+                  weights=None, report=False, advect=None, push=None, map_report=None, render=None):
     """The level loop of solver_dotsocp2d.m:154-250 (dot1d / wdot2d twins): restrict the data to
     levelN grids, solve coarse to fine with warm starts; every solve runs on the device.
     transfer = "device": the state never leaves the GPU -- jump_nextLevel and the output recovery run there
@@ -460,6 +513,8 @@ def _solve_levels(rho0, rho1, nt, levelN, opts, method, dim, weighted, device, b
         raise ValueError("push= needs transfer='device' (the mass moves through the device-resident state)")
     if map_report is not None and transfer != "device":
         raise ValueError("map_report= needs transfer='device' (the particles move through the device-resident state)")
+    if render is not None and transfer != "device":
+        raise ValueError("render= needs transfer='device' (the pictures are made from the device-resident state)")
     wopt = _get(opts, "weight") if weighted else None
     weights = _weights_mode(wopt, weights, transfer, weighted)
     wdev = weights == "device"
@@ -546,6 +601,10 @@ def _solve_levels(rho0, rho1, nt, levelN, opts, method, dim, weighted, device, b
                     output["push"] = ctx.push_from_nodes(**push)
                 if map_report is not None:
                     output["map_report"] = ctx.map_report_from_nodes(**map_report)
+                if render is not None:
+                    asked = [render] if isinstance(render, dict) else list(render)
+                    made = [ctx.render(**(dict(r) if barrier is None else dict(dict(barrier=barrier), **r))) for r in asked]
+                    output["render"] = made[0] if isinstance(render, dict) else made
             if not on_device:
                 ctx.close()
                 recoverOrgVar(var)
@@ -581,36 +640,41 @@ def _solve_levels(rho0, rho1, nt, levelN, opts, method, dim, weighted, device, b
 
 
 def solver_dotsocp2d(rho0, rho1, nt, levelN, opts, method="inPALM", device=0, transfer="device", report=False,
-                     advect=None, push=None, map_report=None):
+                     advect=None, push=None, map_report=None, render=None):
     """[output, timeML, runHistML, runHist] = solver_dotsocp2d(rho0, rho1, nt, levelN, opts, method)
     socp/dot2d/solver_dotsocp2d.m:1.  report=True: output["report"] = the device-side solution report; advect=dict(x=..., y=...,
     ...): output["advect"] = the particles carried along the solved flow; push=dict(stride=..., frames=..., ...):
     output["push"] = the given density carried along it and deposited at the frame nodes; map_report=dict(stride=..., ...):
-    output["map_report"] = cost, straightness and steadiness of the map the flow realises (all four: _solve_levels)."""
+    output["map_report"] = cost, straightness and steadiness of the map the flow realises; render=dict(num_frame=..., mode=...,
+    arrows=..., ...): output["render"] = uint8 pictures of the density evolution and the arrows of the flux (all five:
+    _solve_levels)."""
     output, timeML, runHistML, runHist = _solve_levels(rho0, rho1, nt, levelN, opts, method, 2, False, device,
-                                                       transfer=transfer, report=report, advect=advect, push=push, map_report=map_report)
+                                                       transfer=transfer, report=report, advect=advect, push=push, map_report=map_report,
+                                                       render=render)
     if not check_massConservation(output["rho"], 1e-2):
         print("Warning: The mass conservation constraint violation exceeds 0.01")
     return output, timeML, runHistML, runHist
 
 
 def solver_dotsocp1d(rho0, rho1, nt, levelN, opts, method="inPALM", device=0, transfer="device", report=False,
-                     advect=None, push=None, map_report=None):
-    """socp/dot1d/solver_dotsocp1d.m:1.  report, advect, push, map_report: as for solver_dotsocp2d."""
+                     advect=None, push=None, map_report=None, render=None):
+    """socp/dot1d/solver_dotsocp1d.m:1.  report, advect, push, map_report, render: as for solver_dotsocp2d."""
     output, timeML, runHistML, runHist = _solve_levels(rho0, rho1, nt, levelN, opts, method, 1, False, device,
-                                                       transfer=transfer, report=report, advect=advect, push=push, map_report=map_report)
+                                                       transfer=transfer, report=report, advect=advect, push=push, map_report=map_report,
+                                                       render=render)
     if not check_massConservation(output["rho"], 1e-2):
         print("Warning: The mass conservation constraint violation exceeds 0.01")
     return output, timeML, runHistML, runHist
 
 
 def solver_wdotsocp2d(rho0, rho1, nt, levelN, opts, method="inPALM", barrier=None, device=0, transfer="device",
-                      weights=None, report=False, advect=None, push=None, map_report=None):
+                      weights=None, report=False, advect=None, push=None, map_report=None, render=None):
     """socp/wdot2d/solver_wdotsocp2d.m:1.  opts["weight"]: the Nq array, or a SpaceWeight (examples.py); weights:
-    where the levels' weights are made, "host" or "device" (_solve_levels); report, advect, push, map_report: as for solver_dotsocp2d."""
+    where the levels' weights are made, "host" or "device" (_solve_levels); report, advect, push, map_report, render: as for
+    solver_dotsocp2d (render: `barrier` is the default mask of the pictures)."""
     output, timeML, runHistML, runHist = _solve_levels(rho0, rho1, nt, levelN, opts, method, 2, True, device,
                                                        barrier=barrier, transfer=transfer, weights=weights, report=report,
-                                                       advect=advect, push=push, map_report=map_report)
+                                                       advect=advect, push=push, map_report=map_report, render=render)
     if not check_massConservation(output["rho"], 1e-2):
         print("Warning: The tolerance of mass conservation constraint is under 0.01")
     return output, timeML, runHistML, runHist

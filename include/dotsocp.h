@@ -469,6 +469,69 @@ int dotsocp_map_report(dotsocp_ctx *ctx, const double *rho0, const double *rho1,
                        double *x, double *y, const double *mass, dotsocp_map_report_t *rep, double *disp, double *len,
                        double *action);
 
+/* Pictures of the density evolution on the device: what utils/show_evolution_2d.m, show_movement_2d.m and
+ * export_evolution_2d.m draw from the downloaded outputs -- gray or colour-mapped frames, filled log-spaced levels, the
+ * arrows of the flux -- formed from the device-resident alpha.  A frame reads the two alpha layers around its node; what
+ * crosses PCIe is one byte (three with a colour table) per pixel.  rho, Ex, Ey at a node are the values
+ * dotsocp_recover_outputs writes, bit for bit.
+ *
+ * Range.  vmax = the maximum of rho over all nodes of all nt layers (rho0 and rho1 included) that are finite and not set
+ *   in `barrier`; rho_min = the minimum over the same set (a -0.0 counts as +0.0; +Inf if the set is empty); nonfinite =
+ *   the unmasked nodes whose rho is NaN or +-Inf; masked = the masked nodes (all layers).  The reference sets barrier nodes
+ *   to Inf BEFORE it takes the maximum (show_evolution_2d.m:36,52), which makes its own scale infinite; that is not
+ *   followed here.  opts.vmax > 0 fixes the scale (to compare runs): then only rho_min and the counts come from the pass.
+ *   A scale that is not a positive finite number is DOTSOCP_EINVAL; nothing is written.
+ * Index of a node, by opts.mode (no contraction of a * b + c; render.py restates it with the same bits):
+ *   DOTSOCP_RENDER_LINEAR    imshow(rho, [0, vmax]) (show_evolution_2d.m:56):  i = 0 for rho <= 0 or NaN, else
+ *                            i = min(255, floor((rho / vmax) * 256.0)): one IEEE division, one product; +Inf gives 255.
+ *   DOTSOCP_RENDER_INVERTED  vmax - rho (export_evolution_2d.m:91-92):  255 - i of the linear mode.
+ *   DOTSOCP_RENDER_LEVELS    contourf / contour of rho * (255 / vmax) over exp(linspace(0, log(255), n))
+ *                            (show_evolution_2d.m:58-65), filled, no lines:  s = rho * k with k = 255.0 / vmax formed once
+ *                            on the host;  i = the number of levels[j] <= s, in 0 .. nlevels; NaN gives 0.  `levels`:
+ *                            nlevels strictly ascending doubles, 1 <= nlevels <= 254, made by the caller (render.log_levels);
+ *                            the device evaluates no exp and compares against these doubles.
+ *   In every mode a node set in `barrier` gets opts.barrier_index (0 .. 255) instead.
+ * Picture.  nf frame nodes in [0, nt), in any order, repeats allowed.  image: uint8 [nf][ny][nx][channels], x fastest --
+ *   the row-major picture every image writer takes, an image row being a fixed y, as imshow(rho(:,:,t)) shows it.
+ *   channels = 1: the index itself;  channels = 3: lut[3 * i + 0 .. 2] of the caller's 256 x 3 table (any table: gray, a
+ *   ramp, a colour map of the caller's).  1-D problems: image [nf][nx][channels]; with all nodes requested this is the
+ *   space-time diagram.
+ * Arrows (show_movement_2d.m:31-33,45-46,56), asked for with skip_y >= 1 and skip_x >= 1 (both 0: none).  mvx, mvy:
+ *   doubles [nf][mx][my], y fastest, my = ceil(ny / skip_y), mx = ceil(nx / skip_x): Ex, Ey at the nodes y = 0, skip_y, ..,
+ *   x = 0, skip_x, .. of every frame node -- the bits of dotsocp_recover_outputs, except +0.0 where
+ *   rho < vmax * mask_frac (strict; the product is formed once on the host; the reference's mask_frac is 0.01; a NaN rho
+ *   keeps its arrow).  The reference derives both skips from nx (:21,27); here there is one per axis.  1-D problems: mvx
+ *   alone, [nf][mx], with skip_x along the axis (skip_y >= 1 is only the request), my = 1.
+ * barrier: ny x nx bytes, y fastest (1-D: nx), non-zero = masked; or NULL.
+ *
+ * After finish() (DOTSOCP_ESTATE before); inPALM / ALG2, PALM, acc-ADMM, weighted and 1-D contexts; one slab, `nslabs`
+ * slabs and dotsocp_create_multi: a frame is rendered by the slab that owns its node and lands at its position in the
+ * request.  DOTSOCP_EINVAL, before anything is written: a NULL rho0 / rho1 / opts / frame_nodes / image (info may be NULL), nf < 1, a
+ * frame node outside [0, nt), a mode other than the three, nlevels outside 1 .. 254 or a NULL `levels` in LEVELS mode,
+ * levels not strictly ascending (a NaN among them), channels other than 1 or 3, channels = 3 without lut, barrier_index
+ * outside 0 .. 255, a negative skip, exactly one skip zero, arrows without mvx (2-D: or mvy), a context with an RCCL
+ * communicator attached. */
+enum { DOTSOCP_RENDER_LINEAR = 0, DOTSOCP_RENDER_INVERTED = 1, DOTSOCP_RENDER_LEVELS = 2 };
+typedef struct {
+    int mode;                       /* DOTSOCP_RENDER_* */
+    int channels;                   /* 1 or 3 */
+    dotsocp_i64 nf;                 /* frame nodes */
+    int nlevels;                    /* LEVELS mode: 1 .. 254 */
+    int barrier_index;              /* index of the nodes set in `barrier`, 0 .. 255 */
+    double vmax;                    /* > 0: the scale; else the maximum found */
+    dotsocp_i64 skip_y, skip_x;     /* arrows: both >= 1; none: both 0 */
+    double mask_frac;               /* arrows vanish where rho < vmax * mask_frac */
+} dotsocp_render_opts;
+typedef struct {
+    double vmax, rho_min;           /* the scale used; min over the finite unmasked rho */
+    dotsocp_i64 nonfinite, masked;
+    dotsocp_i64 my, mx;             /* arrow nodes per frame along y, x (0 without arrows) */
+} dotsocp_render_info;
+int dotsocp_render_evolution(dotsocp_ctx *ctx, const double *rho0, const double *rho1, const dotsocp_render_opts *opts,
+                             const dotsocp_i64 *frame_nodes, const double *levels, const unsigned char *lut,
+                             const unsigned char *barrier, unsigned char *image, double *mvx, double *mvy,
+                             dotsocp_render_info *info);
+
 /* Multilevel transfer on the device: socp/dot2d/utils/jump_nextLevel.m:5-16 with
  * interpolate.m:20-84, between the finished context `coarse` and the context `fine` of the next level (created
  * from the fine level's InitialScaling scalars, c and weight uploaded, begin() not yet called; grid

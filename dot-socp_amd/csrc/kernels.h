@@ -153,6 +153,10 @@ int launch_prolong_phi(const Grid &gf, const Grid &gc, const double *phic, doubl
 int launch_prolong_beta(const Grid &gf, const Grid &gc, const double *betac, double *betaf, double *neg, double sc_in0,
                         double sc_in1, double sc_out, hipStream_t st, i64 tc0 = 0, i64 Nzc = -1);
 int launch_scale_div(double *x, const double *w, i64 n, double sc, hipStream_t st);
+// time slabs: q = F*B*w on the slab's first edge layer in one slab's summation order; p3 .. p8: the left neighbour's last
+// cell layer of the cone columns 3, 4, 7, 8
+int launch_conj_first_layer(const Grid &g, double *q, const double *w, double s, const double *p3, const double *p4,
+                            const double *p7, const double *p8, hipStream_t st);
 int launch_fill(double *x, i64 n, double v, hipStream_t st);
 // slab-aware: `out` holds the slab's own layers (ntl node layers resp. ncl cell layers); a_prev: launch_out_tail of the
 // left neighbour (nullptr on the first slab)

@@ -72,6 +72,7 @@ int Solver::recover_outputs(const double *rho0, const double *rho1, double *rho,
         }
         DS_CHECK(sync_all());                               // w0 is reused by the next output
     }
+    DS_CHECK(canary_after());                   // the kernels wrote inside their buffers
     return 0;
 }
 
@@ -346,10 +347,22 @@ int Solver::jump_from(Solver &coarse) {
         DS_CHECK(shift(+1, [](Slab &s) { return s.send_bx; }, [](Slab &s) { return s.btail_bx; }, slabs[0].g.bxLayer));
         DS_CHECK(shift(+1, [](Slab &s) { return s.send_by; }, [](Slab &s) { return s.btail_by; }, slabs[0].g.byLayer));
     }
-    FOR_SLABS(f) {
-        DS_CHECK(launch_bfd_conj(f.g, f.alpha, f.z, 1.0, f.st, f.btail_bx, f.btail_by));
-        DS_CHECK(scale_owned(f, f.alpha, 1.0 / cScale / D, true));
+    FOR_SLABS(f) DS_CHECK(launch_bfd_conj(f.g, f.alpha, f.z, 1.0, f.st, f.btail_bx, f.btail_by));
+    if (multi()) {
+        // ... which adds the neighbour's pair as one term.  The transfer gives the bits of one slab on any split: the first
+        // edge layer once more, from the neighbour's last cell layer of the columns 3, 4 -> w0 and 7, 8 -> w1 (both free
+        // again, two layers at least), in mexBFdConj's order
+        const i64 plane = slabs[0].g.plane;
+        static const int cols[4] = {3, 4, 7, 8};
+        for (int k = 0; k < 4; ++k)
+            DS_CHECK(shift(+1, [k](Slab &s) { return s.z + (i64)cols[k] * s.g.Nc + s.g.plane * (s.g.ncl - 1); },
+                           [k](Slab &s) { return (k < 2 ? s.w0 : s.w1) + s.g.plane * (k & 1); }, plane));
+        FOR_SLABS(f)
+            if (!f.g.first)
+                DS_CHECK(launch_conj_first_layer(f.g, f.alpha, f.z, 1.0, f.w0, f.w0 + plane, f.w1, f.w1 + plane, f.st));
+        DS_CHECK(sync_all());                   // the copies read the neighbours' z, which is zeroed below
     }
+    FOR_SLABS(f) DS_CHECK(scale_owned(f, f.alpha, 1.0 / cScale / D, true));
     // q = (D_f/dScale_f) * grad(phiR) ./ w : the D_f / h factors are those of the loop's own stencil; the forward time
     // difference of a slab's last cell layer reads the first phi layer of its right neighbour
     if (multi())
@@ -360,6 +373,7 @@ int Solver::jump_from(Solver &coarse) {
         DS_HIP(ds_memset_async(f.z, 0, sizeof(double) * 10 * f.g.Nc, f.st));       // var.z of initialize.m
     }
     DS_CHECK(sync_all());
+    DS_CHECK(canary_after());                   // the gathers into w0 / beta2 and the kernels wrote inside their buffers
     return 0;
 }
 

@@ -100,6 +100,45 @@ int launch_prolong_beta(const Grid &gf, const Grid &gc, const double *betac, dou
     return 0;
 }
 
+// Time slabs: F*B*w on a slab's FIRST edge layer, summed as one slab sums it -- ((w1 + w2) + w3) + w4, mexBFdConj's order,
+// with w3, w4 (w7, w8) read from the left neighbour's last cell layer (p3 .. p8: that layer of the four columns, rows py
+// apart).  k_bfd_conj adds the neighbour's pair as ONE term, (w1 + w2) + (w3 + w4): the last bit of a quarter of the layer.
+__global__ void __launch_bounds__(TILE_Y *TILE_X) k_conj_first_layer(Grid g, double *__restrict__ q, const double *__restrict__ w,
+                                                                      double sf, const double *__restrict__ p3,
+                                                                      const double *__restrict__ p4, const double *__restrict__ p7,
+                                                                      const double *__restrict__ p8) {
+    const i64 y = (i64)blockIdx.x * TILE_Y + threadIdx.x;
+    const i64 x = (i64)blockIdx.y * TILE_X + threadIdx.y;
+    if (y < g.ny && x < g.nx - 1) {
+        double acc = 0.0;
+        if (g.ncl > 0) {
+            acc += w[1 * g.Nc + y + g.py * (x + 1)];
+            acc += w[2 * g.Nc + y + g.py * x];
+        }
+        acc += p3[y + g.py * (x + 1)];
+        acc += p4[y + g.py * x];
+        q[g.offBx + y + g.py * x] = sf * acc;
+    }
+    if (y < g.ny - 1 && x < g.nx) {
+        double acc = 0.0;
+        if (g.ncl > 0) {
+            acc += w[5 * g.Nc + (y + 1) + g.py * x];
+            acc += w[6 * g.Nc + y + g.py * x];
+        }
+        acc += p7[(y + 1) + g.py * x];
+        acc += p8[y + g.py * x];
+        q[g.offBy + y + g.pyb * x] = sf * acc;
+    }
+}
+
+int launch_conj_first_layer(const Grid &g, double *q, const double *w, double s, const double *p3, const double *p4,
+                            const double *p7, const double *p8, hipStream_t st) {
+    dim3 grid((unsigned)((g.ny + TILE_Y - 1) / TILE_Y), (unsigned)((g.nx + TILE_X - 1) / TILE_X), 1);
+    DS_KLAUNCH(k_conj_first_layer, grid, dim3(TILE_Y, TILE_X), 0, st, g, q, w, edge_factor(s), p3, p4, p7, p8);
+    DS_HIP(hipGetLastError());
+    return 0;
+}
+
 __global__ void __launch_bounds__(256) k_fill(double *__restrict__ x, i64 n, double v) {
     for (i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (i64)gridDim.x * blockDim.x) x[i] = v;
 }

@@ -85,6 +85,10 @@ CASES = {
     # has amplitudes of its own; the thresholds of tests/test_generic_state_conditions.py are the same for all.
     # 13 layers: a wider class offset and a larger alpha keep polar rows alive through iterations 3..7
     "inPALM-40x12x13": dict(method="inPALM", shape=(40, 12, 13), K=12, shift=20.0, amplitudes=dict(alpha=2.5)),        # the time-slab grid
+    # ny * nx = 4096 and ny % 16 == 0: unpitched rows and cone columns Nz + 48 apart on the device; the coarse level of the
+    # padded transfer case (oracle/transfer_state.py)
+    # (the inside rows nearly die out in iteration 2 on so few layers: the wide offset, and a small beta next to it)
+    "inPALM-128x32x5": dict(method="inPALM", shape=(128, 32, 5), K=7, shift=20.0, amplitudes=dict(alpha=2.5, beta=0.1)),
     # 1e6 weights: with q of the plain size KKT column 5 moves by 3e-12 relative under one-ulp perturbations (w q
     # cancels against A phi in the alpha update); a smaller q brings that to 1e-13.  Past iteration 12 column 4 falls
     # to 1e-3.

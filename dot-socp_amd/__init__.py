@@ -12,6 +12,9 @@ from .examples import (SpaceWeight, ensure_barrier_validity, gene_barrier_of_cir
                        gene_barrier_of_love_heart, gene_space_weight_circle, gene_space_weight_circleInv,
                        gene_weight_circle, gene_weight_circleInv, get_example_1d, get_example_2d,
                        get_space_weight_by_barrier, get_weight_by_barrier)
+from . import images  # noqa: F401
+from .images import (gene_barrier_of_example6, gene_barrier_of_maze14, gene_example5,  # noqa: F401
+                     gene_example_DOTmark_4stitch, get_example_from_images, image_density, imread, imresize, rgb2gray)
 from .mexops import (mexBFd, mexBFd1d, mexBFdConj, mexBFdConj1d, mexProjSoc, mirt_dctn, mirt_idctn,  # noqa: F401
                      oper_poisson, oper_poisson3dim)
 from .model import (InitialScaling, ModelHandle, VarHandle, check_massConservation, initialize,  # noqa: F401

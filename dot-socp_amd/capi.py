@@ -86,6 +86,11 @@ class RenderInfo(ctypes.Structure):
     _fields_ = [("vmax", dbl), ("rho_min", dbl), ("nonfinite", i64), ("masked", i64), ("my", i64), ("mx", i64)]
 
 
+class ImageOpts(ctypes.Structure):
+    """dotsocp_image_opts"""
+    _fields_ = [("ny", i64), ("nx", i64), ("layout", ctypes.c_int), ("reverse", ctypes.c_int), ("lower_bound", dbl)]
+
+
 RENDER_LINEAR, RENDER_INVERTED, RENDER_LEVELS = 0, 1, 2        # DOTSOCP_RENDER_*
 METHOD_INPALM, METHOD_PALM, METHOD_ACCADMM = 0, 1, 2
 
@@ -156,6 +161,10 @@ SYMBOLS = {
     "dotsocp_weights_log10_mean": (ctypes.c_int, [vp, ctypes.c_int, ctypes.POINTER(dbl)]),
     "dotsocp_weights_download": (ctypes.c_int, [vp, ctypes.c_int, vp]),
     "dotsocp_upload_weight_from": (ctypes.c_int, [vp, vp, ctypes.c_int]),
+    "dotsocp_imresize_taps": (ctypes.c_int, [i64, i64]),
+    "dotsocp_imresize_table": (ctypes.c_int, [i64, i64, vp, vp, ctypes.POINTER(ctypes.c_int)]),
+    "dotsocp_imresize": (ctypes.c_int, [vp, vp, ctypes.c_int, i64, i64, i64, i64, i64, ctypes.c_int]),
+    "dotsocp_image_density": (ctypes.c_int, [ctypes.POINTER(ImageOpts), vp, ctypes.c_int, vp, ctypes.c_int]),
 }
 
 _lib = None

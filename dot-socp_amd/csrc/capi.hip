@@ -3,6 +3,7 @@
 #include <new>
 
 #include "comm.h"
+#include "image_table.h"
 #include "solver.h"
 #include "weights.h"
 
@@ -501,6 +502,28 @@ int dotsocp_upload_weight_from(dotsocp_ctx *ctx, dotsocp_weights *w, int level) 
     const Weights::Level *L = nullptr;
     DS_CHECK(w->w.level_for_upload(level, &L));
     return ctx->s.upload_weight_from(L->w, w->w.device, L->ny, L->nx, L->nt);
+}
+
+// ------------------------------------------------------------------ pictures (image.hip, image_table.h)
+int dotsocp_imresize_taps(dotsocp_i64 n_in, dotsocp_i64 n_out) {
+    DS_ARG(imresize_lengths_ok(n_in, n_out), "imresize: lengths must lie in 1 .. 65536");
+    return imresize_max_taps(n_in, n_out);
+}
+
+int dotsocp_imresize_table(dotsocp_i64 n_in, dotsocp_i64 n_out, double *weights, int *indices, int *taps) {
+    DS_ARG(imresize_lengths_ok(n_in, n_out), "imresize: lengths must lie in 1 .. 65536");
+    DS_ARG(weights && indices && taps, "NULL pointer");
+    imresize_table(n_in, n_out, weights, indices, taps);
+    return 0;
+}
+
+int dotsocp_imresize(void *out, const void *in, int dtype, dotsocp_i64 h_in, dotsocp_i64 w_in, dotsocp_i64 planes,
+                     dotsocp_i64 h_out, dotsocp_i64 w_out, int device) {
+    return image_resize(out, in, dtype, h_in, w_in, planes, h_out, w_out, device);
+}
+
+int dotsocp_image_density(const dotsocp_image_opts *o, const dotsocp_image *imgs, int nimg, double *rho, int device) {
+    return image_density(o, imgs, nimg, rho, device);
 }
 
 int dotsocp_poisson_phi(dotsocp_ctx *ctx) { CTX_OR_FAIL(); return ctx->s.poisson_phi(); }

@@ -214,6 +214,9 @@ double report_key_decode(unsigned long long key, bool inverted, double none);
 i64 report_tiles(const Grid &g);
 // sums[r] = partials[r * tiles] + ... + partials[r * tiles + tiles - 1], r < rows, by the fixed tree of the report's layer sums
 int launch_report_rows(const double *partials, i64 tiles, i64 rows, double *sums, hipStream_t st);
+// image.hip: dotsocp_imresize / dotsocp_image_density behind their argument checks (host pointers, the null stream of `device`)
+int image_resize(void *out, const void *in, int dtype, i64 h_in, i64 w_in, i64 planes, i64 h_out, i64 w_out, int device);
+int image_density(const dotsocp_image_opts *o, const dotsocp_image *imgs, int nimg, double *rho, int device);
 // one slab: `partials` [ntl][3][tiles] <- per-workgroup layer sums of rho, min(rho, 0) and the cost terms; `sums` [ntl][3]
 // <- their totals, added in tile order; counts[RC_COUNT] += this slab's share.  rho0 / rho1 / a_prev as for launch_outputs;
 // edges: DOTSOCP_REPORT_BINS + 1 doubles on the device.

@@ -135,9 +135,15 @@ _EXAMPLES_2D = {"example1": gene_example1, "example2": gene_example2, "example3"
                 "love-heart": gene_exampleLoveHeart}
 
 
-def get_example_2d(problem, nx, ny, lowerBound=0.0):
-    """examples/dot2d/get_example.m:24-48 and examples/wdot2d/get_example.m:7-31: the closed-form generators
-    ("example5" and "DOTmark_4stitch" read image files and are not restated)."""
+def get_example_2d(problem, nx, ny, lowerBound=0.0, resources=None, DOTmark_type=None, stitch1_indices=None,
+                   stitch2_indices=None, device=None):
+    """examples/dot2d/get_example.m:24-48 and examples/wdot2d/get_example.m:7-31.  "example5" and "DOTmark_4stitch" read
+    image files (images.get_example_2d_images): they need resources=, the directory laid out as the reference's
+    examples/dot2d/resources, take the reference's DOTmark_type / stitch1_indices / stitch2_indices, and are made on the
+    device with a device ordinal (None: the numpy twin, the same bits); without resources= they raise like an unknown name."""
+    if problem in ("example5", "DOTmark_4stitch"):
+        from .images import get_example_2d_images
+        return get_example_2d_images(problem, nx, ny, lowerBound, resources, DOTmark_type, stitch1_indices, stitch2_indices, device)
     if problem not in _EXAMPLES_2D:
         raise ValueError("Novalid input: 'Problem'")
     rho0, rho1 = _EXAMPLES_2D[problem](nx, ny)
@@ -184,7 +190,7 @@ def gene_barrier_of_circle_pillar():
 
 def gene_barrier_of_love_heart():
     """examples/wdot2d/gene_barrier_of_love_heart.m:3-15: everything outside a large heart curve or inside a small
-    one.  (The maze barriers of example6 / maze14 are read from image files and are not restated.)"""
+    one.  (The maze barriers of example6 / maze14 are read from image files: images.gene_barrier_of_example6 / _maze14.)"""
     def heart(x, y, s):
         u, v = s * (x - 0.5), s * (y - 0.5)
         return (u ** 2 + v ** 2 - 1) ** 3 - u ** 2 * v ** 3

@@ -583,6 +583,65 @@ int dotsocp_weights_download(dotsocp_weights *w, int level, double *host);
  * communicator attached; DOTSOCP_ESTATE: after begin(). */
 int dotsocp_upload_weight_from(dotsocp_ctx *ctx, dotsocp_weights *w, int level);
 
+/* ===================================================================================
+ * Problems given as pictures (csrc/image.hip, csrc/image_table.h; twins: dot-socp_amd/images.py)
+ * ===================================================================================
+ * MATLAB's imresize(img, [h_out w_out]) -- bicubic (a = -0.5), antialiased when shrinking, separable -- and the densities
+ * the reference's image-based examples build with it (examples/dot2d/get_example_from_images.m, gene_example5.m,
+ * gene_example_DOTmark_4stitch.m).  Pictures are column-major like everything else: h fastest, then w, planes slowest.
+ * The calls take HOST pointers; the work runs on the device in one go, the result is downloaded once.
+ *
+ * One pass along an axis: out[r] = sum_k weights[r][k] * in[indices[r][k]], k ascending, product and sum separately
+ * rounded (no fused multiply-add).  The axis with the smaller scale n_out / n_in goes first, on a tie the rows.  uint8
+ * pictures store r = floor(acc), r + 1 if acc - r >= 0.5, clamped to 0 .. 255, after EACH pass; double pictures store acc.
+ * A pass of scale 1 runs like any other (its table is the identity).
+ *
+ * The table of a pass: s = n_out / n_in; kernel f = 1.5|x|^3 - 2.5|x|^2 + 1 on [0, 1], -0.5|x|^3 + 2.5|x|^2 - 4|x| + 2 on
+ * (1, 2], width 4; for s < 1 the kernel s f(s x) of width 4 / s.  Output x = 1 .. n_out sits at u = x / s + 0.5 (1 - 1 / s),
+ * takes P = ceil(width) + 2 positions from floor(u - width / 2) on, weights f(u - position) divided by their sum (Neumaier's compensated
+ * sum, positions ascending: a row then sums to 1 within 2 ulp however many taps it has), positions
+ * mirrored through [1 .. n_in, n_in .. 1]; columns that are zero in every row are dropped.  Pure host arithmetic, no device.
+ * dotsocp_imresize_taps returns P, the room per row that dotsocp_imresize_table needs (n_out * P doubles resp. ints); the
+ * table is stored [n_out][*taps] with the taps that remain, indices 0-based.  Lengths: 1 .. DOTSOCP_IMG_MAX_LEN. */
+#define DOTSOCP_IMG_U8 0
+#define DOTSOCP_IMG_F64 1
+#define DOTSOCP_IMG_MAX_LEN 65536
+int dotsocp_imresize_taps(dotsocp_i64 n_in, dotsocp_i64 n_out);
+int dotsocp_imresize_table(dotsocp_i64 n_in, dotsocp_i64 n_out, double *weights, int *indices, int *taps);
+
+/* out (h_out x w_out x planes) <- imresize(in (h_in x w_in x planes)); dtype DOTSOCP_IMG_U8 (unsigned char) or
+ * DOTSOCP_IMG_F64 (double), planes 1 .. 4.  DOTSOCP_EINVAL, with `out` untouched: a length outside 1 .. DOTSOCP_IMG_MAX_LEN,
+ * planes outside 1 .. 4, NULL, out == in, another dtype, a device ordinal out of range.  No device: DOTSOCP_ENODEVICE. */
+int dotsocp_imresize(void *out, const void *in, int dtype, dotsocp_i64 h_in, dotsocp_i64 w_in, dotsocp_i64 planes,
+                     dotsocp_i64 h_out, dotsocp_i64 w_out, int device);
+
+#define DOTSOCP_IMG_SINGLE 0
+#define DOTSOCP_IMG_STITCH4 1
+typedef struct {
+    const unsigned char *pix;      /* h x w x planes */
+    dotsocp_i64 h, w, planes;      /* planes 1 (gray) or 3 (R, G, B) */
+} dotsocp_image;
+typedef struct {
+    dotsocp_i64 ny, nx;            /* the density's grid, each 2 .. DOTSOCP_IMG_MAX_LEN */
+    int layout;                    /* DOTSOCP_IMG_SINGLE: one picture; DOTSOCP_IMG_STITCH4: four */
+    int reverse;                   /* SINGLE only: (255 - v) / 255 instead of v */
+    double lower_bound;            /* finite, > -1 */
+} dotsocp_image_opts;
+
+/* rho (ny x nx doubles) <- the normalised density of the picture(s).
+ *   SINGLE   uint8 resize to (ny - 1) x (nx - 1) per plane; three planes: gray = 0.298936021293775 R + 0.587043074451121 G +
+ *            0.114020904255103 B, added in that order and rounded like a uint8 pass (rgb2gray AFTER the resize,
+ *            get_example_from_images.m:11-20); reverse or not; one zero row and one zero column appended.
+ *   STITCH4  gray first if three planes; each picture resized as uint8 to floor(nx / 2) x floor(ny / 2) -- the reference
+ *            passes nx as the height (gene_example_DOTmark_4stitch.m:55,70-76) --, converted to double, placed [1 2; 3 4];
+ *            where the stitched size is not ny x nx, a double resize to ny x nx (which overshoots on binary pictures:
+ *            negative entries, as in the reference).
+ * Then rho = ((nx ny / sum(rho)) rho + lower_bound) / (1 + lower_bound) (examples/dot2d/get_example.m:45; lower_bound 0:
+ * the bits of get_example_from_images.m:31).  The sum is added in the order of dotsocp_map_report ("Sums": blocks of 256
+ * consecutive entries in memory order, the rest padded with +0.0).  Errors as for dotsocp_imresize, with `rho` untouched;
+ * also DOTSOCP_EINVAL: nimg that does not fit the layout, reverse with STITCH4. */
+int dotsocp_image_density(const dotsocp_image_opts *o, const dotsocp_image *imgs, int nimg, double *rho, int device);
+
 /* runHist.{kkt (len x 7, column-major), time, iter, pdGap} (:350-354); any pointer may be NULL */
 int dotsocp_get_history(dotsocp_ctx *ctx, double *kkt, double *time, double *iter, double *pdGap);
 

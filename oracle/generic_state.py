@@ -73,8 +73,10 @@ def set_state(var, start):
 
 # --------------------------------------------------------------------------------------------------
 # The cases the generic-start tests run (tests/test_generic_state_conditions.py on the CPU asserts for each that the
-# start does its job; tests/test_gpu_generic_state.py compares the device loops with the same oracle runs).
-# shape: (ny, nx, nt), or (nx, nt) for the 1-D problem.  Every entry may carry seed / amplitudes / shift of its own.
+# start does its job; tests/test_gpu_generic_state.py and tests/test_gpu_generic_accadmm.py compare the device loops with
+# the same oracle runs).
+# shape: (ny, nx, nt), or (nx, nt) for the 1-D problem.  Every entry may carry seed / amplitudes / shift of its own, and
+# solver options (restart, rho, theta, ifCheckStepByStep) under `opts`.
 # --------------------------------------------------------------------------------------------------
 CASES = {
     "inPALM-130x9x7": dict(method="inPALM", shape=(130, 9, 7), K=12),
@@ -100,12 +102,58 @@ CASES = {
     # every row a surface row; PALM's polar rows are gone after iteration 7
     "PALM-66x10x6": dict(method="PALM", shape=(66, 10, 6), K=7, shift=20.0, amplitudes=dict(phi=0.02, beta=0.1)),
     "acc-ADMM-66x10x6": dict(method="acc-ADMM", shape=(66, 10, 6), K=12, shift=20.0, amplitudes=dict(phi=0.02)),
+    # --- acc-ADMM on every path of its device loop.  `opts` are solver options of the case (case_opts merges them).
+    # The tile-crossing grids of the inPALM cases; on 100 x 70 x 20 the polar rows are gone by iteration 17 whatever the
+    # amplitudes: K = 13
+    # (130 x 9 x 7 with phi = 0.02 changes sigma at every check; a smaller phi and beta bring the residual ratio of the check
+    # at iteration 1 to 1.02, inside the band (1/1.1, 1.1) that leaves sigma alone)
+    "acc-ADMM-130x9x7": dict(method="acc-ADMM", shape=(130, 9, 7), K=12, shift=20.0,
+                             amplitudes=dict(phi=0.002, beta=0.1)),
+    "acc-ADMM-100x70x20": dict(method="acc-ADMM", shape=(100, 70, 20), K=13, shift=40.0,
+                               amplitudes=dict(phi=0.02, alpha=2.5, z=2.0)),
+    # a restart by count fires between checks only with restart <= 3: sigma changes at almost every check, which resets k
+    # every three iterations
+    "acc-ADMM-restart2-66x10x6": dict(method="acc-ADMM", shape=(66, 10, 6), K=12, shift=20.0, amplitudes=dict(phi=0.02),
+                                      opts=dict(restart=2, rho=1.7)),
+    # theta != 2: the extrapolation with its hatOld carry, no Halpern anchors
+    "acc-ADMM-theta3-66x10x6": dict(method="acc-ADMM", shape=(66, 10, 6), K=12, shift=20.0, amplitudes=dict(phi=0.02),
+                                    opts=dict(theta=3.0, restart=3)),
+    "acc-ADMM-theta3-130x9x7": dict(method="acc-ADMM", shape=(130, 9, 7), K=12, shift=20.0,
+                                    amplitudes=dict(phi=0.002, beta=0.1), opts=dict(theta=3.0, restart=3)),
+    "acc-ADMM-theta5-66x10x6": dict(method="acc-ADMM", shape=(66, 10, 6), K=12, shift=20.0, amplitudes=dict(phi=0.02),
+                                    opts=dict(theta=5.0, restart=8)),
+    # a KKT check in every iteration
+    "acc-ADMM-checkstep-66x10x6": dict(method="acc-ADMM", shape=(66, 10, 6), K=8, shift=20.0, amplitudes=dict(phi=0.02),
+                                       opts=dict(ifCheckStepByStep=True)),
+    "acc-ADMM-checkstep-theta3-66x10x6": dict(method="acc-ADMM", shape=(66, 10, 6), K=8, shift=20.0,
+                                              amplitudes=dict(phi=0.02),
+                                              opts=dict(ifCheckStepByStep=True, theta=3.0, restart=3)),
+    # 1e6 barrier weights
+    "acc-ADMM-weighted-66x10x6": dict(method="acc-ADMM", shape=(66, 10, 6), K=12, weighted=True, shift=20.0,
+                                      amplitudes=dict(phi=0.02)),
+    "acc-ADMM-weighted-130x9x7": dict(method="acc-ADMM", shape=(130, 9, 7), K=12, weighted=True, shift=20.0,
+                                      amplitudes=dict(phi=0.02, alpha=2.5)),
+    "acc-ADMM-weighted-theta3-66x10x6": dict(method="acc-ADMM", shape=(66, 10, 6), K=12, weighted=True, shift=20.0,
+                                             amplitudes=dict(phi=0.02), opts=dict(theta=3.0, restart=3)),
+    # the time-slab grid.  The inside branch of iteration 2 is the bottleneck of the Halpern cases: at rho = 2 it gets a
+    # share of 0.0014 here, at rho = 1.5 (a regular option of the loop) 0.0052
+    "acc-ADMM-40x12x13": dict(method="acc-ADMM", shape=(40, 12, 13), K=12, shift=20.0, amplitudes=dict(phi=0.02),
+                              opts=dict(rho=1.5)),
+    "acc-ADMM-theta3-40x12x13": dict(method="acc-ADMM", shape=(40, 12, 13), K=12, shift=20.0, amplitudes=dict(phi=0.02),
+                                     opts=dict(theta=3.0, restart=3)),
+    "acc-ADMM-weighted-40x12x13": dict(method="acc-ADMM", shape=(40, 12, 13), K=12, weighted=True, shift=20.0,
+                                       amplitudes=dict(phi=0.02, alpha=2.5)),
+    "acc-ADMM-checkstep-40x12x13": dict(method="acc-ADMM", shape=(40, 12, 13), K=8, shift=20.0, amplitudes=dict(phi=0.02),
+                                        opts=dict(ifCheckStepByStep=True, rho=1.5)),
+    "PALM-40x12x13": dict(method="PALM", shape=(40, 12, 13), K=7, shift=20.0, amplitudes=dict(phi=0.02, beta=0.1)),
 }
 
 # KKT column 5 (index 4), sigma ||F*B*beta + D_w alpha||, is zero in exact arithmetic for the loops whose multiplier step
 # has length 1 (ALG2: tau = 1, acc-ADMM): there the q-step's optimality condition diagQ q = A phi + alpha + F*B*(z + beta)
 # and diagQ = I + F*B*BF give F*B*beta^+ + alpha^+ = 0 identically, whatever the data.  No start makes it generic; it is
 # rounding noise (1e-16) that moves by O(1) relative under a one-ulp perturbation, and is held to an absolute bound instead.
+# (Under 1e6 weights acc-ADMM leaves 1e-11 .. 3e-11 there, mostly systematic: a bound of its own,
+# tests/test_generic_state_conditions.py: NOISE_WEIGHTED.)
 CANCELLING_COLUMNS = {"ALG2": (4,), "acc-ADMM": (4,)}
 
 
@@ -129,7 +177,8 @@ def problem(case):
 
 
 def case_opts(case):
-    return dict(tol=0.0, maxit=CASES[case]["K"])
+    """tol = 0 and maxit = K, with the case's own solver options (restart, rho, theta, ifCheckStepByStep) over them."""
+    return dict(dict(tol=0.0, maxit=CASES[case]["K"]), **CASES[case].get("opts", {}))
 
 
 def case_start(case, var):
@@ -155,7 +204,9 @@ def oracle_run(case, perturb=False):
     """The oracle's free-running loop of a case from its generic start, computed once per process and shared (treat
     the result as read-only).  Returns a dict: var (the finished level), start, hist, sigma, shares (one
     (polar, inside, surface) triple per z-step projection, the projection inside the KKT block not counted),
-    weight, and the level's opts."""
+    weight, and the level's opts; for acc-ADMM also sigma_updates ((iteration, factor) of every check that changed
+    sigma), restarts (the iterations whose extrapolation ended with the count back at 0) and interps ((iteration, k)
+    of every extrapolation, k the count it ran with)."""
     key = (case, bool(perturb))
     if key in _runs:
         return _runs[key]
@@ -176,6 +227,25 @@ def oracle_run(case, perturb=False):
             shares.append(branch_shares(inp))
         plain(out, inp)
 
+    # acc-ADMM: the iterations at which a check changed sigma (with the factor), and those at which the extrapolation
+    # count returned to 0 inside _interpolate (a restart by count, as opposed to the reset a sigma update makes)
+    sigma_updates, restarts, interps = [], [], []
+    if hasattr(st, "_interpolate"):
+        apply_factor, interpolate = st._apply_sigma_factor, st._interpolate
+
+        def recording_factor(factor):
+            sigma_updates.append((st.it, float(factor)))
+            apply_factor(factor)
+
+        def recording_interpolate():
+            k = st.k
+            interpolate()
+            interps.append((st.it, k))
+            if st.k == 0:
+                restarts.append(st.it)
+
+        st._apply_sigma_factor, st._interpolate = recording_factor, recording_interpolate
+
     mexops.mexProjSoc = counting
     try:
         st.run()
@@ -184,5 +254,6 @@ def oracle_run(case, perturb=False):
     hist, sigma = st.finish()
     for f in FIELDS:
         getattr(var, f).flags.writeable = False
-    _runs[key] = dict(var=var, start=start, hist=hist, sigma=sigma, shares=np.array(shares), weight=weight, opts=o)
+    _runs[key] = dict(var=var, start=start, hist=hist, sigma=sigma, shares=np.array(shares), weight=weight, opts=o,
+                      sigma_updates=sigma_updates, restarts=restarts, interps=interps)
     return _runs[key]

@@ -86,6 +86,14 @@ class RenderInfo(ctypes.Structure):
     _fields_ = [("vmax", dbl), ("rho_min", dbl), ("nonfinite", i64), ("masked", i64), ("my", i64), ("mx", i64)]
 
 
+class Dual(ctypes.Structure):
+    """dotsocp_dual"""
+    _fields_ = [("n_nodes", i64), ("nonfinite", i64), ("mass0", dbl), ("mass1", dbl),
+                ("dual_raw", dbl), ("bound_fwd", dbl), ("bound_bwd", dbl), ("bound", dbl),
+                ("gap1_max", dbl), ("gap1_min", dbl), ("gap1_mean", dbl),
+                ("gap0_max", dbl), ("gap0_min", dbl), ("gap0_mean", dbl), ("map_cost_bwd", dbl)]
+
+
 class ImageOpts(ctypes.Structure):
     """dotsocp_image_opts"""
     _fields_ = [("ny", i64), ("nx", i64), ("layout", ctypes.c_int), ("reverse", ctypes.c_int), ("lower_bound", dbl)]
@@ -144,6 +152,7 @@ SYMBOLS = {
                                           vp, vp, vp]),
     "dotsocp_render_evolution": (ctypes.c_int, [vp, vp, vp, ctypes.POINTER(RenderOpts), vp, vp, vp, vp, vp, vp, vp,
                                                 ctypes.POINTER(RenderInfo)]),
+    "dotsocp_dual_bound": (ctypes.c_int, [vp, vp, vp, ctypes.POINTER(Dual), vp, vp, vp, vp]),
     "dotsocp_jump_next_level": (ctypes.c_int, [vp, vp]),
     "dotsocp_finish": (ctypes.c_int, [vp, ctypes.POINTER(Result)]),
     "dotsocp_get_history": (ctypes.c_int, [vp, vp, vp, vp, vp]),

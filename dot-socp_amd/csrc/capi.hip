@@ -392,6 +392,12 @@ int dotsocp_map_report(dotsocp_ctx *ctx, const double *rho0, const double *rho1,
     return ctx->s.map_report(rho0, rho1, o, x, y, mass, rep, disp, len, action);
 }
 
+int dotsocp_dual_bound(dotsocp_ctx *ctx, const double *rho0, const double *rho1, dotsocp_dual *res, double *H, double *B,
+                       int *arg_fwd, int *arg_bwd) {
+    CTX_OR_FAIL();
+    return ctx->s.dual_bound(rho0, rho1, res, H, B, arg_fwd, arg_bwd);
+}
+
 int dotsocp_render_evolution(dotsocp_ctx *ctx, const double *rho0, const double *rho1, const dotsocp_render_opts *opts,
                              const dotsocp_i64 *frame_nodes, const double *levels, const unsigned char *lut,
                              const unsigned char *barrier, unsigned char *image, double *mvx, double *mvy,
@@ -445,7 +451,8 @@ int dotsocp_kernel_time(dotsocp_ctx *ctx, const char *name, double *avg_ms, dots
     static const char *names[PH_COUNT] = {"rhs", "poisson", "cone_proj", "qstep", "beta", "kkt",
                                           "cone_fused_a", "cone_fused_b", "materialise", "comm",
                                           "interp", "acc_cone", "acc_gather", "qstep_first", "transpose", "cone_carry", "qcone",
-                                          "velocity_layer", "advect", "deposit", "frame_l1", "advect_path", "map_final"};
+                                          "velocity_layer", "advect", "deposit", "frame_l1", "advect_path", "map_final",
+                                          "hl_pass_x", "hl_pass_y", "hl_reduce"};
     for (int i = 0; i < PH_COUNT; ++i)
         if (strcmp(name, names[i]) == 0) {
             const i64 n = ctx->s.phase_launches[i];

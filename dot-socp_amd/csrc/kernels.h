@@ -224,6 +224,35 @@ int launch_report(const Grid &g, const double *q, const double *alpha, const dou
                   const double *rho1, const double *a_prev, double sig, double cD, double dD, bool dim1, const double *edges,
                   double *partials, double *sums, unsigned long long *counts, hipStream_t st);
 
+// ---------------- hopflax.hip: Hopf-Lax transform of a node layer, sums of the dual bound (dotsocp_dual_bound) ----------------
+#define HL_MAX_LEN (1 << 20)        // nodes of a line (the limit of the DCT)
+#define HL_YOUT 1024                // outputs of a workgroup of the y pass: one line, 256 threads with 4 outputs each
+#define HL_CHUNK_MAX 1024           // inputs the y pass stages at a time (DOTSOCP_HL_CHUNK lowers it)
+#define HL_XOUT 32                  // outputs of a workgroup of the x pass: 64 lines, 4 wavefronts with 8 outputs each
+#define HL_XCHUNK_MAX 32            // inputs the x pass stages at a time (DOTSOCP_HL_CHUNK lowers it)
+// One pass of the transform over `lines` lines of n nodes: out[j] = min_i in[i] + (double)((i - j)^2) w (forward) resp.
+// max_i in[i] - ... (backward), w = (0.5 h) h, h = 1 / (n - 1); arg[j] = the smallest winning i.  Non-finite inputs count as
+// +Inf / -Inf.  pass_y: the nodes of a line are contiguous, lines `pitch` apart; pass_x: lines are contiguous (1 apart), the
+// nodes of a line `pitch` apart.  in != out; arg has the layout of out.
+int launch_hl_pass_y(bool forward, const double *in, double *out, int *arg, i64 n, i64 lines, i64 pitch, hipStream_t st);
+int launch_hl_pass_x(bool forward, const double *in, double *out, int *arg, i64 n, i64 lines, i64 pitch, hipStream_t st);
+int hl_chunk(int deflt);            // min(deflt, DOTSOCP_HL_CHUNK), at least 1 (read at every call: a test switch)
+int launch_hl_layer(const double *in, double *out, i64 n, double mul, hipStream_t st);      // out = mul * in
+// rows of the partial sums and slots of the 64-bit counters (zeroed before the launch; extrema as the keys of the report)
+enum { HS_M0 = 0, HS_M1, HS_P0R0, HS_P1R1, HS_HR1, HS_BR0, HS_G1, HS_G0, HS_MAP, HS_COUNT };
+enum { HC_G1_MAX = 0, HC_G1_MIN, HC_G0_MAX, HC_G0_MIN, HC_NONFINITE, HC_COUNT };
+struct HlReduceArgs {
+    i64 ny, nx, py;                 // layers ny x nx, rows py apart
+    const double *phi0, *phi1, *H, *B, *rho0, *rho1;
+    const int *ixf, *iyf, *ixb, *iyb;       // winners of the passes (ix*: nullptr for a 1-D line)
+    int *arg_fwd, *arg_bwd;         // flat winner of every node, iy + ny * ix[iy, x]
+    double hx, hy;                  // 1 / (nx - 1), 1 / (ny - 1)
+    double *partials;               // [HS_COUNT][hl_blocks(ny * nx)]
+    unsigned long long *counts;     // [HC_COUNT]
+};
+i64 hl_blocks(i64 nodes);
+int launch_hl_reduce(const HlReduceArgs &a, double *sums /* HS_COUNT */, hipStream_t st);
+
 // ---------------- render.hip: pictures of the density evolution (dotsocp_render_evolution) ----------------
 // Slots of the 64-bit counters of the range pass (zeroed before the launch): max / min of the finite unmasked rho as the
 // keys of the report (max: report_key_decode(k, false, .), min: (k, true, .); 0: no value), then two plain counts

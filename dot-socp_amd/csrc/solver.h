@@ -135,7 +135,7 @@ bool if_adjust_sigma(double iter, double last_iter);   // IfAdjustSigma (solver_
 
 enum Phase { PH_RHS = 0, PH_POISSON, PH_PROJ, PH_QSTEP, PH_BETA, PH_KKT, PH_FUSED_A, PH_FUSED_B, PH_MATERIALISE,
              PH_COMM, PH_INTERP, PH_ACC_CONE, PH_ACC_GATHER, PH_QSTEP0, PH_TRANSPOSE, PH_CONE_CARRY, PH_QCONE, PH_VELOCITY, PH_ADVECT,
-             PH_DEPOSIT, PH_FRAME_L1, PH_ADVECT_PATH, PH_MAP_FINAL, PH_COUNT };
+             PH_DEPOSIT, PH_FRAME_L1, PH_ADVECT_PATH, PH_MAP_FINAL, PH_HL_PASS_X, PH_HL_PASS_Y, PH_HL_REDUCE, PH_COUNT };
 
 // The schedule of the gamma form (fused.hip, Solver::step): pure host arithmetic, also behind the C ABI.
 // rescale_due: the rescale block of iteration `it` takes its norms or rescales (solver_socp_inPALM.m:138-151), given the
@@ -303,6 +303,11 @@ struct Solver {
                   const i64 *frame_nodes, double *frames, i64 *n_clamped, double *unit, double *l1);
     int map_report(const double *rho0, const double *rho1, const dotsocp_advect_opts *o, double *x, double *y, const double *mass,
                    dotsocp_map_report_t *rep, double *disp, double *len, double *action);
+
+    // ================ the dual lower bound on W2^2: solver_dual.hip ================
+    // Hopf-Lax transforms of phi's first and last node layer and the sums of the Kantorovich dual (hopflax.hip), on the first
+    // slab's device; H, B (ny x nx doubles), arg_fwd, arg_bwd (ny x nx ints): host, each may be NULL
+    int dual_bound(const double *rho0, const double *rho1, dotsocp_dual *res, double *H, double *B, int *arg_fwd, int *arg_bwd);
 
     // ================ the inPALM loop and its profiling: solver.hip ================
     // ---- loop state (mirrors solver_socp_inPALM.m:11-135) ----

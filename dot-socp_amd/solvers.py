@@ -222,6 +222,23 @@ class InPALMContext:
                                                       capi.fptr(mass), capi.fptr(neg)))
         return from_struct(rep, mass, neg)
 
+    def dual_bound(self, arrays=False):
+        """A lower bound on W2^2 between the node histograms of rho0 and rho1, on the device (dotsocp_dual_bound; dual.py):
+        the Hopf-Lax transform of phi(t = 0) forward to t = 1 and of phi(t = 1) back to t = 0, and the Kantorovich dual of
+        each pair -- valid whatever state the solve is in.  Returns a dual.DualBound (bound, bound_fwd, bound_bwd, dual_raw,
+        the Hopf-Lax gaps at both ends, map_cost_bwd, ...); arrays=True adds H, B (the transforms) and arg_fwd, arg_bwd (int32,
+        the flat winning node of every node, y fastest).  Same bits as dual.dual_bound() of the downloaded, recovered layers.
+        Call after finish(); unweighted contexts only."""
+        from .dual import from_struct
+        m = self.model
+        shp = (int(m.nx),) if not hasattr(m, "ny") else (int(m.ny), int(m.nx))
+        r0, r1 = self._rho_ends()
+        res = capi.Dual()
+        arr = [np.empty(shp, order="F", dtype=t) if arrays else None for t in (np.float64, np.float64, np.int32, np.int32)]
+        ptr = lambda a: None if a is None else a.ctypes.data         # noqa: E731
+        capi.check(capi.lib().dotsocp_dual_bound(self._ctx, capi.fptr(r0), capi.fptr(r1), ctypes.byref(res), *[ptr(a) for a in arr]))
+        return from_struct(res, *arr)
+
     def render(self, frames=None, num_frame=6, mode="imshow", nlevels=128, lut=None, barrier=None, vmax=None, arrows=False,
                barrier_index=255, levels=None):
         """Pictures of the density evolution on the device (dotsocp_render_evolution; render.py): uint8 frames at the nodes
@@ -476,7 +493,7 @@ def _weights_mode(weight, weights, transfer, weighted=True):
 
 
 def _solve_levels(rho0, rho1, nt, levelN, opts, method, dim, weighted, device, barrier=None, transfer="device",
-                  weights=None, report=False, advect=None, push=None, map_report=None, render=None):
+                  weights=None, report=False, advect=None, push=None, map_report=None, render=None, dual=False):
     """The level loop of solver_dotsocp2d.m:154-250 (dot1d / wdot2d twins): restrict the data to
     levelN grids, solve coarse to fine with warm starts; every solve runs on the device.
     transfer = "device": the state never leaves the GPU -- jump_nextLevel and the output recovery run there
@@ -498,7 +515,9 @@ def _solve_levels(rho0, rho1, nt, levelN, opts, method, dim, weighted, device, b
     asked of the last level's context; output["push"] holds its result.  Needs transfer="device".
     map_report = dict(stride=..., nsub=..., direction=..., rho_floor=...): the keyword arguments of
     InPALMContext.map_report_from_nodes() -- what the map realised by the flow costs and how straight and steady its paths
-    are -- asked of the last level's context; output["map_report"] holds its result.  Needs transfer="device"."""
+    are -- asked of the last level's context; output["map_report"] holds its result.  Needs transfer="device".
+    dual = True: the last level's context is asked for the dual lower bound on W2^2 (InPALMContext.dual_bound(), dual.py);
+    output["dual"] holds it.  Needs transfer="device"; a weighted context refuses (capi.DotsocpError)."""
     from . import multilevel as ML
     from .examples import ensure_barrier_validity
     if not (isinstance(levelN, (int, np.integer)) and levelN >= 1):
@@ -513,6 +532,8 @@ def _solve_levels(rho0, rho1, nt, levelN, opts, method, dim, weighted, device, b
         raise ValueError("push= needs transfer='device' (the mass moves through the device-resident state)")
     if map_report is not None and transfer != "device":
         raise ValueError("map_report= needs transfer='device' (the particles move through the device-resident state)")
+    if dual and transfer != "device":
+        raise ValueError("dual=True needs transfer='device' (the bound is taken from the device-resident potential)")
     if render is not None and transfer != "device":
         raise ValueError("render= needs transfer='device' (the pictures are made from the device-resident state)")
     wopt = _get(opts, "weight") if weighted else None
@@ -595,6 +616,8 @@ def _solve_levels(rho0, rho1, nt, levelN, opts, method, dim, weighted, device, b
                 output = ctx.outputs()
                 if report:
                     output["report"] = ctx.report()
+                if dual:
+                    output["dual"] = ctx.dual_bound()
                 if advect is not None:
                     output["advect"] = ctx.advect(**advect)
                 if push is not None:
@@ -640,41 +663,42 @@ def _solve_levels(rho0, rho1, nt, levelN, opts, method, dim, weighted, device, b
 
 
 def solver_dotsocp2d(rho0, rho1, nt, levelN, opts, method="inPALM", device=0, transfer="device", report=False,
-                     advect=None, push=None, map_report=None, render=None):
+                     advect=None, push=None, map_report=None, render=None, dual=False):
     """[output, timeML, runHistML, runHist] = solver_dotsocp2d(rho0, rho1, nt, levelN, opts, method)
     socp/dot2d/solver_dotsocp2d.m:1.  report=True: output["report"] = the device-side solution report; advect=dict(x=..., y=...,
     ...): output["advect"] = the particles carried along the solved flow; push=dict(stride=..., frames=..., ...):
     output["push"] = the given density carried along it and deposited at the frame nodes; map_report=dict(stride=..., ...):
     output["map_report"] = cost, straightness and steadiness of the map the flow realises; render=dict(num_frame=..., mode=...,
-    arrows=..., ...): output["render"] = uint8 pictures of the density evolution and the arrows of the flux (all five:
-    _solve_levels)."""
+    arrows=..., ...): output["render"] = uint8 pictures of the density evolution and the arrows of the flux; dual=True:
+    output["dual"] = the dual lower bound on W2^2 from the potential (all six: _solve_levels)."""
     output, timeML, runHistML, runHist = _solve_levels(rho0, rho1, nt, levelN, opts, method, 2, False, device,
                                                        transfer=transfer, report=report, advect=advect, push=push, map_report=map_report,
-                                                       render=render)
+                                                       render=render, dual=dual)
     if not check_massConservation(output["rho"], 1e-2):
         print("Warning: The mass conservation constraint violation exceeds 0.01")
     return output, timeML, runHistML, runHist
 
 
 def solver_dotsocp1d(rho0, rho1, nt, levelN, opts, method="inPALM", device=0, transfer="device", report=False,
-                     advect=None, push=None, map_report=None, render=None):
-    """socp/dot1d/solver_dotsocp1d.m:1.  report, advect, push, map_report, render: as for solver_dotsocp2d."""
+                     advect=None, push=None, map_report=None, render=None, dual=False):
+    """socp/dot1d/solver_dotsocp1d.m:1.  report, advect, push, map_report, render, dual: as for solver_dotsocp2d."""
     output, timeML, runHistML, runHist = _solve_levels(rho0, rho1, nt, levelN, opts, method, 1, False, device,
                                                        transfer=transfer, report=report, advect=advect, push=push, map_report=map_report,
-                                                       render=render)
+                                                       render=render, dual=dual)
     if not check_massConservation(output["rho"], 1e-2):
         print("Warning: The mass conservation constraint violation exceeds 0.01")
     return output, timeML, runHistML, runHist
 
 
 def solver_wdotsocp2d(rho0, rho1, nt, levelN, opts, method="inPALM", barrier=None, device=0, transfer="device",
-                      weights=None, report=False, advect=None, push=None, map_report=None, render=None):
+                      weights=None, report=False, advect=None, push=None, map_report=None, render=None, dual=False):
     """socp/wdot2d/solver_wdotsocp2d.m:1.  opts["weight"]: the Nq array, or a SpaceWeight (examples.py); weights:
     where the levels' weights are made, "host" or "device" (_solve_levels); report, advect, push, map_report, render: as for
-    solver_dotsocp2d (render: `barrier` is the default mask of the pictures)."""
+    solver_dotsocp2d (render: `barrier` is the default mask of the pictures; dual=True raises the library's refusal: the
+    weighted cost is not the Euclidean one)."""
     output, timeML, runHistML, runHist = _solve_levels(rho0, rho1, nt, levelN, opts, method, 2, True, device,
                                                        barrier=barrier, transfer=transfer, weights=weights, report=report,
-                                                       advect=advect, push=push, map_report=map_report, render=render)
+                                                       advect=advect, push=push, map_report=map_report, render=render, dual=dual)
     if not check_massConservation(output["rho"], 1e-2):
         print("Warning: The tolerance of mass conservation constraint is under 0.01")
     return output, timeML, runHistML, runHist

@@ -469,6 +469,58 @@ int dotsocp_map_report(dotsocp_ctx *ctx, const double *rho0, const double *rho1,
                        double *x, double *y, const double *mass, dotsocp_map_report_t *rep, double *disp, double *len,
                        double *action);
 
+/* A lower bound on the transport cost from the potential: every other judgement of a solve (KKT history, report, map
+ * report) lives inside the discretised dynamic problem; this one certifies the quantity asked for.  For ANY function psi0 on
+ * the nodes and psi1(y) = min_x psi0(x) + |x - y|^2 / 2 one has psi1(y) - psi0(x) <= |x - y|^2 / 2 for every pair of nodes,
+ * hence 2 (sum psi1 b - sum psi0 a) <= W2^2(a, b) for the node histograms a = rho0 / sum(rho0), b = rho1 / sum(rho1) --
+ * whatever state the solve is in.  With psi0 = phi(t = 0) this is the Hopf-Lax transform of the potential to t = 1; the
+ * mirror transform of phi(t = 1) back to t = 0 gives a second bound.  What is certified is the DISCRETE STATIC cost
+ * between the node histograms (it differs from the continuous W2^2 by O(h)), up to the rounding of the sums.
+ *
+ * One axis of n nodes, h = 1.0 / (double)(n - 1), w = (0.5 * h) * h:
+ *     forward    out[j] = min_i ( in[i] + (double)((i - j)^2) * w )        backward   out[i] = max_j ( in[j] - (double)((i - j)^2) * w )
+ *   the square exactly in integers; each candidate one product and then one sum or difference, separately rounded; on ties
+ *   the SMALLEST index wins; the value is the candidate at the winning index (so the sign of a zero follows the index).
+ *   Before the transform every non-finite input (NaN, +-Inf) counts as +Inf (forward) resp. -Inf (backward); a line without a
+ *   finite entry gives index 0.
+ * Two axes: the pass along x (every row y: T(y, x'), winner ix(y, x')) followed by the pass along y on its result (every
+ *   column x': value at (y', x'), winner iy(y', x')).  The winning node of (y', x') is (iy, ix[iy, x']), returned as the flat
+ *   index iy + ny * ix[iy, x'] (y fastest, int32).  1-D problems: one pass, the index itself.
+ * Inputs.  phi0, phi1: the first and last node layer of phi in original units, dScale * phi (recoverOrgVar,
+ *   solver_dotsocp2d.m:368-386: one product per entry).  rho0, rho1 (ny x nx, host; 1-D: nx) as for dotsocp_solution_report.
+ * Results.  H = forward(phi0), B = backward(phi1).  Every sum below runs over the nodes in memory order (y fastest) and is
+ *   added by the tree of dotsocp_map_report ("Sums", the node index in the place of the particle index): two calls and any
+ *   slab split give the same bits.  m0 = sum rho0, m1 = sum rho1, and with  a0 = (sum phi0 rho0) / m0,
+ *   a1 = (sum phi1 rho1) / m1:
+ *     dual_raw  = 2.0 * (a1 - a0)
+ *     bound_fwd = 2.0 * ((sum H rho1) / m1 - a0)          bound_bwd = 2.0 * (a1 - (sum B rho0) / m0)
+ *     bound     = bound_bwd > bound_fwd ? bound_bwd : bound_fwd
+ *   The Hopf-Lax gap at t = 1, g = phi1 - H: gap1_max / gap1_min over the finite g (a -0.0 counts as +0.0; -Inf / +Inf if there
+ *   is none), gap1_mean = (sum |g| rho1) / m1; the same for g = phi0 - B at t = 0 with rho0 and m0 (gap0_*).
+ *     map_cost_bwd = (sum rho0 d2) / m0,  d2 = ex * ex + ey * ey,  ex = (double)(x - tx) * hx,  ey = (double)(y - ty) * hy
+ *   (1-D: d2 = ex * ex) with (ty, tx) the backward winner of node (y, x), hx = 1.0 / (double)(nx - 1), hy likewise: the cost of
+ *   the map the potential itself names.  nonfinite = the non-finite entries of phi0 and phi1; the sums take phi as it is.
+ *   No contraction of a * b + c anywhere: dual.py restates all of it in numpy with the same bits.
+ * Optional outputs (host; each is written only when its pointer is not NULL): H, B: ny x nx doubles; arg_fwd, arg_bwd: ny x nx
+ *   ints, the flat winners.  1-D: nx entries each.
+ *
+ * After finish() (DOTSOCP_ESTATE before); inPALM / ALG2, PALM and acc-ADMM contexts, 1-D and 2-D; one slab, `nslabs` slabs and
+ * dotsocp_create_multi (phi1 lives on the last slab: that one layer is brought to the first slab's device, where all the
+ * work runs).  DOTSOCP_EINVAL, with res and the optional outputs untouched: a NULL rho0 / rho1 / res, a context with an RCCL
+ * communicator attached, a weighted context (its cost is not the Euclidean one: the bound would be wrong), an axis of more
+ * than 2^20 nodes, m0 or m1 not positive and finite. */
+typedef struct {
+    dotsocp_i64 n_nodes;                    /* ny * nx (1-D: nx) */
+    dotsocp_i64 nonfinite;                  /* NaN / Inf among phi0 and phi1 (0 for a healthy solve) */
+    double mass0, mass1;                    /* m0, m1 */
+    double dual_raw, bound_fwd, bound_bwd, bound;
+    double gap1_max, gap1_min, gap1_mean;   /* phi1 - H at t = 1 */
+    double gap0_max, gap0_min, gap0_mean;   /* phi0 - B at t = 0 */
+    double map_cost_bwd;
+} dotsocp_dual;
+int dotsocp_dual_bound(dotsocp_ctx *ctx, const double *rho0, const double *rho1, dotsocp_dual *res, double *H, double *B,
+                       int *arg_fwd, int *arg_bwd);
+
 /* Pictures of the density evolution on the device: what utils/show_evolution_2d.m, show_movement_2d.m and
  * export_evolution_2d.m draw from the downloaded outputs -- gray or colour-mapped frames, filled log-spaced levels, the
  * arrows of the flux -- formed from the device-resident alpha.  A frame reads the two alpha layers around its node; what
@@ -657,7 +709,8 @@ int dotsocp_get_history(dotsocp_ctx *ctx, double *kkt, double *time, double *ite
  * "velocity_layer", "advect" (the launches of dotsocp_recover_velocity / dotsocp_advect_particles on the first slab),
  * "deposit", "frame_l1" (the per-frame launches of dotsocp_push_mass on the first slab), "advect_path" (the accumulating
  * march of dotsocp_map_report on the first slab: counted here, not under "advect"), "map_final" (its one reduction, when
- * the first slab runs it: one slab, or direction -1). */
+ * the first slab runs it: one slab, or direction -1), "hl_pass_x", "hl_pass_y", "hl_reduce" (the min-plus passes along x and y and the
+ * reduction of dotsocp_dual_bound). */
 int dotsocp_set_profiling(dotsocp_ctx *ctx, int on);
 int dotsocp_kernel_time(dotsocp_ctx *ctx, const char *name, double *avg_ms, dotsocp_i64 *launches);
 

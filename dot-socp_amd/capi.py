@@ -159,6 +159,8 @@ SYMBOLS = {
     "dotsocp_set_profiling": (ctypes.c_int, [vp, ctypes.c_int]),
     "dotsocp_kernel_time": (ctypes.c_int, [vp, ctypes.c_char_p, ctypes.POINTER(dbl), ctypes.POINTER(i64)]),
     "dotsocp_canary_check": (ctypes.c_int, []),
+    "dotsocp_debug_alloc_peek": (ctypes.c_int, [i64, vp]),
+    "dotsocp_debug_cache_held": (i64, [ctypes.c_int]),
     "dotsocp_poisson_phi": (ctypes.c_int, [vp]),
     "dotsocp_synchronize": (ctypes.c_int, [vp]),
     "dotsocp_weights_create": (vp, [ctypes.c_int, i64, i64, i64, ctypes.c_int]),

@@ -464,6 +464,19 @@ int dotsocp_kernel_time(dotsocp_ctx *ctx, const char *name, double *avg_ms, dots
     return DOTSOCP_EINVAL;
 }
 
+// test hooks of the allocator (guard.hip): what n doubles from dmalloc hold as they are handed out -- no kernel of the
+// library runs on them; the bytes the device block cache holds on one device (device < 0: on all)
+int dotsocp_debug_alloc_peek(dotsocp_i64 n, double *out) {
+    DS_ARG(n >= 1 && out != nullptr, "debug_alloc_peek() needs n >= 1 and an array of n doubles");
+    DS_CHECK(require_device());
+    DevBuf d;
+    DS_CHECK(d.alloc(n));
+    DS_HIP(hipMemcpy(out, d.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+dotsocp_i64 dotsocp_debug_cache_held(int device) { return (dotsocp_i64)device_cache_held(device); }
+
 int dotsocp_canary_check(void) {
     std::string rep;
     const int bad = canary_check(&rep);

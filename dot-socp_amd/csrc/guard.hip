@@ -28,8 +28,22 @@ struct Rec {
 std::mutex g_mu;
 std::map<void *, Rec> g_live;      // user pointer -> record
 
-__global__ void k_fill_pattern(unsigned long long *p, size_t n) {
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) p[i] = PATTERN;
+static_assert(POISON_WORD != PATTERN, "a report must tell an uninitialised read from one out of bounds");
+
+__global__ void k_fill_pattern(unsigned long long *p, size_t n, unsigned long long word) {
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) p[i] = word;
+}
+
+// the whole 8-byte words of [p, p + bytes) <- POISON_WORD, on the null stream; the caller synchronises
+int poison_fill(void *p, size_t bytes) {
+    const size_t n = bytes / 8;
+    if (n == 0) return 0;
+    const size_t blocks = (n + 255) / 256;
+    (void)hipGetLastError();
+    DS_KLAUNCH(k_fill_pattern, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(256), 0, nullptr, (unsigned long long *)p, n,
+               POISON_WORD);
+    DS_HIP(hipGetLastError());
+    return 0;
 }
 
 // one workgroup that idles for about `ticks` of the 100 MHz wall clock (bounded: every wave leaves after 2^20 polls at most)
@@ -70,6 +84,18 @@ bool canary_enabled() {
     return e && atoi(e) != 0;
 }
 
+bool poison_enabled() {
+    const char *e = getenv("DOTSOCP_POISON");
+    return e && atoi(e) != 0;
+}
+
+int poison_region(void *p, size_t bytes) {
+    if (!poison_enabled() || !p) return 0;
+    DS_CHECK(poison_fill(p, bytes));
+    DS_HIP(hipStreamSynchronize(nullptr));
+    return 0;
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // Device block cache.  hipFree of a context's buffers is cheap, but the NEXT hipMalloc pays for it: measured on the
 // MI355X boxes, creating a 1025 x 1025 x 129 context (54 GB in ~40 buffers) takes 0.67 s in a fresh process and 1.65 s
@@ -77,8 +103,9 @@ bool canary_enabled() {
 // only once it is wiped), and a context created next to such a release stalls once for 30-90 ms in its first iterations
 // (DESIGN.md section 6).  A caller that solves one problem size again and again -- the usual MATLAB session -- would pay
 // that on every call.  Freed buffers are therefore kept per device and handed out again to requests of (nearly) their
-// size; a reused buffer is zero-filled, as fresh device memory is; the cache holds at most half of the device's memory
-// (DOTSOCP_DEVICE_CACHE_GB), oldest blocks leave first.  DOTSOCP_DEVICE_CACHE=0 switches the cache off,
+// size; a reused buffer is zero-filled, as fresh device memory is (DOTSOCP_POISON=1: filled with POISON_WORD where it
+// holds floating-point numbers); the cache holds at most half of each device's memory (DOTSOCP_DEVICE_CACHE_GB, counted
+// per device), oldest blocks leave first.  DOTSOCP_DEVICE_CACHE=0 switches the cache off,
 // dotsocp_release_cache() returns everything to the driver, an allocation failure does so by itself and retries.
 namespace {
 
@@ -116,7 +143,7 @@ long long device_cache_release() {
     return bytes;
 }
 
-static int cached_malloc(void **p, size_t bytes) {
+static int cached_malloc(void **p, size_t bytes, bool poison) {
     int dev = 0;
     DS_HIP(hipGetDevice(&dev));
     Block got{nullptr, 0, dev};
@@ -136,7 +163,8 @@ static int cached_malloc(void **p, size_t bytes) {
     }
     if (got.p) {
         // like fresh device memory, a reused block reads as zeros (guarded_free made sure nothing is still using it)
-        hipError_t e = hipMemsetAsync(got.p, 0, got.bytes, nullptr);
+        // (poison: the fill below takes the memset's place)
+        hipError_t e = poison ? hipSuccess : hipMemsetAsync(got.p, 0, got.bytes, nullptr);
         if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
         if (e != hipSuccess) {
             (void)hipFree(got.p);
@@ -150,6 +178,14 @@ static int cached_malloc(void **p, size_t bytes) {
         }
         DS_HIP(e);
         got.bytes = bytes;
+    }
+    if (poison) {
+        hipError_t e = poison_fill(got.p, got.bytes) == 0 ? hipSuccess : hipErrorUnknown;
+        if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+        if (e != hipSuccess) {
+            (void)hipFree(got.p);
+            DS_HIP(e);
+        }
     }
     *p = got.p;
     std::lock_guard<std::mutex> lk(c_mu);
@@ -173,42 +209,71 @@ static void cached_free(void *p) {
     (void)hipGetDevice(&cur);
     if (cur != b.dev) (void)hipSetDevice(b.dev);
     const hipError_t e = hipDeviceSynchronize();
-    if (cur >= 0 && cur != b.dev) (void)hipSetDevice(cur);
+    // at most half of THIS device's memory (DOTSOCP_DEVICE_CACHE_GB: that many GB on every device) stays in the cache
+    static const double cap_gb = [] {
+        const char *g = getenv("DOTSOCP_DEVICE_CACHE_GB");
+        return g && atof(g) >= 0 ? atof(g) : -1.0;
+    }();
+    size_t cap = (size_t)(cap_gb * 1e9);
+    if (cap_gb < 0) {
+        static std::mutex cap_mu;
+        static std::map<int, size_t> caps;      // device -> half of its memory, asked once
+        std::lock_guard<std::mutex> lk(cap_mu);
+        auto it = caps.find(b.dev);
+        if (it == caps.end()) {
+            size_t fr = 0, tot = 0;
+            it = caps.emplace(b.dev, hipMemGetInfo(&fr, &tot) == hipSuccess ? tot / 2 : (size_t)64e9).first;
+        }
+        cap = it->second;
+    }
     if (e != hipSuccess) {
         (void)hipFree(b.p);
+        if (cur >= 0 && cur != b.dev) (void)hipSetDevice(cur);
         return;
     }
-    // at most half of the device's memory (DOTSOCP_DEVICE_CACHE_GB) stays in the cache: the oldest blocks go first
-    static const size_t cap = [] {
-        const char *g = getenv("DOTSOCP_DEVICE_CACHE_GB");
-        if (g && atof(g) >= 0) return (size_t)(atof(g) * 1e9);
-        size_t fr = 0, tot = 0;
-        return hipMemGetInfo(&fr, &tot) == hipSuccess ? tot / 2 : (size_t)64e9;
-    }();
+    // the blocks of one device are counted against that device's cap, and only they leave for it: the oldest first
     std::vector<Block> evict;
     {
         std::lock_guard<std::mutex> lk(c_mu);
         c_free.push_back(b);
         size_t held = 0;
-        for (auto &x : c_free) held += x.bytes;
-        while (held > cap && !c_free.empty()) {
-            held -= c_free.front().bytes;
-            evict.push_back(c_free.front());
-            c_free.erase(c_free.begin());
+        for (auto &x : c_free)
+            if (x.dev == b.dev) held += x.bytes;
+        for (size_t i = 0; held > cap && i < c_free.size();) {
+            if (c_free[i].dev != b.dev) { ++i; continue; }
+            held -= c_free[i].bytes;
+            evict.push_back(c_free[i]);
+            c_free.erase(c_free.begin() + (long)i);
         }
     }
-    for (auto &x : evict) {
-        if (x.dev != cur) (void)hipSetDevice(x.dev);
-        (void)hipFree(x.p);
-        if (cur >= 0 && x.dev != cur) (void)hipSetDevice(cur);
-    }
+    for (auto &x : evict) (void)hipFree(x.p);       // (all of b.dev, which is current)
+    if (cur >= 0 && cur != b.dev) (void)hipSetDevice(cur);
 }
 
-int guarded_malloc(void **p, size_t bytes) {
+// bytes the cache holds on device `dev` (all devices: dev < 0)
+long long device_cache_held(int dev) {
+    std::lock_guard<std::mutex> lk(c_mu);
+    long long bytes = 0;
+    for (auto &x : c_free)
+        if (dev < 0 || x.dev == dev) bytes += (long long)x.bytes;
+    return bytes;
+}
+
+int guarded_malloc(void **p, size_t bytes, bool fp) {
     *p = nullptr;
+    const bool poison = fp && poison_enabled();
     if (!canary_enabled()) {
-        if (cache_enabled()) return cached_malloc(p, bytes);
+        if (cache_enabled()) return cached_malloc(p, bytes, poison);
         DS_HIP(hipMalloc(p, bytes));
+        if (poison) {
+            hipError_t e = poison_fill(*p, bytes) == 0 ? hipSuccess : hipErrorUnknown;
+            if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+            if (e != hipSuccess) {
+                (void)hipFree(*p);
+                *p = nullptr;
+                DS_HIP(e);
+            }
+        }
         return 0;
     }
     const size_t padded = (bytes + 255) / 256 * 256;
@@ -217,11 +282,12 @@ int guarded_malloc(void **p, size_t bytes) {
     // the slack between the payload's end and the rear band is pattern too: an overrun by one element is seen
     const size_t head = GUARD / 8, tail = (padded - bytes + GUARD) / 8;
     (void)hipGetLastError();       // a stale error of an earlier, failed call must not be blamed on the fill launches
-    DS_KLAUNCH(k_fill_pattern, dim3(4), dim3(256), 0, nullptr, (unsigned long long *)base, head);
+    DS_KLAUNCH(k_fill_pattern, dim3(4), dim3(256), 0, nullptr, (unsigned long long *)base, head, PATTERN);
     // payload sizes are multiples of 8 (doubles, double2); the tail starts right behind the payload
     DS_KLAUNCH(k_fill_pattern, dim3(4), dim3(256), 0, nullptr, (unsigned long long *)(base + GUARD + bytes / 8 * 8),
-                       tail);
+                       tail, PATTERN);
     DS_HIP(hipGetLastError());
+    if (poison) DS_CHECK(poison_fill(base + GUARD, bytes));       // the payload between the bands
     DS_HIP(hipDeviceSynchronize());
     int dev = 0;
     (void)hipGetDevice(&dev);

@@ -204,10 +204,11 @@ struct ImageCall {
         return 0;
     }
     // n elements and a tail: uint8 kernels read whole 32-bit words, and the guard bands start on 8-byte boundaries
+    // (DOTSOCP_POISON=1 fills the buffers of doubles only: pixels are uploaded whole, tap indices and tile ranges are integers)
     template <class T> int alloc(T **p, i64 n) {
         const i64 bytes = ((i64)sizeof(T) * n + 4 + 7) / 8 * 8;
         unsigned char *raw = nullptr;
-        DS_CHECK(dmalloc(&raw, bytes));
+        DS_CHECK(dmalloc(&raw, bytes, is_fp_payload<T>::value));
         bufs.push_back(raw);
         *p = reinterpret_cast<T *>(raw);
         return 0;

@@ -32,7 +32,7 @@ struct LongScratch {
             if (b.p) retired.push_back(b.p);
             b.p = nullptr;
             b.bytes = 0;
-            DS_CHECK(guarded_malloc((void **)&b.p, bytes));
+            DS_CHECK(guarded_malloc((void **)&b.p, bytes, true));       // complex doubles
             b.bytes = bytes;
         }
         *out = b.p;

@@ -4,6 +4,7 @@
 #include <functional>
 #include <memory>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "hostmem.h"
@@ -16,10 +17,22 @@ namespace dotsocp {
 // out-of-bounds WRITE of a tile kernel on a partial tile changes a guard word, an out-of-bounds READ pulls NaNs
 // into the iterates.  Without the variable freed buffers are kept in a per-device cache and handed out again (guard.hip;
 // DOTSOCP_DEVICE_CACHE=0: plain hipMalloc / hipFree).
-int guarded_malloc(void **p, size_t bytes);
+//
+// DOTSOCP_POISON=1 (read per call; a switch for tests): a payload that holds floating-point numbers (`fp`) is handed out
+// filled with POISON_WORD, a quiet NaN, instead of the zeros that fresh or reused device memory usually shows -- a kernel
+// that reads a slot nothing has written yet then changes its results (tests/test_gpu_poison.py).  Payloads of integers
+// (indices, counters, flags) are never poisoned: a poisoned word read as an index would be a wild address.
+constexpr unsigned long long POISON_WORD = 0x7ff8bad0bad0bad0ull;
+int guarded_malloc(void **p, size_t bytes, bool fp = false);
 void guarded_free(void *p);
+bool poison_enabled();
+// fills a floating-point region of a buffer that was allocated unpoisoned because it also holds integers (no-op unless
+// DOTSOCP_POISON=1); synchronises like guarded_malloc
+int poison_region(void *p, size_t bytes);
 // the device block cache behind them (guard.hip): hipFree everything it holds; returns the bytes given back
 long long device_cache_release();
+// bytes the cache holds on device `dev` (dev < 0: on all devices)
+long long device_cache_held(int dev);
 // number of live buffers whose guard bands were overwritten (0 when the canaries are off); `report` receives a
 // description of the first few.  Synchronises the current device.
 int canary_check(std::string *report);
@@ -28,11 +41,14 @@ bool canary_enabled();
 bool stream_stress_enabled();
 void stream_stress(hipStream_t st);
 
+template <class T> struct is_fp_payload { static constexpr bool value = std::is_floating_point<T>::value; };
+template <> struct is_fp_payload<double2> { static constexpr bool value = true; };
+
 template <class T>
-inline int dmalloc(T **p, i64 n) {
+inline int dmalloc(T **p, i64 n, bool fp = is_fp_payload<T>::value) {
     *p = nullptr;
     if (n <= 0) n = 1;
-    return guarded_malloc((void **)p, sizeof(T) * (size_t)n);
+    return guarded_malloc((void **)p, sizeof(T) * (size_t)n, fp);
 }
 
 inline void dfree(void *p) {
@@ -444,7 +460,9 @@ struct DeviceScratch {
     Solver &S;
     std::vector<double *> bufs;
     explicit DeviceScratch(Solver &s) : S(s) {}
-    int alloc(double **p, i64 n) { DS_CHECK(dmalloc(p, n)); bufs.push_back(*p); return 0; }      // on the current device
+    // on the current device; fp = false: the buffer holds integer regions too and stays as it comes under DOTSOCP_POISON=1
+    // (the caller names its floating-point regions with poison_region())
+    int alloc(double **p, i64 n, bool fp = true) { DS_CHECK(dmalloc(p, n, fp)); bufs.push_back(*p); return 0; }
     ~DeviceScratch() {
         if (bufs.empty()) return;
         S.cur_dev = -1;

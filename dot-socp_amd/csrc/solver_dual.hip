@@ -29,12 +29,17 @@ int Solver::dual_bound(const double *rho0, const double *rho1, dotsocp_dual *res
     DS_CHECK(use(s0));
     // [phi0 | phi1 | T | H | B | rho0 | rho1 | ixf iyf ixb iyb arg_fwd arg_bwd (ints) | partials | sums | counters]
     double *buf = nullptr;
-    DS_CHECK(scratch.alloc(&buf, 7 * plane + 6 * iplane + HS_COUNT * blocks + HS_COUNT + HC_COUNT));
+    // not poisoned as a whole (DOTSOCP_POISON=1): the six planes of ints are indices.  The passes write ix / iy / arg at
+    // every y < ny of every column before k_hl_reduce reads them there, and nothing reads their pad entries; the counters
+    // are set to zero below.  The regions of doubles are poisoned by name.
+    DS_CHECK(scratch.alloc(&buf, 7 * plane + 6 * iplane + HS_COUNT * blocks + HS_COUNT + HC_COUNT, false));
     double *P0 = buf, *P1 = P0 + plane, *T = P1 + plane, *Hd = T + plane, *Bd = Hd + plane, *R0 = Bd + plane, *R1 = R0 + plane;
     int *ints[6];
     for (int k = 0; k < 6; ++k) ints[k] = (int *)(R1 + plane + iplane * k);
     double *partials = R1 + plane + 6 * iplane, *dsums = partials + HS_COUNT * blocks;
     unsigned long long *dcounts = (unsigned long long *)(dsums + HS_COUNT);
+    DS_CHECK(poison_region(buf, sizeof(double) * (size_t)(7 * plane)));
+    DS_CHECK(poison_region(partials, sizeof(double) * (size_t)(HS_COUNT * blocks + HS_COUNT)));
     hipStream_t st = s0.st;
     // (the pad entries of pitched rows stay as they come: the passes, the reduction and the row copies touch y < ny only)
     DS_HIP(ds_memset_async(dcounts, 0, sizeof(unsigned long long) * HC_COUNT, st));

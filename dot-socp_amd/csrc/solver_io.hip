@@ -209,7 +209,10 @@ int Solver::render_evolution(const double *rho0, const double *rho1, const dotso
     FOR_SLABS(s) {
         double *buf = nullptr;
         const i64 nimg = mine[k] * dbl(img_bytes);
-        DS_CHECK(scratch.alloc(&buf, off_img + nimg + mine[k] * (dim1 ? 1 : 2) * my * mx));
+        // (DOTSOCP_POISON=1: the counters in front are integers, set to zero below; everything behind them is poisoned --
+        // levels and arrows are doubles, mask, table and pictures are bytes that are read as values, never as indices)
+        DS_CHECK(scratch.alloc(&buf, off_img + nimg + mine[k] * (dim1 ? 1 : 2) * my * mx, false));
+        DS_CHECK(poison_region(buf + off_lev, sizeof(double) * (size_t)(off_img - off_lev + nimg + mine[k] * (dim1 ? 1 : 2) * my * mx)));
         DS_CHECK(stage_rho_ends(s, rho0, rho1));
         DS_HIP(ds_memset_async(buf, 0, sizeof(unsigned long long) * RR_COUNT, s.st));
         if (lev) DS_HIP(ds_memcpy_async(buf + off_lev, levels, sizeof(double) * (size_t)o->nlevels, hipMemcpyHostToDevice, s.st));

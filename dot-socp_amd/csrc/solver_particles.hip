@@ -162,11 +162,17 @@ struct March {
     template <class T = double> T *at(i64 off) const { return (T *)(block(cur) + off); }
     double *block(size_t k) const { return scratch.bufs[k]; }
     double *frame(size_t k) const { return scratch.bufs[S.slabs.size() + k]; }
-    int alloc_per_slab(i64 doubles) {
+    // Buffers with integer regions stay as they come under DOTSOCP_POISON=1; their regions of doubles [fp_off, + fp_len) and
+    // [fp_off2, + fp_len2) are poisoned by name.  The block: units, flags and count are integers -- seed() sets the whole
+    // block of the first slab to zero, hand_over() copies the whole block to the next.  The frame buffer: the deposit layer
+    // is 64-bit integers, set to zero by frame_at() before every deposit.
+    int alloc_per_slab(i64 doubles, i64 fp_off, i64 fp_len, i64 fp_off2 = 0, i64 fp_len2 = 0) {
         double *b;
         for (auto &s : S.slabs) {
             DS_CHECK(S.use(s));
-            DS_CHECK(scratch.alloc(&b, doubles));
+            DS_CHECK(scratch.alloc(&b, doubles, false));
+            if (fp_len > 0) DS_CHECK(poison_region(b + fp_off, sizeof(double) * (size_t)fp_len));
+            if (fp_len2 > 0) DS_CHECK(poison_region(b + fp_off2, sizeof(double) * (size_t)fp_len2));
         }
         return 0;
     }
@@ -175,8 +181,11 @@ struct March {
     int map_stage() {
         Slab &s = S.slabs[fin];
         DS_CHECK(S.use(s));
-        DS_CHECK(scratch.alloc(&final_buf, M.total));
+        // (DOTSOCP_POISON=1: the counters are integers, set to zero below; the doubles around them are poisoned by name)
+        DS_CHECK(scratch.alloc(&final_buf, M.total, false));
         double *b = final_buf;
+        DS_CHECK(poison_region(b, sizeof(double) * (size_t)M.counts));
+        DS_CHECK(poison_region(b + M.partials, sizeof(double) * (size_t)(M.total - M.partials)));
         report_edges_host(edges);
         if (!dim1) DS_HIP(ds_memcpy_async(b + M.seeds, x, nb, hipMemcpyHostToDevice, s.st));
         DS_HIP(ds_memcpy_async(b + M.seeds + n, y, nb, hipMemcpyHostToDevice, s.st));
@@ -325,8 +334,8 @@ struct March {
         fi = dir > 0 ? 0 : nf - 1;
         l1_host.resize((size_t)(nf * (i64)S.slabs.size()));
         owner.resize((size_t)nf);
-        DS_CHECK(alloc_per_slab(L.total));
-        if (kind == FRAMES) DS_CHECK(alloc_per_slab(plane + tiles + nf));
+        DS_CHECK(alloc_per_slab(L.total, L.px, L.units, L.sq, L.flags - L.sq));
+        if (kind == FRAMES) DS_CHECK(alloc_per_slab(plane + tiles + nf, plane, tiles + nf));
         if (kind == PATH_SUMS) DS_CHECK(map_stage());
         DS_CHECK(seed());
         for (i64 step = 0; step < S.nt - 1; ++step) DS_CHECK(interval(dir > 0 ? step : S.nt - 2 - step));

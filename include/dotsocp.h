@@ -721,6 +721,16 @@ int dotsocp_kernel_time(dotsocp_ctx *ctx, const char *name, double *avg_ms, dots
  * when the canaries are off) and sets dotsocp_last_error() accordingly.  An out-of-bounds READ shows up as NaNs. */
 int dotsocp_canary_check(void);
 
+/* Uninitialised-read poison (test switch): with DOTSOCP_POISON=1 in the environment (read per allocation) every device
+ * buffer of floating-point numbers is handed out filled with the quiet NaN 0x7ff8bad0bad0bad0 instead of the zeros that
+ * fresh or reused device memory usually shows; buffers of integers (indices, counters, flags) are left alone.  A kernel
+ * that reads a slot nothing has written then changes its results (tests/test_gpu_poison.py).
+ * dotsocp_debug_alloc_peek: test hook -- allocates n doubles as the library allocates its buffers, copies them to `out`
+ * as they were handed out, and frees them; no kernel of the library runs on them.
+ * dotsocp_debug_cache_held: test hook -- bytes the device block cache holds on `device` (device < 0: on all devices). */
+int dotsocp_debug_alloc_peek(dotsocp_i64 n, double *out);
+dotsocp_i64 dotsocp_debug_cache_held(int device);
+
 /* Test support: phi <- idctn(dctn(phi) ./ (D^2 * initialize_FFTkernel)) by the loop's own Poisson solve
  * (Solver::poisson_all, the function every iteration calls), on the slabs of the context as created: one slab, `nslabs`
  * on one device, dotsocp_create_multi, or an attached RCCL rank -- so the partitioned tridiagonal solve along t and the

@@ -16,7 +16,7 @@ from .examples import (SpaceWeight, ensure_barrier_validity, gene_barrier_of_cir
 from . import images  # noqa: F401
 from .images import (gene_barrier_of_example6, gene_barrier_of_maze14, gene_example5,  # noqa: F401
                      gene_example_DOTmark_4stitch, get_example_from_images, image_density, imread, imresize, rgb2gray)
-from .mexops import (mexBFd, mexBFd1d, mexBFdConj, mexBFdConj1d, mexProjSoc, mirt_dctn, mirt_idctn,  # noqa: F401
+from .mexops import (dct_axis, mexBFd, mexBFd1d, mexBFdConj, mexBFdConj1d, mexProjSoc, mirt_dctn, mirt_idctn,  # noqa: F401
                      oper_poisson, oper_poisson3dim)
 from .model import (InitialScaling, ModelHandle, VarHandle, check_massConservation, initialize,  # noqa: F401
                     initialize_slab, recover_q, recover_RhoE, recoverOrgVar)

@@ -117,6 +117,7 @@ SYMBOLS = {
     "dotsocp_bfd_conj1d": (ctypes.c_int, [vp, vp, i64, i64, dbl]),
     "dotsocp_oper_poisson": (ctypes.c_int, [vp, vp, i64, i64, i64, dbl]),
     "dotsocp_dctn": (ctypes.c_int, [vp, i64, i64, i64, ctypes.c_int]),
+    "dotsocp_dct_axis": (ctypes.c_int, [vp, i64, i64, i64, ctypes.c_int, ctypes.c_int]),
     "dotsocp_proj_soc_dev": (ctypes.c_int, [vp, vp, i64, i64, vp]),
     "dotsocp_bfd_dev": (ctypes.c_int, [vp, vp, i64, i64, i64, dbl, dbl, vp]),
     "dotsocp_bfd_conj_dev": (ctypes.c_int, [vp, vp, i64, i64, i64, dbl, vp]),

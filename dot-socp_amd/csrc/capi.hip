@@ -210,6 +210,28 @@ int dotsocp_dctn(double *a, dotsocp_i64 ny, dotsocp_i64 nx, dotsocp_i64 nt, int 
     return 0;
 }
 
+// Test support: the one pass of dotsocp_dctn along `axis` -- its length checks, its plan for that length, its source
+// and destination buffers (dctn_dev: y and t go a -> b, x goes b -> a, in both directions).
+int dotsocp_dct_axis(double *a, dotsocp_i64 ny, dotsocp_i64 nx, dotsocp_i64 nt, int axis, int inverse) {
+    DS_ARG(a && ny >= 1 && nx >= 1 && nt >= 1, "bad array");
+    DS_ARG(axis >= 0 && axis <= 2, "axis must be 0 (y), 1 (x) or 2 (t)");
+    DS_CHECK(dct_length_check(ny)); DS_CHECK(dct_length_check(nx)); DS_CHECK(dct_length_check(nt));
+    DS_CHECK(require_device());
+    const i64 n = ny * nx * nt;
+    DevBuf da, db;
+    Plans pl;
+    DS_CHECK(da.alloc(n));
+    DS_CHECK(db.alloc(n));
+    DS_CHECK(pl.make(ny, nx, nt));
+    DctPlan *plan = axis == 0 ? pl.py : axis == 1 ? pl.px : pl.pt;
+    double *src = axis == 1 ? db.p : da.p, *dst = axis == 1 ? da.p : db.p;
+    DS_HIP(hipMemcpy(src, a, sizeof(double) * n, hipMemcpyHostToDevice));
+    DS_CHECK(launch_dct_axis(plan, src, dst, ny, nx, nt, axis, inverse ? 1 : 0, nullptr));
+    DS_HIP(hipDeviceSynchronize());
+    DS_HIP(hipMemcpy(a, dst, sizeof(double) * n, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 int dotsocp_oper_poisson(double *res, const double *rhs, dotsocp_i64 ny, dotsocp_i64 nx, dotsocp_i64 nt,
                          double kernelScale) {
     DS_ARG(res && rhs && ny >= 1 && nx >= 1 && nt >= 1, "bad array");

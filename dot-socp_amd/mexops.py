@@ -91,6 +91,16 @@ def mirt_idctn(a):
     return out
 
 
+def dct_axis(a, axis, inverse=False):
+    """Test support (dotsocp_dct_axis): the orthonormal DCT-II (DCT-III with inverse=True) along ONE axis of `a`, the
+    pass mirt_dctn / mirt_idctn makes along that axis and nothing else; returns a new array.  `axis` counts the axes of
+    the three-dimensional (ny, nx, nt) view of `a` (a 2-D array is a 1-D problem: (nx1d, 1, nt))."""
+    out = np.array(a, dtype=np.float64, order="F", copy=True)
+    ny, nx, nt = _dims3(out)
+    capi.check(capi.lib().dotsocp_dct_axis(capi.fptr(out), ny, nx, nt, int(axis), int(bool(inverse))))
+    return out
+
+
 def oper_poisson3dim(kernelScale, rhs):
     """res = oper_poisson3dim(kernelScale * initialize_FFTkernel(nt,nx,ny), rhs)
     (socp/dot2d/utils/oper_poisson3dim.m:4; 1-D: socp/dot1d/utils/oper_poisson.m:4 with a 2-D rhs).

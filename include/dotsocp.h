@@ -97,6 +97,12 @@ int dotsocp_oper_poisson(double *res, const double *rhs, dotsocp_i64 ny, dotsocp
  *    2^19 - 1 (dotsocp_cdft_levels); longer: DOTSOCP_EINVAL. */
 int dotsocp_dctn(double *a, dotsocp_i64 ny, dotsocp_i64 nx, dotsocp_i64 nt, int inverse);
 
+/* Test support: a <- the DCT-II (inverse = 0) or DCT-III (inverse = 1) of a along ONE axis (0: y, 1: x, 2: t), the other
+ * two axes untouched -- exactly the pass dotsocp_dctn makes along that axis: the same length checks, the same plan for
+ * the length, the same source and destination buffers.  Different lines of the axis can so carry different data with a
+ * known result (tests/test_gpu_dct_probes.py).  Not a reference operator. */
+int dotsocp_dct_axis(double *a, dotsocp_i64 ny, dotsocp_i64 nx, dotsocp_i64 nt, int axis, int inverse);
+
 /* Same operators on DEVICE pointers (no PCIe traffic), enqueued on `stream`
  * (a hipStream_t, NULL = default stream).  Used by the parity tests and by bench.py. */
 int dotsocp_proj_soc_dev(double *d_out, const double *d_in, dotsocp_i64 M, dotsocp_i64 K, void *stream);

@@ -7,9 +7,10 @@ of the SOLUTION is O(1); the device result is projected back onto u_ky (x) v_kx 
 other modes are orthogonal and drop out) and compared, per mode, with the literal definition of the operation along t,
     x_j = C' diag(1 / (D^2 (CY[ky] + CX[kx] + CT))) C g_j       (C: the nt x nt orthonormal DCT-II matrix, long double,
                                                                   the zero eigenvalue replaced by 1: initialize_FFTkernel)
-which shares nothing with the tridiagonal algebra of tri.hip.  Modes whose amplitudes differ by more than a factor of 16
-go into separate solves: otherwise the rounding of the y / x transforms of the large components leaks into the small ones,
-which is the conditioning of the problem and not the kernel's doing.
+which shares nothing with the tridiagonal algebra of tri.hip.  CY and CX are the float64 tables of initialize_FFTkernel
+taken to long double (_eig_table: the numbers the operator divides by), CT the eigenvalues along t in long double.  Modes
+whose amplitudes differ by more than a factor of 16 go into separate solves: otherwise the rounding of the y / x transforms
+of the large components leaks into the small ones, which is the conditioning of the problem and not the kernel's doing.
 
 Bound per mode: 1e-12 max(1, 1e-2 / a'), a' = (CY[ky] + CX[kx]) / (nt-1)^2; 1e-12 for the singular (0, 0) mode.  It comes
 from the CPU model of the partitioned solve (tests/test_tri_closed_form.py) against the same long-double reference: <= 3e-14
@@ -34,6 +35,15 @@ zero-mode recurrence at nt = 512.  The shapes are the smallest grids that reach 
                     (34 / 33 / 33 / 33: n == R on wave 0 only), 200 <32, 8>, 270 <34, 8>, 500 <64, 8>
   19 (514, 3, 200)  ONE slab, small but legal powers: a' up to 27, rho^24 = 1e-35
   20 (2048, 1, 505) 1-D, ONE slab: pieces of 64 / 63 rows, rho^63 = 4e-116, dotsocp_tsolve_tri_safe = 1
+  21 .. 29 ONE slab, nt = 12 (k_tsolve_single<8, 2> along t): the y / x transforms of the other DCT families under the
+                    pitched rows of a context (py = ny rounded up to 16 doubles), every output bin paired with its
+                    eigenvalue at the highest modes: along y 21 (257, 5, 12) Rader, 22 (1000, 3, 12) Bluestein inside the
+                    LDS, 23 (1025, 3, 12) prime-factor, 24 (96, 5, 12) dense product, 25 (4096, 1, 12) 1-D, the two-level
+                    power of two, 26 (4101, 1, 12) 1-D, the two-level Bluestein; along x 27 (6, 257, 12), 28 (6, 1000, 12),
+                    29 (6, 1025, 12)
+  30 (66, 5, 64)    a power of two along t that k_tsolve_pipe does not take (it starts above 64 nodes): the fused transform
+                    pass along t (k_dct_strided<2, true>: DCT-II, division, DCT-III in one kernel, rows 80 doubles apart)
+  31 (66, 5, 33)    with DOTSOCP_TSOLVE=dct only: the fused prime-factor pass along t (k_pfa_strided<., 2, .>)
 The CPU model on the pieces of shapes 10 .. 20 (the left interface as xl N_0 rho^t, the power walked up from rho^(n-1)) stays
 below 1e-2 of the bound at every probed mode.
 
@@ -58,11 +68,14 @@ SHAPES = {1: ((130, 9, 40), 2), 2: ((66, 10, 80), 2), 3: ((66, 10, 140), 2), 4: 
           6: ((2048, 1, 512), 1), 7: ((2048, 4, 340), 2), 8: ((2048, 4, 262), 2), 9: ((3, 4096, 505), 2),
           10: ((66, 5, 5), 2), 11: ((66, 5, 12), 2), 12: ((66, 5, 23), 2), 13: ((66, 5, 49), 2), 14: ((66, 5, 100), 2),
           15: ((66, 5, 133), 2), 16: ((66, 5, 200), 2), 17: ((66, 5, 270), 2), 18: ((66, 5, 500), 2),
-          19: ((514, 3, 200), 2), 20: ((2048, 1, 505), 1)}
+          19: ((514, 3, 200), 2), 20: ((2048, 1, 505), 1),
+          21: ((257, 5, 12), 2), 22: ((1000, 3, 12), 2), 23: ((1025, 3, 12), 2), 24: ((96, 5, 12), 2), 25: ((4096, 1, 12), 1),
+          26: ((4101, 1, 12), 1), 27: ((6, 257, 12), 2), 28: ((6, 1000, 12), 2), 29: ((6, 1025, 12), 2), 30: ((66, 5, 64), 2),
+          31: ((66, 5, 33), 2)}
 LAYOUTS = [(1, dict(nslabs=1)), (1, dict(nslabs=2)), (1, dict(nslabs=3)), (1, dict(nslabs=12)), (1, dict(nslabs=20)),
            (1, dict(ngpu=2)), (2, dict(nslabs=2)), (3, dict(nslabs=2)), (4, dict(nslabs=1)), (4, dict(nslabs=2)),
            (4, dict(nslabs=4)), (5, dict(nslabs=2)), (6, dict(nslabs=2)), (6, dict(nslabs=4)), (7, dict(nslabs=2)),
-           (8, dict(nslabs=2)), (9, dict(nslabs=1))] + [(no, dict(nslabs=1)) for no in range(10, 21)]
+           (8, dict(nslabs=2)), (9, dict(nslabs=1))] + [(no, dict(nslabs=1)) for no in range(10, 31)]
 
 
 def _id(case):
@@ -81,6 +94,15 @@ def _eig(n):
     return 2 * LD(n - 1) ** 2 * (1 - np.cos(PI * np.arange(n, dtype=LD) / n))
 
 
+def _eig_table(n):
+    """the same eigenvalues as the operator holds them: the float64 table of initialize_FFTkernel.m:6-8, which the
+    reference and the device alike evaluate as 2 (n-1)^2 (1 - cos(pi k / n)) in doubles.  They are the operator's data
+    along y and x -- the t solve divides by these numbers -- and 1 - cos cancels at the low modes of a long axis: at
+    n = 4096 the entry k = 1 is good to 3e-11 only, which a solution at nt = 12 shows in full (1.6e-11 at (1, 0) against
+    the eigenvalues in long double, on the device and in numpy alike)"""
+    return ((2.0 * (n - 1) ** 2) * (1.0 - np.cos(np.pi * np.arange(n) / n))).astype(LD)
+
+
 def _modes(ny, nx):
     kys = sorted({0, 1, 2, ny // 8, ny // 2, ny - 2, ny - 1} & set(range(ny)))
     kxs = sorted({0, 1, nx - 1} & set(range(nx)))
@@ -94,7 +116,7 @@ def _probe(shape_no):
     (ny, nx, nt), _ = SHAPES[shape_no]
     rng = np.random.default_rng(1000 + shape_no)
     C = np.stack([_basis(nt, k) for k in range(nt)])            # C[k, t]
-    cy, cx, ct = _eig(ny), _eig(nx), _eig(nt)
+    cy, cx, ct = _eig_table(ny), _eig_table(nx), _eig(nt)
     modes = []
     for ky, kx in _modes(ny, nx):
         g = rng.standard_normal(nt).astype(LD)
@@ -173,9 +195,11 @@ def test_modes_on_slabs(case):
 
 
 @gpu
-@pytest.mark.parametrize("case", [(1, dict(nslabs=2)), (1, dict(nslabs=3)), (3, dict(nslabs=2))], ids=_id)
+@pytest.mark.parametrize("case", [(1, dict(nslabs=2)), (1, dict(nslabs=3)), (3, dict(nslabs=2)), (31, dict(nslabs=1))],
+                         ids=_id)
 def test_modes_through_the_transposes(case, monkeypatch):
-    """DOTSOCP_TSOLVE=dct: the slab <-> pencil transposes around the t-axis transform, same probes, same bounds"""
+    """DOTSOCP_TSOLVE=dct: the slab <-> pencil transposes around the t-axis transform, same probes, same bounds; on one
+    slab (shape 31) the fused transform pass along t instead of the tridiagonal kernel"""
     monkeypatch.setenv("DOTSOCP_TSOLVE", "dct")
     shape_no, kw = case
     _check(_id(case) + "-dct", _errors(shape_no, kw))

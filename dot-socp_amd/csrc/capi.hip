@@ -324,16 +324,16 @@ int dotsocp_cdft_levels(dotsocp_i64 n) { return cdft_levels(n); }
 int dotsocp_tsolve_tri_safe(dotsocp_i64 ny, dotsocp_i64 nx, dotsocp_i64 nt) { return tsolve_tri_safe(ny, nx, nt) ? 1 : 0; }
 
 int dotsocp_cone_writes_beta(dotsocp_i64 it, double last_sigma_it, dotsocp_i64 maxit, int check_step_by_step,
-                             int last_of_run, int rescale, double maxFeas, double relGap) {
-    return cone_writes_beta(it, last_sigma_it, maxit, check_step_by_step != 0, last_of_run != 0, rescale, maxFeas, relGap) ? 1 : 0;
+                             int ends_run, int rescale, double maxFeas, double relGap) {
+    return cone_writes_beta(SchedState{it, maxit, last_sigma_it, check_step_by_step != 0, rescale, maxFeas, relGap, ends_run ? 1 : -1}) ? 1 : 0;
 }
 int dotsocp_rescale_due(dotsocp_i64 it, int rescale, double maxFeas, double relGap) {
     return rescale_due(it, rescale, maxFeas, relGap) ? 1 : 0;
 }
-int dotsocp_qcone_form(dotsocp_i64 it, double last_sigma_it, dotsocp_i64 maxit, int check_step_by_step, int last_of_run,
-                       int next_last_of_run, int rescale, double maxFeas, double relGap) {
-    return qcone_form(it, last_sigma_it, maxit, check_step_by_step != 0, last_of_run != 0, next_last_of_run != 0, rescale,
-                      maxFeas, relGap);
+int dotsocp_qcone_form(dotsocp_i64 it, double last_sigma_it, dotsocp_i64 maxit, int check_step_by_step, int ends_run,
+                       int next_ends_run, int rescale, double maxFeas, double relGap) {
+    const long long run_left = ends_run ? 1 : (next_ends_run ? 2 : -1);
+    return qcone_form(SchedState{it, maxit, last_sigma_it, check_step_by_step != 0, rescale, maxFeas, relGap, run_left});
 }
 
 dotsocp_i64 dotsocp_field_len(const dotsocp_problem *p, int field) {

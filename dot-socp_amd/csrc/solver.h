@@ -5,10 +5,12 @@
 #include <memory>
 #include <string>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "hostmem.h"
 #include "kernels.h"
+#include "schedule.h"
 
 namespace dotsocp {
 
@@ -122,6 +124,17 @@ struct Slab {
     double *send_pbx = nullptr, *send_pby = nullptr, *ptail_bx = nullptr, *ptail_by = nullptr;
     double *alpha2 = nullptr;   // ping-pong partner of alpha (q-step that also forms the next rhs)
     double *sx2 = nullptr, *sy2 = nullptr;   // ping-pong partners of sx / sy (the early cone pass; allocated at its first use)
+    // Behind k_qcone, which wrote alpha^{k+1} to alpha2, q^{k+1} to q_old (exit form; the steady form stores none), the new
+    // sums to q / sx2 / sy2 and the multipliers to beta2: q holds q^{k+1}, q2 / sx / sy the new sums, and q_old the old
+    // sums -- a dead buffer, as the next q-step expects
+    void rotate_after_qcone() {
+        std::swap(alpha, alpha2);
+        double *const sums = q;
+        q = q_old; q_old = q2; q2 = sums;
+        std::swap(sx, sx2);
+        std::swap(sy, sy2);
+        std::swap(beta, beta2);
+    }
     // partitioned tridiagonal t-solve (tri.hip): messages to / from the owners of the modes, zero-mode work line
     double *tri_send = nullptr, *tri_recv = nullptr, *tri_bsend = nullptr, *tri_brecv = nullptr, *tri_zero = nullptr;
     double *carry = nullptr;    // 4 layer planes: hand-off between the chunk launches of a cone pass (FusedArgs::carry_in / _out)
@@ -147,29 +160,9 @@ struct Slab {
 int dotsocp_slab_range_impl(i64 nt, int world, int rank, i64 *t0, i64 *t1);
 void pencil_range(i64 plane, int world, int j, i64 *l0, i64 *l1);
 
-bool if_adjust_sigma(double iter, double last_iter);   // IfAdjustSigma (solver_socp_inPALM.m:361-379)
-
 enum Phase { PH_RHS = 0, PH_POISSON, PH_PROJ, PH_QSTEP, PH_BETA, PH_KKT, PH_FUSED_A, PH_FUSED_B, PH_MATERIALISE,
              PH_COMM, PH_INTERP, PH_ACC_CONE, PH_ACC_GATHER, PH_QSTEP0, PH_TRANSPOSE, PH_CONE_CARRY, PH_QCONE, PH_VELOCITY, PH_ADVECT,
              PH_DEPOSIT, PH_FRAME_L1, PH_ADVECT_PATH, PH_MAP_FINAL, PH_HL_PASS_X, PH_HL_PASS_Y, PH_HL_REDUCE, PH_COUNT };
-
-// The schedule of the gamma form (fused.hip, Solver::step): pure host arithmetic, also behind the C ABI.
-// rescale_due: the rescale block of iteration `it` takes its norms or rescales (solver_socp_inPALM.m:138-151), given the
-// state it finds -- it reads beta.
-bool rescale_due(i64 it, int rescale, double maxFeas, double relGap);
-// The cone pass of iteration `it` must leave beta (not gamma) behind: the iteration ends in a KKT check, ends the run()
-// call, or the next iteration's rescale block reads beta.  (maxFeas / relGap change at KKT checks only, so the present
-// values are the ones iteration it + 1 will see whenever this iteration has no check.)
-bool cone_writes_beta(i64 it, double lastSigmaIt, i64 maxit, bool checkStepByStep, bool last_of_run, int rescale,
-                      double maxFeas, double relGap);
-
-// The early cone pass (solver.h: Solver::qcone): the q-step of iteration `it` also runs the cone pass of iteration it + 1.
-// QCONE_NONE: the pass of `it` writes beta (cone_writes_beta), so a reader of beta or q follows it; else the form of the
-// early pass is the schedule of it + 1: QCONE_EXIT if that pass must leave beta (and q in memory), QCONE_STEADY if it
-// leaves gamma.  All inputs change at KKT checks only, and `it` has none.  next_last_of_run: it + 1 ends its run() call.
-enum { QCONE_NONE = 0, QCONE_STEADY = 1, QCONE_EXIT = 2 };
-int qcone_form(i64 it, double lastSigmaIt, i64 maxit, bool checkStepByStep, bool last_of_run, bool next_last_of_run,
-               int rescale, double maxFeas, double relGap);
 
 struct Solver {
     // ================ devices, streams, slabs: solver_slabs.hip ================
@@ -352,24 +345,23 @@ struct Solver {
     // The gamma form.  Between two plain iterations the cone pass stores gamma^k = beta^k + tau z^{k+1} where it would
     // store beta^k; the next pass forms beta^{k+1} = gamma^k - tau (BF q^{k+1} + d) from the q it reads anyway -- no q_old,
     // no second projection.  Every other reader of beta or z needs the beta form: an iteration known (at its start) to be
-    // followed by one writes beta (cone_writes_beta).
+    // followed by one writes beta (schedule.h: cone_writes_beta; plan_step decides it as StepPlan::pass_gout).
     bool cone_carry = true;      // DOTSOCP_CONE_CARRY=0: every deferred pass reads and writes beta
     bool beta_gamma = false;     // s.beta holds gamma (deferred only)
-    bool cone_gout = false;      // this iteration's pass writes gamma (set by step())
-    bool last_of_run = false;    // this iteration is the last of its run() call (set by run())
+    i64 run_left = -1;           // iterations the current run() call still has, counting this one (set by run(); negative: no bound)
     // The early cone pass.  A gamma-reading pass needs q^{k+1} and gamma^k only -- not phi -- so the q-step of an iteration
     // whose own pass left gamma runs the NEXT iteration's pass in the same kernel, on the q it holds in registers
-    // (qstep_march.hip: k_qcone; one slab, inPALM / ALG2, unweighted).  The bookkeeping of that pass is done where the launch is
-    // issued (phase_q); phase_z of the next iteration launches nothing and checks that step() schedules what was predicted.
+    // (qstep_march.hip: k_qcone; one slab, inPALM / ALG2, unweighted).  plan_step names the form (StepPlan::qcone_candidate),
+    // step() drops it if the time limit has passed, and the bookkeeping of that pass is done where the launch is issued
+    // (phase_q).  The form is handed to the next iteration's plan, which schedules no launch and reports a form that
+    // contradicts its own schedule (StepPlan::error).
     // After the steady form q^{k+1} is not in memory (q_valid): by the schedule every reader of q follows an exit form.
     int qcone = -1;              // DOTSOCP_QCONE: 0 never, 1 wherever eligible, 2 as 1 with the two kernels back to back
                                  // (the schedule alone); unset (-1): on grids of at least 2048 tiles
     bool q_valid = true;         // s.q holds q of the last q-step
-    bool early_pass = false;     // the cone pass of the NEXT iteration has run ...
-    bool early_gout = false;     // ... and has written gamma
-    bool next_last_of_run = false;   // the next iteration is the last of this run() call (set by run())
+    int early_pass = QCONE_NONE; // the form in which the cone pass of the NEXT iteration has run
+    StepIn step_in() const;      // the facts plan_step() decides this iteration from (schedule.h)
     int need_q(const char *who) const;
-    int qcone_decide() const;    // QCONE_* for this iteration's q-step, after its phase_z
     bool time_limit_passed() const;
     i64 timeout_at = -1;         // DOTSOCP_TEST_TIMEOUT_AT (test hook): the time limit counts as passed from this iteration on
     bool timeout_pending = false;   // the time limit passed in an iteration that wrote gamma: the next one checks and stops
@@ -404,9 +396,10 @@ struct Solver {
     int poisson_phi();               // test support: poisson_all() on the phi field, before begin()
     int phase_phi(const PhiHooks *hooks = nullptr);
     // part 0: all chunks; 1: all but the last chunk; 2: the last chunk (the only one that reads the q halo)
-    int phase_z(int part = 0);
-    // part 0: whole q-step; 1: all chunks but the last; 2: the last chunk (the one that reads the phi halo), then finish
-    int phase_q(int part = 0, bool kkt = false, int early = QCONE_NONE);
+    int phase_z(const StepPlan &plan, int part);
+    // part 0: whole q-step; 1: all chunks but the last; 2: the last chunk (the one that reads the phi halo), then finish;
+    // early: the QCONE_* form of the next iteration's cone pass that rides along
+    int phase_q(const StepPlan &plan, int part, int early = QCONE_NONE);
     int phase_mult();
     int materialise();
     int ensure_z();

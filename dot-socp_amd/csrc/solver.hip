@@ -178,12 +178,9 @@ int Solver::begin(const dotsocp_opts *o) {
     if (const char *e = getenv("DOTSOCP_QCONE")) qcone = atoi(e);
     if (qcone < -1 || qcone > 2) qcone = -1;
     q_valid = true;
-    early_pass = false;
-    early_gout = false;
-    next_last_of_run = false;
+    early_pass = QCONE_NONE;
     beta_gamma = false;
-    cone_gout = false;
-    last_of_run = false;
+    run_left = -1;
     timeout_pending = false;
     checkPrimDualFeas = (o->checkPrimDualFeas < 0) ? !prob.weighted : (o->checkPrimDualFeas != 0);   // :20-24 / wsocp :25-29
     time_limit = (o->time_limit > 0) ? o->time_limit : 3600.0;                                        // :26-30
@@ -321,21 +318,18 @@ int Solver::phase_phi(const PhiHooks *hooks) {
     return 0;                        // the phi head travels with the adjoint tails (ship_tails)
 }
 
+// part 0 / 1 / 2 of a launch in C chunks (phase_z, phase_q): all of them, all but the last, the last
+static void part_chunks(int part, i64 C, i64 *z0, i64 *zc) {
+    *z0 = (part == 2) ? C - 1 : 0;
+    *zc = (part == 0) ? C : ((part == 1) ? C - 1 : 1);
+}
+
 // The cone pass needs q^k and beta only -- not phi^{k+1}.  Time slabs: it runs in chunks of time cells, one launch per
 // chunk in ascending order (the "t + 1" cone entries of a chunk's last cell travel to the next launch through s.carry),
 // and only the last chunk reads the q halo -- step() puts the others in front of the halo's arrival (part 1) and the
-// last one beside the first interface exchange of the Poisson solve (part 2).
-int Solver::phase_z(int part) {
-    if (early_pass) {
-        // this iteration's pass ran inside the last q-step (phase_q), which also did its bookkeeping
-        early_pass = false;
-        if (part != 0 || !fused || !deferred || cone_gout != early_gout) {
-            set_error("internal: the early cone pass wrote %s, the schedule asks for %s", early_gout ? "gamma" : "beta",
-                      cone_gout ? "gamma" : "beta");
-            return DOTSOCP_ESTATE;
-        }
-        return 0;
-    }
+// last one beside the first interface exchange of the Poisson solve (part 2).  A pass that ran inside the last q-step
+// (StepPlan::cone_launch is false) is not launched again: step() does not call this.
+int Solver::phase_z(const StepPlan &plan, int part) {
     DS_CHECK(need_q("phase_z"));
     if (part != 1) DS_CHECK(ensure_halo());     // the last chunk reads the q halo (part 1 never does)
     if (!fused) {
@@ -344,9 +338,9 @@ int Solver::phase_z(int part) {
         prof_end(PH_PROJ);
         return 0;
     }
-    // flavour of the deferred pass (kernels.h): reads gamma if the last pass left it, writes what step() scheduled.  The
+    // flavour of the deferred pass (kernels.h): reads gamma if the last pass left it, writes what the plan scheduled.  The
     // passes that do not read q_old move fewer bytes and are timed as a phase of their own.
-    const bool gin = beta_gamma, gout = deferred && cone_gout;
+    const bool gin = beta_gamma, gout = plan.pass_gout;
     if (gin && (!deferred || !bops.empty())) {
         set_error("internal: gamma form %s", deferred ? "with a pending scaling of beta" : "without a pending multiplier step");
         return DOTSOCP_ESTATE;
@@ -365,8 +359,8 @@ int Solver::phase_z(int part) {
         a.beta_in = s.beta;
         a.bops = bops;
         const i64 C = s.fg.chunks;
-        const i64 z0 = (part == 2) ? C - 1 : 0;
-        const i64 zc = (part == 0) ? C : ((part == 1) ? C - 1 : 1);
+        i64 z0, zc;
+        part_chunks(part, C, &z0, &zc);
         if (deferred) {
             // beta^k = beta^{k-1} + tau (z^k - BF q^k - d) folded into this iteration's projection
             a.q_old = s.q_old;
@@ -402,8 +396,9 @@ KktCoef Solver::kkt_coef() const {
     return k;
 }
 
-// kkt: the iteration ends with a KKT check and the q-step runs in its KKT variant (one slab: part == 0)
-int Solver::phase_q(int part, bool kkt, int early) {
+// plan.fold: the iteration ends with a KKT check and the q-step runs in its KKT variant
+int Solver::phase_q(const StepPlan &plan, int part, int early) {
+    const bool kkt = plan.fold;
     if (!fused) DS_CHECK(flush_alpha());
     if (early != QCONE_NONE && (part != 0 || kkt || multi() || !fused || !deferred || !beta_gamma || !bops.empty())) {
         set_error("internal: early cone pass in a state it does not serve");
@@ -429,21 +424,14 @@ int Solver::phase_q(int part, bool kkt, int early) {
             a.ap_on = aops.n; a.ap_mul = aops.mul; a.ap_div = aops.div;
             a.c_ends = (c_ends_on && s.c_ends) ? 1 : 0;
             DS_CHECK(launch_qcone(s.g, lc, s.fg, a, egout, st));
-            std::swap(s.alpha, s.alpha2);
-            std::swap(s.q, s.q_old);          // s.q: q^{k+1} (steady form: not stored), s.q_old: the new sums
-            std::swap(s.q2, s.q_old);         // s.q2: the new sums, s.q_old: a dead buffer, as the next q-step expects
-            std::swap(s.sx, s.sx2);
-            std::swap(s.sy, s.sy2);
-            std::swap(s.beta, s.beta2);
+            s.rotate_after_qcone();
         } else if (!fused) {
             DS_CHECK(launch_qstep(s.g, lc, s.phi, s.z, s.beta, s.weight, s.tail_bx, s.tail_by, s.q, s.alpha, s.st));
         } else {
             // q^{k+1} goes to the buffer that held q^{k-1}; q^k is kept for the deferred beta update
             // ... and the right-hand side of the next phi-step is formed in the same pass (alpha ping-pongs)
-            const i64 C = qstep_rhs_chunks(s.g, s.fg);
-            i64 z0 = 0, zc = C, zs = 1;
-            if (part == 1) { zc = C - 1; }                     // all but the last chunk
-            else if (part == 2) { z0 = C - 1; zc = 1; }        // the last chunk
+            i64 z0, zc;
+            part_chunks(part, qstep_rhs_chunks(s.g, s.fg), &z0, &zc);
             QStepExtra ex{};
             ex.aops = aops;
             ex.c_ends = (c_ends_on && s.c_ends) ? 1 : 0;
@@ -455,7 +443,7 @@ int Solver::phase_q(int part, bool kkt, int early) {
                 ex.kappa = k.kappa; ex.dsD = k.dsD;
             }
             DS_CHECK(launch_qstep_rhs(s.g, lc, s.fg, s.phi, s.q2, s.sx, s.sy, s.weight, s.tail_bx, s.tail_by, s.c,
-                                      s.q_old, s.alpha, s.alpha2, s.w0, st, z0, zc, zs, &ex));
+                                      s.q_old, s.alpha, s.alpha2, s.w0, st, z0, zc, 1, &ex));
             if (part != 1) std::swap(s.alpha, s.alpha2);
             if (part != 1) std::swap(s.q, s.q_old);
             if (early != QCONE_NONE) {
@@ -473,14 +461,13 @@ int Solver::phase_q(int part, bool kkt, int early) {
     if (part == 1) return 0;
     q_valid = true;
     if (early != QCONE_NONE) {
-        // the bookkeeping of the next iteration's cone pass (phase_z)
+        // the bookkeeping of the next iteration's cone pass, which its plan will not launch
         q_valid = !egout || qcone == 2;
         beta_gamma = egout;
         z_valid = false;
         z_prev_ok = false;
-        early_pass = true;
-        early_gout = egout;
     }
+    early_pass = early;
     u0_made = multi() && fused;
     if (fused) aops.clear();                 // the q-step wrote the scaled alpha into the ping-pong partner
     rhs_valid = fused;
@@ -695,14 +682,12 @@ int Solver::rescale_block() {
         return 0;
     };
     if (rescale_due(it, rescale, maxFeas, relGap)) DS_CHECK(need_beta_form("rescale_block"));
-    if (rescale >= 3 && (it % 100) == 0) {
+    if (norm_check_due(it, rescale)) {
         DS_CHECK(norms(normPhis, normAlps));
         const double ratio = std::max(normAlps, normPhis) / std::min(normAlps, normPhis);
         if (ratio > 1.2) scaleYes = true;
     }
-    const bool first = (rescale == 1) && (maxFeas < 2e-2) && (it >= 10) && (relGap < 5e-2);
-    const bool second = (rescale == 2) && (maxFeas < 5e-3) && (it >= 50) && (relGap < 1e-2);
-    if (!(first || second || scaleYes)) return 0;
+    if (!(rescale_trigger(it, rescale, maxFeas, relGap) || scaleYes)) return 0;
     if (!scaleYes) DS_CHECK(norms(normPhis, normAlps));
     // A multiplier step that is still pending belongs to the OLD scaling (z^k = Pi(BF q^{k-1} + d - beta^{k-1}) with the old
     // d and the unscaled q, beta): it is executed before anything is rescaled.  (Right after a KKT check nothing is
@@ -725,55 +710,31 @@ int Solver::rescale_block() {
     return 0;
 }
 
-bool rescale_due(i64 it, int rescale, double maxFeas, double relGap) {
-    if (rescale >= 3 && (it % 100) == 0) return true;                                   // :139-146, the norm check
-    if (rescale == 1 && maxFeas < 2e-2 && it >= 10 && relGap < 5e-2) return true;       // :148
-    if (rescale == 2 && maxFeas < 5e-3 && it >= 50 && relGap < 1e-2) return true;       // :149
-    return false;
-}
-
-bool cone_writes_beta(i64 it, double lastSigmaIt, i64 maxit, bool checkStepByStep, bool last_of_run, int rescale,
-                      double maxFeas, double relGap) {
-    if (checkStepByStep || if_adjust_sigma((double)it, lastSigmaIt) || it >= maxit) return true;   // ends in a KKT check
-    if (last_of_run) return true;                                                                  // the caller may read anything
-    return rescale_due(it + 1, rescale, maxFeas, relGap);
-}
-
-int qcone_form(i64 it, double lastSigmaIt, i64 maxit, bool checkStepByStep, bool last_of_run, bool next_last_of_run,
-               int rescale, double maxFeas, double relGap) {
-    if (cone_writes_beta(it, lastSigmaIt, maxit, checkStepByStep, last_of_run, rescale, maxFeas, relGap)) return QCONE_NONE;
-    // `it` has no check: lastSigmaIt, rescale, maxFeas and relGap are what iteration it + 1 will find
-    return cone_writes_beta(it + 1, lastSigmaIt, maxit, checkStepByStep, next_last_of_run, rescale, maxFeas, relGap)
-               ? QCONE_EXIT : QCONE_STEADY;
-}
-
-// the time-out predicate of step(): the same expression in front of the q-step (qcone_decide) and behind the body
+// the time-out predicate of step(): the same expression in front of a q-step that could run an early pass and behind the body
 bool Solver::time_limit_passed() const {
     // with one slab per process a per-rank clock could split the ranks: see kkt_block()
     return timeout_pending || (remote() ? false : (elapsed() > time_limit || (timeout_at > 0 && it >= timeout_at)));
 }
 
-// Does this iteration's q-step also run the cone pass of the next one?  Called after phase_z: beta_gamma says what this
-// iteration's own pass left.
-int Solver::qcone_decide() const {
-    if (qcone == 0 || !fused || multi() || prob.weighted || method != DOTSOCP_METHOD_INPALM) return QCONE_NONE;
-    if (!deferred || !beta_gamma || !bops.empty()) return QCONE_NONE;
-    const Slab &s = slabs[0];
-    if (s.g.ncl < 1 || s.fg.XB != 4) return QCONE_NONE;
-    if (qcone < 0 && s.fg.nyblk * s.fg.nxblk < 2048) return QCONE_NONE;      // grids whose cone pass runs as one chunk
-    if (time_limit_passed()) return QCONE_NONE;       // the check this asks for needs the state between two iterations
-    return qcone_form(it, lastSigmaIt, opts.maxit, opts.ifCheckStepByStep != 0, last_of_run, next_last_of_run, rescale,
-                      maxFeas, relGap);
-}
-
-bool if_adjust_sigma(double iter, double last_iter) {   // :361-379
-    const double passed = iter - last_iter;
-    if (iter < 20 && passed >= 3) return true;
-    if (iter < 50 && passed >= 6) return true;
-    if (iter < 100 && passed >= 10) return true;
-    if (iter < 200 && passed >= 15) return true;
-    if (iter < 500 && passed >= 25) return true;
-    return passed >= 40;
+// What plan_step() decides this iteration from, read at the top of step() behind the rescale block
+StepIn Solver::step_in() const {
+    StepIn in{};
+    in.s = SchedState{it, opts.maxit, lastSigmaIt, opts.ifCheckStepByStep != 0, rescale, maxFeas, relGap, run_left};
+    in.fused = fused; in.deferred = deferred; in.cone_carry = cone_carry; in.kkt_fold = kkt_fold;
+    in.beta_gamma = beta_gamma; in.timeout_pending = timeout_pending; in.early = early_pass;
+    const Slab &s0 = slabs[0];
+    in.qcone_eligible = qcone != 0 && fused && !multi() && !prob.weighted && method == DOTSOCP_METHOD_INPALM &&
+                        s0.g.ncl >= 1 && s0.fg.XB == 4 &&
+                        (qcone > 0 || s0.fg.nyblk * s0.fg.nxblk >= 2048);   // unset: grids whose cone pass runs as one chunk
+    // Time slabs, messages on the second streams (solver.h: comm_z): kernels on the main streams in an order that leaves
+    // every message time to travel while kernels that do not need it run.
+    in.inter = comm_z && multi() && fused;
+    in.can_split_z = in.can_split_q = in.inter && cone_split_enabled();
+    for (auto &s : slabs) {
+        in.can_split_z = in.can_split_z && s.fg.chunks >= 2;
+        in.can_split_q = in.can_split_q && qstep_rhs_chunks(s.g, s.fg) >= 2;
+    }
+    return in;
 }
 
 static const double kUpdateRule[11][2] = {   // :39-51
@@ -879,26 +840,15 @@ int Solver::step(bool *brk) {
     if (method == DOTSOCP_METHOD_PALM) return palm_step(brk);
     it += 1;
     DS_CHECK(rescale_block());
-    const bool adjustSigmaYes = if_adjust_sigma((double)it, lastSigmaIt);                  // :220
-    // known before the q-step (the time limit is the one trigger that is not: such a check takes the unfolded path)
-    // ... and a time limit that passed in an iteration which left gamma behind: this one checks (folded) and stops
-    // (a steady early pass has already run this iteration's pass and left gamma and no q: the pending check waits for the
-    // next iteration that writes beta -- the one after this, since no further early pass is issued past the limit)
-    const bool early_steady = early_pass && early_gout;
-    const bool kkt_due = opts.ifCheckStepByStep || adjustSigmaYes || it == opts.maxit || (timeout_pending && !early_steady);
-    // what this iteration's cone pass leaves in s.beta (solver.h: the gamma form)
-    // (cone_writes_beta covers every term of kkt_due but timeout_pending, which only step() knows: hence !kkt_due)
-    cone_gout = cone_carry && fused && deferred && !kkt_due &&
-                !cone_writes_beta(it, lastSigmaIt, opts.maxit, opts.ifCheckStepByStep != 0, last_of_run, rescale, maxFeas, relGap);
-    // fused dataflow: the q-step of a checking iteration accumulates its share of the KKT sums itself
-    const bool fold = kkt_due && kkt_fold && fused;
-    // Time slabs, messages on the second streams (solver.h: comm_z): kernels on the main streams in an order that leaves
-    // every message time to travel while kernels that do not need it run.
-    const bool inter = comm_z && multi() && fused;
-    bool split = inter && cone_split_enabled();
-    for (auto &s : slabs) split = split && s.fg.chunks >= 2;
-    bool split_q = inter && cone_split_enabled();
-    for (auto &s : slabs) split_q = split_q && qstep_rhs_chunks(s.g, s.fg) >= 2;
+    // the whole schedule of the iteration (schedule.h); the time limit is the one trigger it cannot know: a check it asks for
+    // takes the unfolded path
+    const StepIn in = step_in();
+    const StepPlan plan = plan_step(in);
+    if (plan.error) {
+        set_error("internal: the early cone pass wrote %s, the schedule asks for %s", early_pass == QCONE_STEADY ? "gamma" : "beta",
+                  plan.pass_gout ? "gamma" : "beta");
+        return DOTSOCP_ESTATE;
+    }
     // an exchange issued on the second streams without the join: fork, messages, mark
     auto async_comm = [&](const std::function<int()> &fn, SlabEvent ev) -> int {
         DS_CHECK(comm_fork());
@@ -908,7 +858,7 @@ int Solver::step(bool *brk) {
         DS_CHECK(rc);
         return comm_mark(ev);
     };
-    if (inter) {
+    if (in.inter) {
         // [E2 + E1] the q halo and the u0 tail of the last q-step travel while the cone chunks in front of the last one
         // -- which alone reads the halo -- run
         const bool pend = halo_pending;
@@ -916,51 +866,51 @@ int Solver::step(bool *brk) {
             DS_CHECK(make_u0_tail());
             DS_CHECK(async_comm([&]() { return ensure_halo(); }, EV_HALO));
         }
-        if (split) DS_CHECK(phase_z(1));
+        if (plan.split_z) DS_CHECK(phase_z(plan, 1));
         if (pend) DS_CHECK(comm_wait(EV_HALO));
-        if (!split) DS_CHECK(phase_z(0));
+        if (!plan.split_z && plan.cone_launch) DS_CHECK(phase_z(plan, 0));
         // The phi-step.  The last cone chunk (and the finalising of its adjoint tails) runs while the second streams carry
         // the latency-bound middle of the Poisson solve (poisson_t_tridiag); the tails [E4] leave right behind that and
         // travel beside the rest of the solve and the front of the q-step
         PhiHooks hooks;
         hooks.fill = [&]() -> int {
-            if (split) DS_CHECK(phase_z(2));
+            if (plan.split_z) DS_CHECK(phase_z(plan, 2));
             return make_tails();
         };
         hooks.behind = [&]() -> int { return async_comm([&]() { return send_tails(); }, EV_JOIN); };
         DS_CHECK(phase_phi(&hooks));
     } else {
         DS_CHECK(phase_phi());
-        DS_CHECK(phase_z(0));
+        if (plan.cone_launch) DS_CHECK(phase_z(plan, 0));
     }
-    if (fold) {
+    if (plan.fold) {
         // every region of partial sums is cleared before the q-step writes region 0; kkt_sums() then only adds the cell,
         // border and (time slabs) first-layer launches
         FOR_SLABS(s) DS_CHECK(clear_partials(s));
     }
-    if (inter) {
+    if (in.inter) {
         // [E3] the phi head travels (behind the tails) while every chunk of the q-step but the last -- the only reader of
         // the phi halo -- runs; the tails (read by the first chunk) have had the second half of the phi-step to arrive
         DS_CHECK(async_comm([&]() { return send_phi_head(); }, EV_HALO));
         DS_CHECK(comm_wait(EV_JOIN));
-        if (split_q) DS_CHECK(phase_q(1, fold));
+        if (plan.split_q) DS_CHECK(phase_q(plan, 1));
         DS_CHECK(comm_wait(EV_HALO));
-        DS_CHECK(phase_q(split_q ? 2 : 0, fold));
+        DS_CHECK(phase_q(plan, plan.split_q ? 2 : 0));
     } else {
         DS_CHECK(ship_tails());      // time slabs: phi head -> left, adjoint tails -> right
-        DS_CHECK(phase_q(0, fold, fold ? QCONE_NONE : qcone_decide()));
+        // the check a passed time limit asks for needs the state between two iterations: no early pass then
+        const bool early_ok = plan.qcone_candidate != QCONE_NONE && !time_limit_passed();
+        DS_CHECK(phase_q(plan, 0, early_ok ? plan.qcone_candidate : QCONE_NONE));
     }
     DS_CHECK(phase_mult());
     const bool timed_out = time_limit_passed();
     timeout_pending = false;
-    if (timed_out && (beta_gamma || early_pass)) {
-        // the unscheduled check would read beta: it is taken at the end of the next iteration, which writes beta
-        // (early_pass: the state is already that of the middle of the next iteration, whatever its pass wrote)
-        timeout_pending = true;
+    if (timed_out && timeout_check_waits(beta_gamma, early_pass != QCONE_NONE)) {
+        timeout_pending = true;      // taken at the end of the next iteration that writes beta, which then stops
         return 0;
     }
-    if (kkt_due || timed_out)                                                             // :221
-        DS_CHECK(kkt_block(adjustSigmaYes, timed_out, brk, fold));
+    if (plan.kkt_due || timed_out)                                                        // :221
+        DS_CHECK(kkt_block(plan.adjust_sigma, timed_out, brk, plan.fold));
     return 0;
 }
 
@@ -980,15 +930,14 @@ int Solver::run(i64 n_iters, i64 *done) {
     while (it < opts.maxit && !stopped) {
         if (n_iters >= 0 && n >= n_iters) break;
         bool brk = false;
-        last_of_run = (n_iters >= 0 && n + 1 >= n_iters);
-        next_last_of_run = (n_iters >= 0 && n + 2 >= n_iters);
+        run_left = (n_iters >= 0) ? n_iters - n : -1;
         DS_CHECK(step(&brk));
         if (brk) stopped = true;
         ++n;
     }
     DS_CHECK(need_beta_form("the end of run()"));
     DS_CHECK(need_q("the end of run()"));
-    if (early_pass) { set_error("internal: an early cone pass is pending at the end of run()"); return DOTSOCP_ESTATE; }
+    if (early_pass != QCONE_NONE) { set_error("internal: an early cone pass is pending at the end of run()"); return DOTSOCP_ESTATE; }
     DS_CHECK(ensure_halo());          // callers between run() calls see exchanged halos
     DS_CHECK(sync_all());
     DS_CHECK(prof_flush());

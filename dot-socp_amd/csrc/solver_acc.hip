@@ -132,9 +132,7 @@ int Solver::acc_rescale_block() {
         const double ratio = std::max(normAlps, normPhis) / std::min(normAlps, normPhis);
         if (ratio > 1.2) scaleYes = true;
     }
-    const bool first = (rescale == 1) && (maxFeas < 2e-2) && (it >= 10) && (relGap < 5e-2);
-    const bool second = (rescale == 2) && (maxFeas < 5e-3) && (it >= 50) && (relGap < 1e-2);
-    if (!(first || second || scaleYes)) return 0;
+    if (!(rescale_trigger(it, rescale, maxFeas, relGap) || scaleYes)) return 0;
     if (!scaleYes) DS_CHECK(norms(normPhis, normAlps));
     const double dScale2 = normPhis, cScale2 = normAlps;
     sigma = sigma * (cScale2 / dScale2);
@@ -178,7 +176,7 @@ int Solver::acc_step(bool *brk) {
     // one slab per process: time-outs are detected at KKT checks only, from the agreed clock (see Solver::kkt_block)
     const bool timed_out = remote() ? false : (elapsed() > time_limit);
     // the time-limit term of :254 is evaluated before the q-step here (the device queue is asynchronous)
-    const bool kkt_due = opts.ifCheckStepByStep || adjustSigmaYes || it == opts.maxit || timed_out;
+    const bool kkt_due = check_scheduled(it, lastSigmaIt, opts.maxit, opts.ifCheckStepByStep != 0) || timed_out;
     const AccCoef kc = acc_coef();
     const bool fold = acc_halpern && !kkt_due;      // extrapolation of z, beta inside the cone pass
     // an iteration with a KKT check: x^+ is stored for the block; afterwards z and beta are extrapolated by a second cone pass

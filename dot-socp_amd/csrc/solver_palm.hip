@@ -186,7 +186,7 @@ int Solver::palm_step(bool *brk) {
     // (Solver::phase_q; the right-hand side it also writes is not used: PALM's first q-step forms its own), and the
     // cell pass of the block then carries the pending multiplier step, the cell sums and F*B*beta (Solver::kkt_sums).
     const bool adjustSigmaYes = if_adjust_sigma((double)it, lastSigmaIt);                 // :231
-    const bool kkt_due = opts.ifCheckStepByStep || adjustSigmaYes || it == opts.maxit;
+    const bool kkt_due = check_scheduled(it, lastSigmaIt, opts.maxit, opts.ifCheckStepByStep != 0);
     const bool fold = kkt_due && kkt_fold;
     prof_begin(PH_QSTEP);
     if (fold) {

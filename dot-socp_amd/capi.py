@@ -132,6 +132,9 @@ SYMBOLS = {
     "dotsocp_dct_levels": (ctypes.c_int, [i64, ctypes.c_int]),
     "dotsocp_cdft_levels": (ctypes.c_int, [i64]),
     "dotsocp_tsolve_tri_safe": (ctypes.c_int, [i64, i64, i64]),
+    "dotsocp_dct_pass_kernel": (ctypes.c_int, [ctypes.c_int, i64, i64, i64, i64, ctypes.c_int]),
+    "dotsocp_tsolve_kernel": (ctypes.c_int, [ctypes.c_int, i64, i64, i64, i64]),
+    "dotsocp_row_pitch": (i64, [i64]),
     "dotsocp_cone_writes_beta": (ctypes.c_int, [i64, dbl, i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, dbl, dbl]),
     "dotsocp_rescale_due": (ctypes.c_int, [i64, ctypes.c_int, dbl, dbl]),
     "dotsocp_qcone_form": (ctypes.c_int, [i64, dbl, i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, dbl, dbl]),
@@ -266,6 +269,35 @@ def dct_levels(n, axis):
     lines beyond the LDS (from 4096 along y and 16384 along x / t up to 2^20; DOTSOCP_DCT_LONG_MIN lowers the start),
     negative: unsupported.  No device needed."""
     return int(lib().dotsocp_dct_levels(int(n), int(axis)))
+
+
+DCT_PASS_KERNELS = ("none", "pow2-wave", "pow2-wg", "pow2-pipe", "pow2-long", "other")
+TSOLVE_KERNELS = (None, "tri", "tri-pipe", "fused", "fused-pipe", "fused-pfa", "passes")
+
+
+def poisson_kernels(ny, nx, nt, pitch=None, device=0):
+    """Test support: the kernels the Poisson solve of a single slab launches on an ny x nx x nt grid (1-D: (nx1d, 1, nt))
+    on HIP device `device`, as (y pass, x pass, t step): two of DCT_PASS_KERNELS and one of TSOLVE_KERNELS.  pitch: doubles
+    between rows (default: what a context gives rows of ny doubles; 0: unpitched, as dotsocp_oper_poisson and
+    dotsocp_dct_axis run).  The library answers from the functions its launchers switch on (dotsocp_dct_pass_kernel,
+    dotsocp_tsolve_kernel); arrays are taken to be 16-byte aligned; without a device 256 CUs are assumed."""
+    L = lib()
+    ny, nx, nt = int(ny), int(nx), int(nt)
+    pitch = int(L.dotsocp_row_pitch(ny)) if pitch is None else int(pitch)
+    ky, kx = (L.dotsocp_dct_pass_kernel(int(device), ny, nx, nt, pitch, a) for a in (0, 1))
+    kt = L.dotsocp_tsolve_kernel(int(device), ny, nx, nt, pitch)
+    for k in (ky, kx, kt):
+        check(min(k, 0))
+    return DCT_PASS_KERNELS[ky], DCT_PASS_KERNELS[kx], TSOLVE_KERNELS[kt]
+
+
+def dct_pass_kernel(shape, axis, device=0):
+    """Test support: the kernel (one of DCT_PASS_KERNELS) of the DCT pass along `axis` of an unpitched array of `shape`
+    = (ny, nx, nt), as dotsocp_dct_axis runs it on HIP device `device`."""
+    ny, nx, nt = (int(v) for v in shape)
+    k = lib().dotsocp_dct_pass_kernel(int(device), ny, nx, nt, 0, int(axis))
+    check(min(k, 0))
+    return DCT_PASS_KERNELS[k]
 
 
 def cdft_levels(n):

@@ -323,6 +323,16 @@ int dotsocp_dct_levels(dotsocp_i64 n, int axis) { return dct_levels(n, axis); }
 int dotsocp_cdft_levels(dotsocp_i64 n) { return cdft_levels(n); }
 int dotsocp_tsolve_tri_safe(dotsocp_i64 ny, dotsocp_i64 nx, dotsocp_i64 nt) { return tsolve_tri_safe(ny, nx, nt) ? 1 : 0; }
 
+int dotsocp_dct_pass_kernel(int device, dotsocp_i64 ny, dotsocp_i64 nx, dotsocp_i64 nt, dotsocp_i64 pitch, int axis) {
+    DS_ARG(ny >= 1 && nx >= 1 && nt >= 1 && axis >= 0 && axis <= 2 && device >= 0, "bad pass request");
+    return dct_pass_kind(ny, nx, nt, axis, pitch, device_cus_of(device));
+}
+int dotsocp_tsolve_kernel(int device, dotsocp_i64 ny, dotsocp_i64 nx, dotsocp_i64 nt, dotsocp_i64 pitch) {
+    DS_ARG(ny >= 1 && nx >= 1 && nt >= 2 && device >= 0, "bad t-solve request");
+    return poisson_t_kind(ny, nx, nt, pitch, tsolve_tri_allowed(), device_cus_of(device));
+}
+dotsocp_i64 dotsocp_row_pitch(dotsocp_i64 ny) { return default_row_pitch(ny); }
+
 int dotsocp_cone_writes_beta(dotsocp_i64 it, double last_sigma_it, dotsocp_i64 maxit, int check_step_by_step,
                              int ends_run, int rescale, double maxFeas, double relGap) {
     return cone_writes_beta(SchedState{it, maxit, last_sigma_it, check_step_by_step != 0, rescale, maxFeas, relGap, ends_run ? 1 : -1}) ? 1 : 0;

@@ -99,9 +99,8 @@ void dct_plan_destroy(DctPlan *p) {
 
 bool dct_plan_is_pow2(const DctPlan *p) { return p->alg == DCT_ALG_FFT; }
 // (a t length that takes the two-level transform has no fused pass: forward pass, division, inverse pass)
-bool dct_plan_has_tsolve(const DctPlan *p) {
-    return (p->alg == DCT_ALG_FFT && p->n < dct_long_min(2)) || p->alg == DCT_ALG_PFA;
-}
+static bool alg_has_tsolve(int alg, i64 n) { return (alg == DCT_ALG_FFT && n < dct_long_min(2)) || alg == DCT_ALG_PFA; }
+bool dct_plan_has_tsolve(const DctPlan *p) { return alg_has_tsolve(p->alg, p->n); }
 
 __global__ void __launch_bounds__(256) k_copy(const double *__restrict__ src, double *__restrict__ dst, i64 n) {
     for (i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (i64)gridDim.x * blockDim.x) dst[i] = src[i];
@@ -132,6 +131,25 @@ int launch_dct_t_solve(const DctPlan *p, const double *src, double *dst, i64 ny,
     return pfa_launch_strided(p->pfa, src, dst, nl, 1, 0, nl, 0, nl, 2, &a, st);
 }
 
+// the lines of one axis of an [n0][n1][n2] array whose rows are P0 >= n0 doubles apart
+static LineMap axis_map(i64 n0, i64 n1, i64 n2, int axis, i64 P0) {
+    const i64 dims[3] = {n0, n1, n2};
+    const i64 n = dims[axis];
+    LineMap map;
+    if (P0 == n0) {
+        if (axis == 0) { map.nin = 1; map.outerStride = n; map.es = 1; }
+        else if (axis == 1) { map.nin = n0; map.outerStride = n0 * n1; map.es = n0; }
+        else { map.nin = n0 * n1; map.outerStride = 0; map.es = n0 * n1; }
+    } else {
+        // (power-of-two lengths: the axis-0 kernels take the line distance as an argument, the strided ones honour map.es)
+        if (axis == 0) { map.nin = 1; map.outerStride = P0; map.es = 1; }
+        else if (axis == 1) { map.nin = n0; map.outerStride = P0 * n1; map.es = P0; }
+        else { map.nin = n0; map.outerStride = P0; map.es = P0 * n1; }
+    }
+    map.nLines = n0 * n1 * n2 / n;
+    return map;
+}
+
 int launch_dct_axis(const DctPlan *p, const double *src, double *dst, i64 n0, i64 n1, i64 n2, int axis, int inverse,
                     hipStream_t st, i64 pitch0) {
     const i64 P0 = pitch0 > n0 ? pitch0 : n0;           // row pitch of both arrays
@@ -150,18 +168,7 @@ int launch_dct_axis(const DctPlan *p, const double *src, double *dst, i64 n0, i6
         DS_HIP(hipGetLastError());
         return 0;
     }
-    LineMap map;
-    if (P0 == n0) {
-        if (axis == 0) { map.nin = 1; map.outerStride = n; map.es = 1; }
-        else if (axis == 1) { map.nin = n0; map.outerStride = n0 * n1; map.es = n0; }
-        else { map.nin = n0 * n1; map.outerStride = 0; map.es = n0 * n1; }
-    } else {
-        // (power-of-two lengths: the axis-0 kernels take the line distance as an argument, the strided ones honour map.es)
-        if (axis == 0) { map.nin = 1; map.outerStride = P0; map.es = 1; }
-        else if (axis == 1) { map.nin = n0; map.outerStride = P0 * n1; map.es = P0; }
-        else { map.nin = n0; map.outerStride = P0; map.es = P0 * n1; }
-    }
-    map.nLines = total / n;
+    const LineMap map = axis_map(n0, n1, n2, axis, P0);
     switch (p->alg) {
         case DCT_ALG_FFT:
             if (axis == 0) return pow2_launch_axis0(p->pow2, src, dst, map, inverse, st);
@@ -231,17 +238,49 @@ bool tsolve_tri_allowed() {
     return !(e && strcmp(e, "dct") == 0);
 }
 
+// The alternatives of the single slab's t step, from the transform family of nt and the shape (pure host arithmetic):
+// launch_poisson_t_single switches on it, poisson_t_kind (dotsocp_tsolve_kernel) refines the same answer by kernel.
+enum { TS_TRI, TS_FUSED, TS_THREE };
+static int choose_t_single(int alg, i64 ny, i64 nx, i64 nt, i64 plane, bool allow_tri, int ncu) {
+    if (allow_tri && tsolve_tri_preferred(nt, alg == DCT_ALG_FFT, plane, ncu) && tsolve_tri_safe(ny, nx, nt)) return TS_TRI;
+    return alg_has_tsolve(alg, nt) ? TS_FUSED : TS_THREE;
+}
+
 int launch_poisson_t_single(const DctPlan *pt, const Grid &g, double kscale, const double *cy, const double *cx,
                             const double *ct, double *p, double *p2, i64 pitch0, hipStream_t st, bool allow_tri) {
     const i64 ny = g.ny, nx = g.nx, nt = g.nt;
-    if (allow_tri && tsolve_tri_preferred(nt, dct_plan_is_pow2(pt), g.plane) && tsolve_tri_safe(ny, nx, nt))
-        // no transform along t: the (ky, kx) modes are tridiagonal systems in t (tri.hip: k_tsolve_single / _pipe)
-        return launch_tsolve_tri(g, nt, kscale, cy, cx, p, st);
-    if (dct_plan_has_tsolve(pt))
-        return launch_dct_t_solve(pt, p, p, ny, ny * nx, 0, ny * nx, nt, kscale, cy, cx, ct, st, pitch0);
-    DS_CHECK(launch_dct_axis(pt, p, p2, ny, nx, nt, 2, 0, st, pitch0));
-    DS_CHECK(launch_spectral_divide(p2, ny, nt, 0, nx, kscale, cy, cx, ct, st, pitch0));
-    return launch_dct_axis(pt, p2, p, ny, nx, nt, 2, 1, st, pitch0);
+    switch (choose_t_single(pt->alg, ny, nx, nt, g.plane, allow_tri, device_cus())) {
+        case TS_TRI:
+            // no transform along t: the (ky, kx) modes are tridiagonal systems in t (tri.hip: k_tsolve_single / _pipe)
+            return launch_tsolve_tri(g, nt, kscale, cy, cx, p, st);
+        case TS_FUSED:
+            return launch_dct_t_solve(pt, p, p, ny, ny * nx, 0, ny * nx, nt, kscale, cy, cx, ct, st, pitch0);
+        default:
+            DS_CHECK(launch_dct_axis(pt, p, p2, ny, nx, nt, 2, 0, st, pitch0));
+            DS_CHECK(launch_spectral_divide(p2, ny, nt, 0, nx, kscale, cy, cx, ct, st, pitch0));
+            return launch_dct_axis(pt, p2, p, ny, nx, nt, 2, 1, st, pitch0);
+    }
+}
+
+int dct_pass_kind(i64 n0, i64 n1, i64 n2, int axis, i64 pitch0, int ncu) {
+    const i64 dims[3] = {n0, n1, n2};
+    const i64 n = dims[axis];
+    if (n <= 1) return DOTSOCP_PASS_NONE;
+    if (dct_choose_algorithm(n) != DCT_ALG_FFT) return DOTSOCP_PASS_OTHER;
+    return pow2_pass_kind(n, axis_map(n0, n1, n2, axis, pitch0 > n0 ? pitch0 : n0), axis == 0, ncu);
+}
+
+int poisson_t_kind(i64 ny, i64 nx, i64 nt, i64 pitch0, bool allow_tri, int ncu) {
+    const i64 py = pitch0 > ny ? pitch0 : ny;
+    const int alg = dct_choose_algorithm(nt);
+    switch (choose_t_single(alg, ny, nx, nt, py * nx, allow_tri, ncu)) {
+        case TS_TRI: return tsolve_tri_pipelined(nt, py * nx, ncu) ? DOTSOCP_TSOLVE_TRI_PIPE : DOTSOCP_TSOLVE_TRI;
+        case TS_FUSED:
+            if (alg != DCT_ALG_FFT) return DOTSOCP_TSOLVE_FUSED_PFA;
+            return pow2_tsolve_pipelined(nt, ny, ny * nx, 0, ny * nx, pitch0, ncu) ? DOTSOCP_TSOLVE_FUSED_PIPE
+                                                                                   : DOTSOCP_TSOLVE_FUSED;
+        default: return DOTSOCP_TSOLVE_PASSES;
+    }
 }
 
 }  // namespace dotsocp

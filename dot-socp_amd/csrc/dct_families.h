@@ -22,6 +22,14 @@ int pow2_launch_strided(const Pow2Plan *p, const double *src, double *dst, const
 int pow2_launch_tsolve(const Pow2Plan *p, const double *src, double *dst, i64 ny, i64 nplane, i64 line0, i64 nl,
                        double kscale, const double *cy, const double *cx, const double *ct, hipStream_t st, i64 pitch0);
 
+// Which kernel those launchers take, from the shape alone (pure host arithmetic; ncu: the CU count of the device; the
+// arrays are taken to be 16-byte aligned, as every allocation of the library is).  The launchers switch on the same
+// choice functions (choose_axis0 / choose_strided), so the answer is what runs.
+// pow2_pass_kind: DOTSOCP_PASS_POW2_* for a DCT-II / DCT-III pass over the lines of `map`
+int pow2_pass_kind(i64 n, const LineMap &map, bool axis0, int ncu);
+// does pow2_launch_tsolve with these arguments run k_dct_tsolve_pipe (else: k_dct_strided<2, .>)?
+bool pow2_tsolve_pipelined(i64 n, i64 ny, i64 nplane, i64 line0, i64 nl, i64 pitch0, int ncu);
+
 // Two-level transform for power-of-two lines that do not fit the LDS (dct_long.hip): 256 <= n <= DCT_LONG_MAX_N.
 #define DCT_LONG_MAX_N ((i64)1 << 20)
 i64 dct_long_min(int axis);             // smallest power of two that takes it along `axis` (DOTSOCP_DCT_LONG_MIN)

@@ -957,16 +957,21 @@ static int tile_log2_rows(int n, i64 nLines, int nbuf) {
     return lp;
 }
 
-int device_cus() {
+int device_cus_of(int dev) {
     static int cus[64] = {0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
+    if (dev < 0 || dev >= 64) return 256;
     if (cus[dev] == 0) {
         int v = 0;
         if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
         cus[dev] = v;
     }
     return cus[dev];
+}
+
+int device_cus() {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return 256;
+    return device_cus_of(dev);
 }
 
 static bool dct_pipe_enabled() {
@@ -992,125 +997,162 @@ static void for_const(int v, F f) {
 #define PIPE_LG_MIN 7
 #define PIPE_LG_MAX 11
 
-// mode 0: DCT-II, 1: DCT-III, 2: the fused t solve (sa)
+// ---------------------------------------------------------------------------------------------
+// Which kernel a pass takes.  choose_strided / choose_axis0 are pure host arithmetic on the shape of the pass, the
+// alignment of its arrays and the CU count; the launchers below switch on their answer and on nothing else, and
+// pow2_pass_kind / pow2_tsolve_pipelined (dotsocp_dct_pass_kernel, dotsocp_tsolve_kernel) give the same answer to the tests.
+// ---------------------------------------------------------------------------------------------
+enum { PK_WAVE, PK_WG, PK_WG1024, PK_PIPE, PK_TSOLVE_PIPE };
+struct Pow2Choice {
+    int kind;           // PK_*
+    bool vec;           // strided axes: one 16-byte access carries both lines of a pair
+    int lp;             // log2 of the staged pairs (axis 0: of the rows of ONE wave, lrw)
+    size_t lds;         // bytes of the in-LDS kernels' tile (PK_WG1024: of the doubled one)
+    unsigned blocks;
+    int G, nTiles;      // pipelined kernels: persistent workgroups, tiles
+    size_t ldsPipe;
+};
+
+// mode 0: DCT-II, 1: DCT-III, 2: the fused t solve (ny, line0, nplane: SolveArgs)
+static Pow2Choice choose_strided(int mode, int n, int lg, const LineMap &map, i64 ny, i64 line0, i64 nplane, bool aligned,
+                                 int ncu) {
+    Pow2Choice c{};
+    // t-axis solve (two transforms per row, in place): half the rows per workgroup so that twice as many
+    // workgroups are resident
+    c.lp = tile_log2_rows(n, map.nLines, mode == 2 ? 2 : 1);
+    c.lds = ((size_t)1 << c.lp) * row_stride(n) * sizeof(double2);
+    const i64 linesPerBlock = (i64)2 << c.lp;
+    c.blocks = (unsigned)((map.nLines + linesPerBlock - 1) / linesPerBlock);
+    // one 16-byte access carries both lines of a pair when consecutive lines are adjacent, even-aligned doubles
+    c.vec = (map.nin % 2 == 0) && (map.outerStride % 2 == 0) && (map.es % 2 == 0) && aligned;
+    c.kind = PK_WAVE;
+    // fused t-axis solve, pipelined: eigenvalue tables in LDS, a tile = consecutive columns of one x
+    // (rows of whole layers may be pitched: map.nin = ny lines per row, rows map.outerStride apart, time nodes map.es apart)
+    if (dct_pipe_enabled() && c.vec && mode == 2 && lg >= TS_LG_MIN && lg <= TS_LG_MAX &&
+        ((map.outerStride == 0 && map.es == map.nin) || (map.nin == ny && line0 == 0))) {
+        const i64 tileLines = ((i64)2 << TS_LG_CPLX) / n;
+        const i64 nxv = ny > 0 ? nplane / ny : 0;
+        c.ldsPipe = (((size_t)2 << TS_LG_CPLX) + (size_t)(n >> 1) + (size_t)n) * sizeof(double2) +
+                    ((size_t)n + (size_t)ny) * sizeof(double);
+        c.G = ncu * (c.ldsPipe <= DCT_LDS_MAX / 2 ? 2 : 1);     // two workgroups per CU when they fit
+        if (tileLines >= 2 && ny % tileLines == 0 && line0 % tileLines == 0 && map.nLines % tileLines == 0 &&
+            nxv * ny == nplane && c.ldsPipe <= DCT_LDS_MAX && map.nLines / tileLines >= 2 * (i64)c.G &&
+            map.nLines / tileLines < (1ll << 30)) {
+            c.nTiles = (int)(map.nLines / tileLines);
+            c.kind = PK_TSOLVE_PIPE;
+            return c;
+        }
+    }
+    // pipelined persistent kernel (see k_dct_axis0_pipe): whole tiles of 4096 complex values, the chip filled twice over
+    if (dct_pipe_enabled() && c.vec && mode != 2 && lg >= PIPE_LG_MIN && lg <= PIPE_LG_MAX) {
+        const i64 tileLines = ((i64)2 << PIPE_LG_CPLX) / n;
+        c.G = ncu & ~31;
+        if (map.nin % tileLines == 0 && map.nLines % tileLines == 0 && c.G >= 32 && map.nLines / tileLines >= 2 * (i64)c.G &&
+            map.nLines / tileLines < (1ll << 30)) {
+            c.nTiles = (int)(map.nLines / tileLines);
+            // tables: n / 2 twiddles + n weights (2048-point lines: n / 4 + n / 2 + 1, TwQuarter / WwHalf)
+            const size_t ntab = lg > 10 ? (size_t)(n >> 2) + (size_t)(n >> 1) + 1 : (size_t)(n >> 1) + (size_t)n;
+            c.ldsPipe = (((size_t)2 << PIPE_LG_CPLX) + ntab) * sizeof(double2);
+            c.kind = PK_PIPE;
+            return c;
+        }
+    }
+    if (c.vec && mode != 2 && ((i64)n << c.lp) >= 2 * DCT_WG_THREADS) {
+        // long lines: one workgroup of 1024 threads with the whole LDS (twice the rows) keeps 16 waves per CU
+        // like two workgroups of 512 would, and widens the contiguous segment per line to 128 bytes
+        const size_t lds2 = c.lds * 2;
+        if (lds2 <= DCT_LDS_MAX && lds2 > DCT_LDS_MAX / 2 && map.nLines >= ((i64)4 << c.lp)) {
+            c.lp += 1;
+            c.lds = lds2;
+            c.blocks = (unsigned)((map.nLines + ((i64)2 << c.lp) - 1) / ((i64)2 << c.lp));
+            c.kind = PK_WG1024;
+            return c;
+        }
+        c.kind = PK_WG;
+    }
+    return c;
+}
+
 static int launch_strided(int mode, const Pow2Plan *p, const double *src, double *dst, const LineMap &map,
                           const SolveArgs &sa, hipStream_t st) {
     const int n = (int)p->n, lg = p->lg;
     const double2 *tw = p->tw, *ww = p->ww;
-    // t-axis solve (two transforms per row, in place): half the rows per workgroup so that twice as many
-    // workgroups are resident
-    const int lp = tile_log2_rows(n, map.nLines, mode == 2 ? 2 : 1);
-    const size_t lds = ((size_t)1 << lp) * row_stride(n) * sizeof(double2);
-    if (lds > DCT_LDS_MAX) {
+    const Pow2Choice c = choose_strided(mode, n, lg, map, sa.ny, sa.line0, sa.nplane,
+                                        ((uintptr_t)src | (uintptr_t)dst) % 16 == 0, device_cus());
+    if (c.kind != PK_WG1024 && c.lds > DCT_LDS_MAX) {
         set_error("power-of-two DCT length %d does not fit the LDS in one pass (largest supported there: 8192)", n);
         return DOTSOCP_EINVAL;
     }
-    const i64 linesPerBlock = (i64)2 << lp;
-    const unsigned blocks = (unsigned)((map.nLines + linesPerBlock - 1) / linesPerBlock);
-    // one 16-byte access carries both lines of a pair when consecutive lines are adjacent, even-aligned doubles
-    const bool vec = (map.nin % 2 == 0) && (map.outerStride % 2 == 0) && (map.es % 2 == 0) && (((uintptr_t)src | (uintptr_t)dst) % 16 == 0);
-    // fused t-axis solve, pipelined: eigenvalue tables in LDS, a tile = consecutive columns of one x
-    // (rows of whole layers may be pitched: map.nin = ny lines per row, rows map.outerStride apart, time nodes map.es apart)
-    if (dct_pipe_enabled() && vec && mode == 2 && lg >= TS_LG_MIN && lg <= TS_LG_MAX &&
-        ((map.outerStride == 0 && map.es == map.nin) || (map.nin == sa.ny && sa.line0 == 0))) {
-        const i64 tileLines = ((i64)2 << TS_LG_CPLX) / n;
-        const i64 nxv = sa.ny > 0 ? sa.nplane / sa.ny : 0;
-        const size_t ldsPipe = (((size_t)2 << TS_LG_CPLX) + (size_t)(n >> 1) + (size_t)n) * sizeof(double2) +
-                               ((size_t)n + (size_t)sa.ny) * sizeof(double);
-        const int G = device_cus() * (ldsPipe <= DCT_LDS_MAX / 2 ? 2 : 1);     // two workgroups per CU when they fit
-        if (tileLines >= 2 && sa.ny % tileLines == 0 && sa.line0 % tileLines == 0 && map.nLines % tileLines == 0 &&
-            nxv * sa.ny == sa.nplane && ldsPipe <= DCT_LDS_MAX && map.nLines / tileLines >= 2 * (i64)G &&
-            map.nLines / tileLines < (1ll << 30)) {
-            const int nTiles = (int)(map.nLines / tileLines);
+    switch (c.kind) {
+        case PK_TSOLVE_PIPE: {
             static unsigned long long done_tp = 0;
             if (DeviceOnce once_(done_tp); once_)
-                for_const<TS_LG_MIN, TS_LG_MAX>(ALL_CONST, [](auto c) { allow_big_lds(k_dct_tsolve_pipe<decltype(c)::value>); });
-            for_const<TS_LG_MIN, TS_LG_MAX>(lg, [&](auto c) {
-                DS_KLAUNCH((k_dct_tsolve_pipe<decltype(c)::value>), dim3((unsigned)G), dim3(TS_THREADS), ldsPipe, st, src, dst,
-                           map, nTiles, sa, tw, ww);
+                for_const<TS_LG_MIN, TS_LG_MAX>(ALL_CONST, [](auto k) { allow_big_lds(k_dct_tsolve_pipe<decltype(k)::value>); });
+            for_const<TS_LG_MIN, TS_LG_MAX>(lg, [&](auto k) {
+                DS_KLAUNCH((k_dct_tsolve_pipe<decltype(k)::value>), dim3((unsigned)c.G), dim3(TS_THREADS), c.ldsPipe, st, src, dst,
+                           map, c.nTiles, sa, tw, ww);
             });
-            DS_HIP(hipGetLastError());
-            return 0;
+            break;
         }
-    }
-    // pipelined persistent kernel (see k_dct_axis0_pipe): whole tiles of 4096 complex values, the chip filled twice over
-    if (dct_pipe_enabled() && vec && mode != 2 && lg >= PIPE_LG_MIN && lg <= PIPE_LG_MAX) {
-        const i64 tileLines = ((i64)2 << PIPE_LG_CPLX) / n;
-        const int G = device_cus() & ~31;
-        if (map.nin % tileLines == 0 && map.nLines % tileLines == 0 && G >= 32 && map.nLines / tileLines >= 2 * (i64)G &&
-            map.nLines / tileLines < (1ll << 30)) {
-            const int nTiles = (int)(map.nLines / tileLines);
+        case PK_PIPE: {
             static unsigned long long done_sp = 0;
             if (DeviceOnce once_(done_sp); once_)
-                for_const<PIPE_LG_MIN, PIPE_LG_MAX>(ALL_CONST, [](auto c) {
-                    allow_big_lds(k_dct_strided_pipe<0, decltype(c)::value>);
-                    allow_big_lds(k_dct_strided_pipe<1, decltype(c)::value>);
+                for_const<PIPE_LG_MIN, PIPE_LG_MAX>(ALL_CONST, [](auto k) {
+                    allow_big_lds(k_dct_strided_pipe<0, decltype(k)::value>);
+                    allow_big_lds(k_dct_strided_pipe<1, decltype(k)::value>);
                 });
-            // tables: n / 2 twiddles + n weights (2048-point lines: n / 4 + n / 2 + 1, TwQuarter / WwHalf)
-            const size_t ntab = lg > 10 ? (size_t)(n >> 2) + (size_t)(n >> 1) + 1 : (size_t)(n >> 1) + (size_t)n;
-            const size_t ldsPipe = (((size_t)2 << PIPE_LG_CPLX) + ntab) * sizeof(double2);
-            for_const<PIPE_LG_MIN, PIPE_LG_MAX>(lg, [&](auto c) {
+            for_const<PIPE_LG_MIN, PIPE_LG_MAX>(lg, [&](auto k) {
                 for_const<0, 1>(mode, [&](auto m) {
-                    DS_KLAUNCH((k_dct_strided_pipe<decltype(m)::value, decltype(c)::value>), dim3((unsigned)G),
-                               dim3(PIPE_THREADS), ldsPipe, st, src, dst, map, nTiles, tw, ww);
+                    DS_KLAUNCH((k_dct_strided_pipe<decltype(m)::value, decltype(k)::value>), dim3((unsigned)c.G),
+                               dim3(PIPE_THREADS), c.ldsPipe, st, src, dst, map, c.nTiles, tw, ww);
                 });
             });
-            DS_HIP(hipGetLastError());
-            return 0;
+            break;
         }
-    }
-    if (vec && mode != 2 && ((i64)n << lp) >= 2 * DCT_WG_THREADS) {
-        static unsigned long long done_wg = 0;
-        if (DeviceOnce once_(done_wg); once_)
-            for_const<0, 1>(ALL_CONST, [](auto m) {
-                allow_big_lds(k_dct_strided_wg<decltype(m)::value, 512>);
-                allow_big_lds(k_dct_strided_wg<decltype(m)::value, 1024>);
-            });
-        // long lines: one workgroup of 1024 threads with the whole LDS (twice the rows) keeps 16 waves per CU
-        // like two workgroups of 512 would, and widens the contiguous segment per line to 128 bytes
-        const size_t lds2 = lds * 2;
-        if (lds2 <= DCT_LDS_MAX && lds2 > DCT_LDS_MAX / 2 && map.nLines >= ((i64)4 << lp)) {
-            const int lp2 = lp + 1;
-            const unsigned blocks2 = (unsigned)((map.nLines + ((i64)2 << lp2) - 1) / ((i64)2 << lp2));
+        case PK_WG1024:
+        case PK_WG: {
+            static unsigned long long done_wg = 0;
+            if (DeviceOnce once_(done_wg); once_)
+                for_const<0, 1>(ALL_CONST, [](auto m) {
+                    allow_big_lds(k_dct_strided_wg<decltype(m)::value, 512>);
+                    allow_big_lds(k_dct_strided_wg<decltype(m)::value, 1024>);
+                });
             for_const<0, 1>(mode, [&](auto m) {
-                DS_KLAUNCH((k_dct_strided_wg<decltype(m)::value, 1024>), dim3(blocks2), dim3(1024), lds2, st, src, dst, map, lg,
-                           lp2, tw, ww);
+                if (c.kind == PK_WG1024)
+                    DS_KLAUNCH((k_dct_strided_wg<decltype(m)::value, 1024>), dim3(c.blocks), dim3(1024), c.lds, st, src, dst, map,
+                               lg, c.lp, tw, ww);
+                else
+                    DS_KLAUNCH((k_dct_strided_wg<decltype(m)::value, 512>), dim3(c.blocks), dim3(DCT_WG_THREADS), c.lds, st, src,
+                               dst, map, lg, c.lp, tw, ww);
             });
-            DS_HIP(hipGetLastError());
-            return 0;
+            break;
         }
-        for_const<0, 1>(mode, [&](auto m) {
-            DS_KLAUNCH((k_dct_strided_wg<decltype(m)::value, 512>), dim3(blocks), dim3(DCT_WG_THREADS), lds, st, src, dst, map,
-                       lg, lp, tw, ww);
-        });
-        DS_HIP(hipGetLastError());
-        return 0;
+        default: {
+            static unsigned long long done = 0;
+            if (DeviceOnce once_(done); once_)
+                for_const<0, 2>(ALL_CONST, [](auto m) {
+                    allow_big_lds(k_dct_strided<decltype(m)::value, true>);
+                    allow_big_lds(k_dct_strided<decltype(m)::value, false>);
+                });
+            for_const<0, 2>(mode, [&](auto m) {
+                if (c.vec)
+                    DS_KLAUNCH((k_dct_strided<decltype(m)::value, true>), dim3(c.blocks), dim3(DCT_THREADS), c.lds, st, src, dst,
+                               map, lg, c.lp, sa, tw, ww);
+                else
+                    DS_KLAUNCH((k_dct_strided<decltype(m)::value, false>), dim3(c.blocks), dim3(DCT_THREADS), c.lds, st, src, dst,
+                               map, lg, c.lp, sa, tw, ww);
+            });
+        }
     }
-    static unsigned long long done = 0;
-    if (DeviceOnce once_(done); once_)
-        for_const<0, 2>(ALL_CONST, [](auto m) {
-            allow_big_lds(k_dct_strided<decltype(m)::value, true>);
-            allow_big_lds(k_dct_strided<decltype(m)::value, false>);
-        });
-    for_const<0, 2>(mode, [&](auto m) {
-        if (vec)
-            DS_KLAUNCH((k_dct_strided<decltype(m)::value, true>), dim3(blocks), dim3(DCT_THREADS), lds, st, src, dst, map, lg,
-                       lp, sa, tw, ww);
-        else
-            DS_KLAUNCH((k_dct_strided<decltype(m)::value, false>), dim3(blocks), dim3(DCT_THREADS), lds, st, src, dst, map, lg,
-                       lp, sa, tw, ww);
-    });
     DS_HIP(hipGetLastError());
     return 0;
 }
 
-int pow2_launch_strided(const Pow2Plan *p, const double *src, double *dst, const LineMap &map, int inverse, hipStream_t st) {
-    if (p->lng && p->n >= dct_long_min(1)) return long_launch(p->lng, src, dst, map, false, inverse, st);
-    return launch_strided(inverse ? 1 : 0, p, src, dst, map, SolveArgs{}, st);
-}
+// lines of this length along this axis (0: y; else x / t) leave the LDS: the two-level transform (dct_long.hip)
+static bool pow2_two_level(i64 n, int axis) { return n >= dct_long_min(axis == 0 ? 0 : 1); }
 
-int pow2_launch_tsolve(const Pow2Plan *p, const double *src, double *dst, i64 ny, i64 nplane, i64 line0, i64 nl,
-                       double kscale, const double *cy, const double *cx, const double *ct, hipStream_t st, i64 pitch0) {
+// line map of the fused t solve over the columns line0 .. line0 + nl - 1 (pow2_launch_tsolve)
+static LineMap tsolve_map(i64 ny, i64 nplane, i64 nl, i64 pitch0) {
     LineMap map;
     map.nin = nl;
     map.outerStride = 0;
@@ -1121,76 +1163,126 @@ int pow2_launch_tsolve(const Pow2Plan *p, const double *src, double *dst, i64 ny
         map.outerStride = pitch0;
         map.es = pitch0 * (nplane / ny);
     }
+    return map;
+}
+
+static int lg_of(i64 n) {
+    int lg = 0;
+    while (((i64)1 << lg) < n) ++lg;
+    return lg;
+}
+
+int pow2_launch_strided(const Pow2Plan *p, const double *src, double *dst, const LineMap &map, int inverse, hipStream_t st) {
+    if (pow2_two_level(p->n, 1)) return long_launch(p->lng, src, dst, map, false, inverse, st);
+    return launch_strided(inverse ? 1 : 0, p, src, dst, map, SolveArgs{}, st);
+}
+
+int pow2_launch_tsolve(const Pow2Plan *p, const double *src, double *dst, i64 ny, i64 nplane, i64 line0, i64 nl,
+                       double kscale, const double *cy, const double *cx, const double *ct, hipStream_t st, i64 pitch0) {
+    const LineMap map = tsolve_map(ny, nplane, nl, pitch0);
     if (map.nLines <= 0) return 0;
     SolveArgs sa{ny, line0, nplane, kscale, cy, cx, ct};
     return launch_strided(2, p, src, dst, map, sa, st);
 }
 
-int pow2_launch_axis0(const Pow2Plan *p, const double *src, double *dst, const LineMap &map, int inverse, hipStream_t st) {
-    if (p->lng && p->n >= dct_long_min(0)) return long_launch(p->lng, src, dst, map, true, inverse, st);
+// axis 0: PK_WAVE, PK_WG or PK_PIPE; lp = lrw, the log2 of the rows of one wave
+static Pow2Choice choose_axis0(i64 n, int lg, const LineMap &map, bool aligned, int ncu) {
+    Pow2Choice c{};
     // each wave owns 2^lrw rows; a workgroup of 4 waves stages 4 * 2^lrw rows
+    const int lp = tile_log2_rows((int)n, map.nLines, 1);
+    const int lrw = lp >= 2 ? lp - 2 : 0;
+    c.vec = aligned;
+    c.lp = lrw;
+    c.lds = ((size_t)DCT_WAVES << lrw) * row_stride((int)n) * sizeof(double2);
+    const i64 linesPerBlock = (i64)(2 * DCT_WAVES) << lrw;
+    c.blocks = (unsigned)((map.nLines + linesPerBlock - 1) / linesPerBlock);
+    c.kind = PK_WAVE;
+    // pipelined persistent kernel: whole tiles of 8192 doubles, enough of them to fill the chip twice
+    const i64 tileLines = ((i64)2 << PIPE_LG_CPLX) / n;
+    if (dct_pipe_enabled() && lg >= PIPE_LG_MIN && lg <= PIPE_LG_MAX && map.nLines % tileLines == 0 && aligned) {
+        const i64 nTiles = map.nLines / tileLines;
+        if (nTiles >= 2 * (i64)ncu && nTiles < (1ll << 30)) {
+            const size_t rs = (size_t)n + 1;
+            const size_t ntab = lg > 10 ? (size_t)(n >> 2) + (size_t)(n >> 1) + 1 : (size_t)(n >> 1) + (size_t)n;
+            c.ldsPipe = (2 * (rs << (PIPE_LG_CPLX - lg)) + ntab) * sizeof(double2);
+            c.G = ncu;
+            c.nTiles = (int)nTiles;
+            c.kind = PK_PIPE;
+            return c;
+        }
+    }
+    if (((n / 2) << lp) >= 2 * DCT_WG_THREADS) {
+        // same rows per workgroup (4 << lrw complex rows), twice the threads, shared by all of them
+        const int lrows = lrw + 2;
+        c.blocks = (unsigned)((((map.nLines + 1) / 2) + ((i64)1 << lrows) - 1) >> lrows);
+        c.kind = PK_WG;
+    }
+    return c;
+}
+
+int pow2_launch_axis0(const Pow2Plan *p, const double *src, double *dst, const LineMap &map, int inverse, hipStream_t st) {
+    if (pow2_two_level(p->n, 0)) return long_launch(p->lng, src, dst, map, true, inverse, st);
     const i64 n = p->n;
     const int lg = p->lg;
     const double2 *tw = p->tw, *ww = p->ww;
-    int lp = tile_log2_rows((int)n, map.nLines, 1);
-    const int lrw = lp >= 2 ? lp - 2 : 0;
-    const size_t lds = ((size_t)DCT_WAVES << lrw) * row_stride((int)n) * sizeof(double2);
-    if (lds > DCT_LDS_MAX) {
+    const Pow2Choice c = choose_axis0(n, lg, map, ((uintptr_t)src | (uintptr_t)dst) % 16 == 0, device_cus());
+    if (c.lds > DCT_LDS_MAX) {
         set_error("power-of-two DCT length %lld does not fit the LDS (largest supported: 2048 along y, 8192 along x / t)",
                   (long long)n);
         return DOTSOCP_EINVAL;
     }
-    const i64 linesPerBlock = (i64)(2 * DCT_WAVES) << lrw;
-    const unsigned blocks = (unsigned)((map.nLines + linesPerBlock - 1) / linesPerBlock);
     static unsigned long long done = 0;
     if (DeviceOnce once_(done); once_)
         for_const<0, 1>(ALL_CONST, [](auto i) {
             allow_big_lds(k_dct_axis0<decltype(i)::value != 0>);
             allow_big_lds(k_dct_axis0_wg<decltype(i)::value != 0>);
         });
-    // pipelined persistent kernel: whole tiles of 8192 doubles, enough of them to fill the chip twice
-    const i64 tileLines = ((i64)2 << PIPE_LG_CPLX) / n;
-    if (dct_pipe_enabled() && lg >= PIPE_LG_MIN && lg <= PIPE_LG_MAX && map.nLines % tileLines == 0 &&
-        (((uintptr_t)src | (uintptr_t)dst) % 16 == 0)) {
-        const i64 nTiles = map.nLines / tileLines;
-        const int ncu = device_cus();
-        if (nTiles >= 2 * (i64)ncu && nTiles < (1ll << 30)) {
+    switch (c.kind) {
+        case PK_PIPE: {
             static unsigned long long done_pipe = 0;
             if (DeviceOnce once_(done_pipe); once_)
-                for_const<PIPE_LG_MIN, PIPE_LG_MAX>(ALL_CONST, [](auto c) {
-                    allow_big_lds(k_dct_axis0_pipe<false, decltype(c)::value>);
-                    allow_big_lds(k_dct_axis0_pipe<true, decltype(c)::value>);
+                for_const<PIPE_LG_MIN, PIPE_LG_MAX>(ALL_CONST, [](auto k) {
+                    allow_big_lds(k_dct_axis0_pipe<false, decltype(k)::value>);
+                    allow_big_lds(k_dct_axis0_pipe<true, decltype(k)::value>);
                 });
-            const size_t rs = (size_t)n + 1;
-            const size_t ntab = lg > 10 ? (size_t)(n >> 2) + (size_t)(n >> 1) + 1 : (size_t)(n >> 1) + (size_t)n;
-            const size_t ldsPipe = (2 * (rs << (PIPE_LG_CPLX - lg)) + ntab) * sizeof(double2);
-            for_const<PIPE_LG_MIN, PIPE_LG_MAX>(lg, [&](auto c) {
+            for_const<PIPE_LG_MIN, PIPE_LG_MAX>(lg, [&](auto k) {
                 for_const<0, 1>(inverse ? 1 : 0, [&](auto i) {
-                    DS_KLAUNCH((k_dct_axis0_pipe<decltype(i)::value != 0, decltype(c)::value>), dim3((unsigned)ncu),
-                               dim3(PIPE_THREADS), ldsPipe, st, src, dst, (int)nTiles, map.outerStride, tw, ww);
+                    DS_KLAUNCH((k_dct_axis0_pipe<decltype(i)::value != 0, decltype(k)::value>), dim3((unsigned)c.G),
+                               dim3(PIPE_THREADS), c.ldsPipe, st, src, dst, c.nTiles, map.outerStride, tw, ww);
                 });
             });
-            DS_HIP(hipGetLastError());
-            return 0;
+            break;
         }
+        case PK_WG:
+            for_const<0, 1>(inverse ? 1 : 0, [&](auto i) {
+                DS_KLAUNCH(k_dct_axis0_wg<decltype(i)::value != 0>, dim3(c.blocks), dim3(DCT_WG_THREADS), c.lds, st, src, dst,
+                           map.nLines, map.outerStride, lg, c.lp + 2, tw, ww);
+            });
+            break;
+        default:
+            for_const<0, 1>(inverse ? 1 : 0, [&](auto i) {
+                DS_KLAUNCH(k_dct_axis0<decltype(i)::value != 0>, dim3(c.blocks), dim3(DCT_THREADS), c.lds, st, src, dst,
+                           map.nLines, map.outerStride, lg, c.lp, tw, ww);
+            });
     }
-    if (((n / 2) << lp) >= 2 * DCT_WG_THREADS) {
-        // same rows per workgroup (4 << lrw complex rows), twice the threads, shared by all of them
-        const int lrows = lrw + 2;
-        const unsigned wblocks = (unsigned)((((map.nLines + 1) / 2) + ((i64)1 << lrows) - 1) >> lrows);
-        for_const<0, 1>(inverse ? 1 : 0, [&](auto i) {
-            DS_KLAUNCH(k_dct_axis0_wg<decltype(i)::value != 0>, dim3(wblocks), dim3(DCT_WG_THREADS), lds, st, src, dst,
-                       map.nLines, map.outerStride, lg, lrows, tw, ww);
-        });
-        DS_HIP(hipGetLastError());
-        return 0;
-    }
-    for_const<0, 1>(inverse ? 1 : 0, [&](auto i) {
-        DS_KLAUNCH(k_dct_axis0<decltype(i)::value != 0>, dim3(blocks), dim3(DCT_THREADS), lds, st, src, dst, map.nLines,
-                   map.outerStride, lg, lrw, tw, ww);
-    });
     DS_HIP(hipGetLastError());
     return 0;
+}
+
+static int pass_kind_of(int pk) {
+    return pk == PK_WAVE ? DOTSOCP_PASS_POW2_WAVE : (pk == PK_PIPE ? DOTSOCP_PASS_POW2_PIPE : DOTSOCP_PASS_POW2_WG);
+}
+
+int pow2_pass_kind(i64 n, const LineMap &map, bool axis0, int ncu) {
+    if (pow2_two_level(n, axis0 ? 0 : 1)) return DOTSOCP_PASS_POW2_LONG;
+    const int lg = lg_of(n);
+    if (axis0) return pass_kind_of(choose_axis0(n, lg, map, true, ncu).kind);
+    return pass_kind_of(choose_strided(0, (int)n, lg, map, 0, 0, 0, true, ncu).kind);
+}
+
+bool pow2_tsolve_pipelined(i64 n, i64 ny, i64 nplane, i64 line0, i64 nl, i64 pitch0, int ncu) {
+    const LineMap map = tsolve_map(ny, nplane, nl, pitch0);
+    return map.nLines > 0 && choose_strided(2, (int)n, lg_of(n), map, ny, line0, nplane, true, ncu).kind == PK_TSOLVE_PIPE;
 }
 
 }  // namespace dotsocp

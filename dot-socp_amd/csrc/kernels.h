@@ -379,10 +379,12 @@ int launch_tri_final(const Grid &g, i64 nt, double kscale, const double *cy, con
                      const double *back, double *x, hipStream_t st);
 // the SINGLE slab's t-axis solve by the same elimination, in place on x = [g.plane][nt] (no transform along t; any nt <= 512)
 bool tsolve_tri_supported(i64 nt);
-bool tsolve_tri_preferred(i64 nt, bool pow2, i64 plane);      // faster than the transform pass(es) along t?
+bool tsolve_tri_preferred(i64 nt, bool pow2, i64 plane, int ncu);   // faster than the transform pass(es) along t?
 bool tsolve_tri_safe(i64 ny, i64 nx, i64 nt);                 // no power rho^t of a piece leaves the safe range (else: transform passes)
 int launch_tsolve_tri(const Grid &g, i64 nt, double kscale, const double *cy, const double *cx, double *x, hipStream_t st);
+bool tsolve_tri_pipelined(i64 nt, i64 plane, int ncu);        // launch_tsolve_tri: k_tsolve_pipe (else k_tsolve_single)
 int device_cus();              // compute units of the current device, cached per device (dct_pow2.hip); 256 if the query fails
+int device_cus_of(int dev);    // ... of device `dev`
 // up to DS_MAX_WORLD messages copied by ONE launch on the receiving slab's stream: message m = count[m] doubles from
 // src[m] (this or a peer device) to dst[m] -- the exchanges between the slabs of one process (one launch per receiver
 // instead of one event-ordered copy per message)
@@ -482,5 +484,12 @@ bool tsolve_tri_allowed();
 // forward transform + spectral division + inverse transform.
 int launch_poisson_t_single(const DctPlan *pt, const Grid &g, double kscale, const double *cy, const double *cx,
                             const double *ct, double *p, double *p2, i64 pitch0, hipStream_t st, bool allow_tri);
+// Which kernel launch_dct_axis resp. launch_poisson_t_single take on a device of ncu CUs (DOTSOCP_PASS_* / DOTSOCP_TSOLVE_*
+// of include/dotsocp.h).  Pure host arithmetic on the same choice functions the launchers switch on; the arrays are taken to
+// be 16-byte aligned, as every allocation of the library is.
+int dct_pass_kind(i64 n0, i64 n1, i64 n2, int axis, i64 pitch0, int ncu);
+int poisson_t_kind(i64 ny, i64 nx, i64 nt, i64 pitch0, bool allow_tri, int ncu);
+// row pitch of a context's device arrays for rows of ny doubles (solver_slabs.hip: Solver::row_pitch)
+i64 default_row_pitch(i64 ny);
 
 }  // namespace dotsocp

@@ -215,7 +215,9 @@ int Solver::ensure_alloc() {
 // pad between the ten columns of z and beta (common.h: Grid::Nc)
 i64 Solver::column_pad() const { return (ny * nx >= 4096) ? 48 : 0; }
 
-i64 Solver::row_pitch() const {
+i64 Solver::row_pitch() const { return default_row_pitch(ny); }
+
+i64 default_row_pitch(i64 ny) {
     static const bool on = !(getenv("DOTSOCP_PITCH") && atoi(getenv("DOTSOCP_PITCH")) == 0);
     if (!on || ny <= 16) return ny;
     if (ny % 16 == 0) {

@@ -414,15 +414,16 @@ static bool tsolve_pipe_on() {
 }
 // the persistent LDS-DMA flavour: grids with enough tiles to keep two workgroups per CU busy for many rounds; its image
 // fits twice into a CU's LDS up to nt = 136
-static bool tsolve_pipe_fits(i64 nt, i64 plane) {
-    return nt > 64 && nt <= 136 && (plane + 63) / 64 >= 16 * (i64)device_cus() && (plane % 2) == 0;
+static bool tsolve_pipe_fits(i64 nt, i64 plane, int ncu) {
+    return nt > 64 && nt <= 136 && (plane + 63) / 64 >= 16 * (i64)ncu && (plane % 2) == 0;
 }
+bool tsolve_tri_pipelined(i64 nt, i64 plane, int ncu) { return tsolve_pipe_on() && tsolve_pipe_fits(nt, plane, ncu); }
 // Is the tridiagonal solve the faster t-axis solve of a single slab?  Every length without a power-of-two transform pass
 // (prime-factor lengths 0.66 vs 0.86 ms at 1025 x 1025 x 129, and no dense product along t for the rest); powers of two
 // where the pipelined flavour applies (0.51 vs 0.56 ms at 1024 x 1024 x 128; the one-tile-per-workgroup kernel: 0.62).
-bool tsolve_tri_preferred(i64 nt, bool pow2, i64 plane) {
+bool tsolve_tri_preferred(i64 nt, bool pow2, i64 plane, int ncu) {
     if (!tsolve_tri_supported(nt)) return false;
-    return !pow2 || (tsolve_pipe_on() && tsolve_pipe_fits(nt, plane));
+    return !pow2 || tsolve_tri_pipelined(nt, plane, ncu);
 }
 
 // in place on x: [plane][nt] with plane = py * nx doubles per layer (pad entries of a row are modes of their own: zeros)
@@ -437,8 +438,7 @@ int launch_tsolve_tri(const Grid &g, i64 nt, double kscale, const double *cy, co
     const size_t img = (size_t)((nt + 1) / 2) * 2 * 64 * sizeof(double);
     // persistent LDS-DMA flavour (DOTSOCP_TS_PIPE=0: the one-tile-per-workgroup kernel)
     const int G = 2 * device_cus();
-    const bool pipe = tsolve_pipe_on() && tsolve_pipe_fits(nt, g.plane);
-    if (pipe) {
+    if (tsolve_tri_pipelined(nt, g.plane, device_cus())) {
         static std::mutex mu;
         static unsigned long long done = 0;
         int dev = 0;

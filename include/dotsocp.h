@@ -249,6 +249,33 @@ int dotsocp_dct_levels(dotsocp_i64 n, int axis);
  * as with DOTSOCP_TSOLVE=dct.  Pure host arithmetic, no device. */
 int dotsocp_tsolve_tri_safe(dotsocp_i64 ny, dotsocp_i64 nx, dotsocp_i64 nt);
 
+/* Test support: which kernels the Poisson solve of a single slab launches on an ny x nx x nt grid (1-D: ny = nx1d, nx = 1)
+ * whose rows are `pitch` doubles apart (dotsocp_row_pitch(ny) in a context; <= ny: unpitched), on HIP device `device`.
+ * Pure host arithmetic on the functions the launchers themselves switch on; the one HIP call is the query of the
+ * device's CU count (cached; 256 is assumed where it cannot be asked).  Honours the switches the launchers honour
+ * (DOTSOCP_DCT_PIPE, DOTSOCP_TS_PIPE, DOTSOCP_TSOLVE, DOTSOCP_DCT_LONG_MIN and those of dotsocp_dct_algorithm).  What a
+ * query by shape cannot know is the alignment of the arrays: it assumes the 16-byte alignment every allocation of
+ * the library has (arrays of a caller's own, as dotsocp_dct_axis copies them, are allocations of the library too).
+ *   dotsocp_dct_pass_kernel: the DCT-II / DCT-III pass along `axis` (0: y, 1: x, 2: t as a plain transform pass).
+ *   dotsocp_tsolve_kernel:   the t step between the forward and the inverse x / y passes.
+ * Negative: a bad argument. */
+#define DOTSOCP_PASS_NONE 0        /* length 1: a copy */
+#define DOTSOCP_PASS_POW2_WAVE 1   /* power of two inside the LDS, one wave per row: k_dct_axis0, k_dct_strided */
+#define DOTSOCP_PASS_POW2_WG 2     /* ... the whole workgroup per tile: k_dct_axis0_wg, k_dct_strided_wg */
+#define DOTSOCP_PASS_POW2_PIPE 3   /* ... persistent workgroups fed by LDS-DMA: k_dct_axis0_pipe, k_dct_strided_pipe */
+#define DOTSOCP_PASS_POW2_LONG 4   /* power of two beyond the LDS: the two-level transform */
+#define DOTSOCP_PASS_OTHER 5       /* another family (dotsocp_dct_algorithm) */
+#define DOTSOCP_TSOLVE_TRI 1          /* tridiagonal systems, one tile per workgroup: k_tsolve_single */
+#define DOTSOCP_TSOLVE_TRI_PIPE 2     /* ... pipelined: k_tsolve_pipe */
+#define DOTSOCP_TSOLVE_FUSED 3        /* DCT-II, division, DCT-III in one pass: k_dct_strided<2, .> */
+#define DOTSOCP_TSOLVE_FUSED_PIPE 4   /* ... pipelined: k_dct_tsolve_pipe */
+#define DOTSOCP_TSOLVE_FUSED_PFA 5    /* ... of a prime-factor length: k_pfa_strided */
+#define DOTSOCP_TSOLVE_PASSES 6       /* forward pass, spectral division, inverse pass */
+int dotsocp_dct_pass_kernel(int device, dotsocp_i64 ny, dotsocp_i64 nx, dotsocp_i64 nt, dotsocp_i64 pitch, int axis);
+int dotsocp_tsolve_kernel(int device, dotsocp_i64 ny, dotsocp_i64 nx, dotsocp_i64 nt, dotsocp_i64 pitch);
+/* Row pitch (doubles) of the device arrays of a context whose rows hold ny doubles.  Pure host arithmetic. */
+dotsocp_i64 dotsocp_row_pitch(dotsocp_i64 ny);
+
 /* The schedule of the cone pass's gamma form (pure host arithmetic, no device).  Between two plain inPALM iterations
  * the cone pass leaves gamma = beta + tau z in the multiplier array instead of beta; only the next cone pass can read
  * that.  dotsocp_cone_writes_beta: 1 if the pass of iteration `it` must leave beta -- the iteration ends in a KKT check

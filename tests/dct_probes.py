@@ -66,7 +66,9 @@ CASES = {
              ((10, 1024, 1), 1), ((16, 1024, 1), 1), ((10, 2048, 1), 1),
              ((3, 3, 8), 2), ((2, 5, 64), 2), ((3, 3, 1024), 2), ((2, 8, 1024), 2)],
     "fft1-pipe": [((128, 32768, 1), 0), ((512, 8192, 1), 0), ((2048, 2048, 1), 0),
-                  ((512, 128, 64), 1), ((512, 512, 16), 1), ((2048, 2048, 1), 1)],
+                  ((512, 128, 64), 1), ((512, 512, 16), 1), ((2048, 2048, 1), 1),
+                  # 256 and 1024: the lengths of the parity-gate grid and of the benchmark grid
+                  ((256, 16384, 1), 0), ((1024, 4096, 1), 0), ((512, 256, 32), 1), ((512, 1024, 8), 1)],
     "fft2": [((4096, 9, 1), 0), ((8192, 9, 1), 0), ((33, 16384, 1), 1), ((3, 3, 16384), 2), ((65536, 5, 1), 0, 14),
              ((1 << 19, 5, 1), 0, 8), ((1 << 20, 5, 1), 0, 8)],
     "pfa": [c for n in (1025, 513, 129, 17, 3) for c in (((n, 9, 1), 0), ((9, n, 1), 1), ((10, n, 1), 1), ((3, 3, n), 2))] +
@@ -456,18 +458,26 @@ def family_on_device(D, n, axis):
     return alg
 
 
+def kernel_on_device(D, shape, axis):
+    """which kernel generation the library's launcher takes for this pass on the current device (capi.DCT_PASS_KERNELS:
+    the launchers switch on the function that answers)"""
+    from dotsocp_amd import capi
+    return capi.dct_pass_kernel(shape, axis)
+
+
 def main(argv):
     sys.path.insert(0, ROOT)
     import dotsocp_amd as D
     cases = [parse_case(s) for s in argv[2:]]
-    rows, fams = [], []
+    rows, fams, kernels = [], [], []
     for case in cases:
         family, shape, axis, npos = case_shape(case)
         fams.append(family_on_device(D, shape[axis], axis))
+        kernels.append(kernel_on_device(D, shape, axis))
         rows += measure(case, D.dct_axis)
     for r in rows:
         print(format_row(r))
-    save_rows(argv[1], rows, families=np.array(fams))
+    save_rows(argv[1], rows, families=np.array(fams), kernels=np.array(kernels))
 
 
 if __name__ == "__main__":

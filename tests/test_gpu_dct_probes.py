@@ -20,11 +20,16 @@ in-LDS powers of two (dct_pow2.hip, pow2_launch_axis0 / launch_strided; lp = log
                                                 fewer than 4 * 2^lp = 16 lines (1024)
   (16, 1024, 1), (10, 2048, 1) axis 1; (2, 8, 1024) axis 2                       k_dct_strided_wg<., 1024>: 2 x the tile in
                                                 (80 KB, 160 KB] and at least 4 * 2^lp lines
-pipelined powers of two (lg 7, 9, 11; whole tiles of 8192 doubles, 512 = 2 x 256 of them; every line is checked)
+pipelined powers of two (lg 7 .. 11; whole tiles of 8192 doubles, 512 = 2 x 256 of them, the fewest the launchers take;
+every line is checked; test_power_of_two_pipelined ASSERTS the instance through dotsocp_dct_pass_kernel)
   (128, 32768, 1), (512, 8192, 1), (2048, 2048, 1) axis 0      k_dct_axis0_pipe<., 7 / 9 / 11>, 64 / 16 / 4 lines per tile;
                                                                2048: the quarter / half tables TwQuarter, WwHalf
+  (256, 16384, 1), (1024, 4096, 1) axis 0                      k_dct_axis0_pipe<., 8 / 10>, 32 / 8 lines per tile: the y
+                                                               lengths of the parity-gate grid and of the benchmark grid
   (512, 128, 64), (512, 512, 16), (2048, 2048, 1) axis 1       k_dct_strided_pipe<., 7 / 9 / 11>: n0 a multiple of the tile
-  with DOTSOCP_DCT_PIPE=0 the same shapes: k_dct_axis0_wg (32 / 8 / 4 rows) resp. k_dct_strided_wg<., 1024>
+  (512, 256, 32), (512, 1024, 8) axis 1                        k_dct_strided_pipe<., 8 / 10>, 16 / 4 pairs per tile
+  with DOTSOCP_DCT_PIPE=0 the same shapes: k_dct_axis0_wg (32 / 16 / 8 / 4 / 4 rows) resp. k_dct_strided_wg<., 1024>
+  (asserted too: "pow2-wg")
 two-level powers of two (dct_long.hip: k_long_cols + k_long_rows through the scratch array; n = n1 x n2)
   (4096, 9, 1), (8192, 9, 1) axis 0             64 x 64, 128 x 64: one pair per tile (lP = 0)
   (33, 16384, 1) axis 1                         128 x 128, 17 pairs: lP = 4, two tiles, the second holds one line
@@ -94,6 +99,11 @@ def test_power_of_two_inside_the_lds(case):
 
 @pytest.mark.parametrize("case", P.cases_of("fft1-pipe"), ids=P.case_id)
 def test_power_of_two_pipelined(case):
+    """asserts the instance: the library's own launch decision for this pass on this device (dotsocp_dct_pass_kernel)"""
+    family, shape, axis, _ = P.case_shape(case)
+    kernel = P.kernel_on_device(D, shape, axis)
+    assert kernel == "pow2-pipe", "%s: this device runs the %s kernel along axis %d, not the pipelined one" % (
+        P.case_id(case), kernel, axis)
     _run(case)
 
 
@@ -135,5 +145,7 @@ def test_with_a_switch_of_the_dispatcher(name):
         assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
         rows, extra = P.load_rows(path)
     assert extra["families"] == [family] * len(cases)
+    if name.startswith("dct_pipe_off"):          # the workgroup-wide counterparts of the pipelined instances
+        assert extra["kernels"] == ["pow2-wg"] * len(cases)
     assert len(rows) == 6 * len(cases)
     _judge(rows)

@@ -108,9 +108,7 @@ __global__ void __launch_bounds__(T) k_cdft(const double *src, double *dst, Line
             if (e == 0) {
                 v = make_double2(wk.x * xk.x, wk.x * xk.y);
             } else {
-                const double gar = 0.5 * (wk.x * xk.x + wm.x * xm.x), gai = 0.5 * (wk.y * xk.x - wm.y * xm.x);
-                const double gbr = 0.5 * (wk.x * xk.y + wm.x * xm.y), gbi = 0.5 * (wk.y * xk.y - wm.y * xm.y);
-                v = make_double2(gar - gbi, gai + gbr);
+                v = idct_half(wk, xk, wm, xm);
             }
             if (!RADER) v = cmul(v, c.mul[e]);
             r[c.pos[n + e]] = v;
@@ -124,7 +122,7 @@ __global__ void __launch_bounds__(T) k_cdft(const double *src, double *dst, Line
         }
     }
     __syncthreads();
-    fft_rows_wg(lds, lp, lg, rowStride, tid, T, c.tw);
+    fft_rows<false>(lds, lp, lg, rowStride, BlockTeam<T>{tid}, c.tw);
     // ---- spectrum of the kernel, conjugate ----
     for (int b = tid; b < (P << lg); b += T) {
         double2 *r = lds + (b >> lg) * rowStride;
@@ -140,7 +138,7 @@ __global__ void __launch_bounds__(T) k_cdft(const double *src, double *dst, Line
         r[padi(i)] = make_double2(y.x, -y.y);
     }
     __syncthreads();
-    fft_rows_wg_dit(lds, lp, lg, rowStride, tid, T, c.tw);
+    fft_rows<true>(lds, lp, lg, rowStride, BlockTeam<T>{tid}, c.tw);
     // ---- scatter ----
     for (int b = first; b < total; b += step) {
         int rr, e;
@@ -164,9 +162,7 @@ __global__ void __launch_bounds__(T) k_cdft(const double *src, double *dst, Line
             const double2 vk = cdft_out<RADER>(r, c.pos[2 * n + e], e, c.mul);
             const double2 vm = cdft_out<RADER>(r, c.pos[2 * n + m], m, c.mul);
             const double2 w = c.ww[e];
-            const double ar = 0.5 * (vk.x + vm.x), ai = 0.5 * (vk.y - vm.y);
-            const double br = 0.5 * (vk.y + vm.y), bi = -0.5 * (vk.x - vm.x);
-            o = make_double2(w.x * ar - w.y * ai, w.x * br - w.y * bi);
+            o = dct_split(vk, vm).at_k(w);
         } else {
             o = cdft_out<RADER>(r, c.pos[3 * n + e], makhoul(e, n), c.mul);
         }
@@ -213,8 +209,7 @@ CdftPlan *cdft_plan_create(i64 n64) {
     if (n64 < 48 || n64 > CDFT_MAX_N || (n64 & (n64 - 1)) == 0) return nullptr;
     const int n = (int)n64;
     const bool rader = n == 257;
-    int lg = 0;
-    while ((1 << lg) < (rader ? 256 : 2 * n - 1)) ++lg;
+    const int lg = ceil_log2(rader ? 256 : 2 * n - 1);
     const int M = 1 << lg;
     const long double PI = 3.141592653589793238462643383279502884L;
     CdftPlan *p = new CdftPlan();

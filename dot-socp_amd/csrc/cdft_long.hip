@@ -64,8 +64,7 @@ CdftLongPlan *cdft_long_plan_create(i64 n64) {
     const int n = (int)n64;
     CdftLongPlan *p = new CdftLongPlan();
     p->n = n;
-    p->lg = 0;
-    while (((i64)1 << p->lg) < 2 * n64 - 1) ++p->lg;
+    p->lg = ceil_log2(2 * n64 - 1);
     p->lg2 = p->lg / 2;
     p->lg1 = p->lg - p->lg2;
     const i64 M = (i64)1 << p->lg, m1 = (i64)1 << p->lg1, m2 = (i64)1 << p->lg2;
@@ -198,10 +197,7 @@ __global__ void __launch_bounds__(LONG_THREADS) k_clong_cols(const double *__res
                     if (j == 0) {
                         v = make_double2(wk.x * xk[u].x, wk.x * xk[u].y);
                     } else {
-                        const double2 wm = a.ww[n - j];
-                        const double gar = 0.5 * (wk.x * xk[u].x + wm.x * xm[u].x), gai = 0.5 * (wk.y * xk[u].x - wm.y * xm[u].x);
-                        const double gbr = 0.5 * (wk.x * xk[u].y + wm.x * xm[u].y), gbi = 0.5 * (wk.y * xk[u].y - wm.y * xm[u].y);
-                        v = make_double2(gar - gbi, gai + gbr);
+                        v = idct_half(wk, xk[u], a.ww[n - j], xm[u]);
                     }
                 }
                 v = cmul(v, a.chirp[j]);
@@ -210,7 +206,7 @@ __global__ void __launch_bounds__(LONG_THREADS) k_clong_cols(const double *__res
         }
     }
     __syncthreads();
-    fft_rows_wg(lds, lNR, a.lg1, rowStride, tid, LONG_THREADS, a.tw);
+    fft_rows<false>(lds, lNR, a.lg1, rowStride, BlockTeam<LONG_THREADS>{tid}, a.tw);
     // times exp(-2 pi i j2 k1 / M), to scratch[k1][j2] of this tile (pairs interleaved: the lanes of a row group are adjacent)
     double2 *out = scratch + (((pt << a.lg) + j2) << a.lP) + p;
     for (int k1 = tid >> lNR; k1 < m1; k1 += jstep) {
@@ -256,7 +252,7 @@ __global__ void __launch_bounds__(LONG_THREADS) k_clong_rows(double2 *__restrict
         }
     }
     __syncthreads();
-    fft_rows_wg(lds, lNR, a.lg2, rowStride, tid, LONG_THREADS, a.tw);
+    fft_rows<false>(lds, lNR, a.lg2, rowStride, BlockTeam<LONG_THREADS>{tid}, a.tw);
     // ---- spectrum of the kernel (1 / M folded in), conjugate ----
     for (int b = tid; b < (NR << a.lg2); b += LONG_THREADS) {
         const int r = b >> a.lg2, i = b & (m2 - 1);
@@ -266,7 +262,7 @@ __global__ void __launch_bounds__(LONG_THREADS) k_clong_rows(double2 *__restrict
         *q = make_double2(y.x, -y.y);
     }
     __syncthreads();
-    fft_rows_wg_dit(lds, lNR, a.lg2, rowStride, tid, LONG_THREADS, a.tw);
+    fft_rows<true>(lds, lNR, a.lg2, rowStride, BlockTeam<LONG_THREADS>{tid}, a.tw);
     // ---- store: conj(y[k1][j2]) exp(-2 pi i k1 j2 / M) = conj(y[k1][j2] exp(+2 pi i k1 j2 / M)) ----
     for (int b = tid; b < total; b += LONG_THREADS) {
         const int slot = b >> (a.lP + a.lg2), j2 = (b >> a.lP) & (m2 - 1), p = b & (P - 1);
@@ -328,7 +324,7 @@ __global__ void __launch_bounds__(LONG_THREADS) k_clong_back(const double2 *__re
         }
     }
     __syncthreads();
-    fft_rows_wg(lds, lNR, a.lg1, rowStride, tid, LONG_THREADS, a.tw);
+    fft_rows<false>(lds, lNR, a.lg1, rowStride, BlockTeam<LONG_THREADS>{tid}, a.tw);
     // ---- store: X[j] = conj(row[j1]) w_j for j = j1 m2 + col < n ----
     const i64 La = 2 * (((a.tile0 + pt) << a.lP) + p);
     const bool oka = La < a.map.nLines, okb = La + 1 < a.map.nLines;
@@ -354,10 +350,9 @@ __global__ void __launch_bounds__(LONG_THREADS) k_clong_back(const double2 *__re
             }
             const double2 w = a.ww[j];
             // (Xa[k], Xb[k]) = real(ww[k] * V_{a,b}[k])   (the scatter of k_cdft)
-            const double ar = 0.5 * (vk.x + vm.x), ai = 0.5 * (vk.y - vm.y);
-            const double br = 0.5 * (vk.y + vm.y), bi = -0.5 * (vk.x - vm.x);
-            if (oka) da[j * es] = w.x * ar - w.y * ai;
-            if (okb) db[j * es] = w.x * br - w.y * bi;
+            const double2 o = dct_split(vk, vm).at_k(w);
+            if (oka) da[j * es] = o.x;
+            if (okb) db[j * es] = o.y;
         }
     }
 }

@@ -81,8 +81,7 @@ LongPlan *long_plan_create(i64 n) {
     if (n < 256 || n > DCT_LONG_MAX_N || (n & (n - 1))) return nullptr;
     LongPlan *p = new LongPlan();
     p->n = n;
-    p->lg = 0;
-    while (((i64)1 << p->lg) < n) ++p->lg;
+    p->lg = ceil_log2(n);
     p->lg2 = p->lg / 2;
     p->lg1 = p->lg - p->lg2;
     const i64 n1 = (i64)1 << p->lg1, n2 = (i64)1 << p->lg2;
@@ -191,7 +190,7 @@ __global__ void __launch_bounds__(LONG_THREADS) k_long_cols(const double *__rest
             if (!INVERSE) {
                 row[padi(j1)] = xk[u];
             } else {
-                // G[j] = (ww[j] X[j] + conj(ww[n-j]) X[n-j]) / 2, G[0] = ww[0] X[0]   (idct_combine_wg of dct_pow2.hip);
+                // G[j] = (ww[j] X[j] + conj(ww[n-j]) X[n-j]) / 2, G[0] = ww[0] X[0]   (idct_combine of dct_pow2.hip);
                 // ww[j] = ia[j1] ib[j2], ww[n-j] = (-imag ww[j], -real ww[j])
                 const double2 wk = cmul(a.ta[j1], eb);
                 if (j1 == 0 && j2 == 0) {
@@ -199,15 +198,13 @@ __global__ void __launch_bounds__(LONG_THREADS) k_long_cols(const double *__rest
                     row[0] = make_double2(w0 * xk[u].x, w0 * xk[u].y);
                 } else {
                     const double2 wm = make_double2(-wk.y, -wk.x);
-                    const double gar = 0.5 * (wk.x * xk[u].x + wm.x * xm[u].x), gai = 0.5 * (wk.y * xk[u].x - wm.y * xm[u].x);
-                    const double gbr = 0.5 * (wk.x * xk[u].y + wm.x * xm[u].y), gbi = 0.5 * (wk.y * xk[u].y - wm.y * xm[u].y);
-                    row[padi(j1)] = make_double2(gar - gbi, gai + gbr);
+                    row[padi(j1)] = idct_half(wk, xk[u], wm, xm[u]);
                 }
             }
         }
     }
     __syncthreads();
-    fft_rows_wg(lds, lNR, a.lg1, rowStride, tid, LONG_THREADS, a.tw);
+    fft_rows<false>(lds, lNR, a.lg1, rowStride, BlockTeam<LONG_THREADS>{tid}, a.tw);
     // times exp(-2 pi i j2 k1 / n), to scratch[k1][j2] of this tile (pairs interleaved: the lanes of a row group are adjacent)
     double2 *out = scratch + (((pt << a.lg) + j2) << a.lP) + p;
     for (int k1 = tid >> lNR; k1 < n1; k1 += jstep) {
@@ -269,7 +266,7 @@ __global__ void __launch_bounds__(LONG_THREADS) k_long_rows(const double2 *__res
         }
     }
     __syncthreads();
-    fft_rows_wg(lds, lNR, a.lg2, rowStride, tid, LONG_THREADS, a.tw);
+    fft_rows<false>(lds, lNR, a.lg2, rowStride, BlockTeam<LONG_THREADS>{tid}, a.tw);
     // ---- store: (k2, slot, p) with p, then the slot fastest; a thread keeps its row ----
     const int s = tid & (NR - 1);
     const int p = s & (P - 1), slot = s >> a.lP;
@@ -298,11 +295,10 @@ __global__ void __launch_bounds__(LONG_THREADS) k_long_rows(const double2 *__res
             double2 w = cmul(wa, a.tb[k2]);
             if (k1 == 0 && k2 == 0) w = make_double2(w.x * 0.70710678118654752440, 0.0);
             // (Xa[k], Xb[k]) = real(ww[k] * V_{a,b}[k])   (dct_post of dct_pow2.hip)
-            const double ar = 0.5 * (vk.x + vm.x), ai = 0.5 * (vk.y - vm.y);
-            const double br = 0.5 * (vk.y + vm.y), bi = -0.5 * (vk.x - vm.x);
+            const double2 o = dct_split(vk, vm).at_k(w);
             const i64 e = (i64)k1 + ((i64)k2 << a.lg1);
-            if (oka) da[e * es] = w.x * ar - w.y * ai;
-            if (okb) db[e * es] = w.x * br - w.y * bi;
+            if (oka) da[e * es] = o.x;
+            if (okb) db[e * es] = o.y;
         }
     }
 }

@@ -1,6 +1,7 @@
 // LDS FFT building blocks shared by the power-of-two DCT kernels (dct_pow2.hip) and the convolution-based DFT
 // (cdft.hip): line addressing, the bank-spreading row layout, radix-2 register groups (decimation in frequency
-// and in time) and the per-wave / per-workgroup drivers over them.
+// and in time), the two drivers over them (fft_rows: sizes known at run time, fft_tile: at compile time), the arithmetic
+// on a pair (k, n - k) of a DCT's spectrum, and the integer logarithms of the host side.
 #pragma once
 #include "device_utils.h"
 
@@ -58,14 +59,17 @@ __device__ __forceinline__ double2 mul_w16(double2 d, int t) {
     }
 }
 
-// One group of LR radix-2 decimation-in-frequency stages done in registers: the lane owns the
-// R = 2^LR elements base + m * (S/R) of one sub-transform of span S = 2^sl and performs the
-// butterflies of spans S, S/2, ..., S/2^(LR-1) on them (same data flow as LR passes of the
-// textbook in-place radix-2 DIF, so the output order is plain bit reversal).
+// One group of LR radix-2 stages done in registers: the lane owns the R = 2^LR elements base + m * (S/R) of one
+// sub-transform of span S = 2^sl and performs the butterflies of LR spans on them.
+//   DIT = false, decimation in frequency: spans S, S/2, ..., S/2^(LR-1), the twiddle applied after the subtraction (same
+//                data flow as LR passes of the textbook in-place radix-2 DIF, so the output order is plain bit reversal)
+//   DIT = true,  decimation in time: the same element set, spans S/2^(LR-1), ..., S/2, S in INCREASING order with the
+//                twiddle applied before the add / subtract -- bit-reversed input, natural-order output.  Used where the
+//                spectrum is needed in place in natural order (fused t-axis solve).
 // LES > 0: the rows of a tile are interleaved element by element (element p of row r at (padi(p) << LES) + r, `row`
 // = tile + r) -- the image an LDS-DMA piece leaves when each lane fetches one (pair, k) element; LES = 0: plain rows
-template <int LR, int LES = 0, class TW = const double2 *>
-__device__ __forceinline__ void dif_group(double2 *__restrict__ row, int sl, int bidx, int lg, TW tw) {
+template <bool DIT, int LR, int LES = 0, class TW = const double2 *>
+__device__ __forceinline__ void fft_group(double2 *__restrict__ row, int sl, int bidx, int lg, TW tw) {
     constexpr int R = 1 << LR;
     const int strideLog = sl - LR;
     const int j = bidx & ((1 << strideLog) - 1);
@@ -75,164 +79,151 @@ __device__ __forceinline__ void dif_group(double2 *__restrict__ row, int sl, int
     for (int m = 0; m < R; ++m) x[m] = row[padi(base + (m << strideLog)) << LES];
     const int tj = j << (lg - sl);   // j * N / S
 #pragma unroll
-    for (int u = 0; u < LR; ++u) {
+    for (int i = 0; i < LR; ++i) {
+        const int u = DIT ? LR - 1 - i : i;
         const int hm = R >> (u + 1);
         const double2 bu = tw[tj << u];
 #pragma unroll
         for (int m = 0; m < R; ++m) {
             if ((m / hm) & 1) continue;
             const int mm = m % hm;
-            const double2 a = x[m], b = x[m + hm];
-            x[m] = make_double2(a.x + b.x, a.y + b.y);
-            double2 d = make_double2(a.x - b.x, a.y - b.y);
-            d = mul_w16(d, (mm << u) * (16 / R));
-            x[m + hm] = cmul(d, bu);
+            if constexpr (!DIT) {
+                const double2 a = x[m], b = x[m + hm];
+                x[m] = make_double2(a.x + b.x, a.y + b.y);
+                double2 d = make_double2(a.x - b.x, a.y - b.y);
+                d = mul_w16(d, (mm << u) * (16 / R));
+                x[m + hm] = cmul(d, bu);
+            } else {
+                const double2 a = x[m];
+                const double2 t = cmul(mul_w16(x[m + hm], (mm << u) * (16 / R)), bu);
+                x[m] = make_double2(a.x + t.x, a.y + t.y);
+                x[m + hm] = make_double2(a.x - t.x, a.y - t.y);
+            }
         }
     }
 #pragma unroll
     for (int m = 0; m < R; ++m) row[padi(base + (m << strideLog)) << LES] = x[m];
-}
-
-// FFT of the `nrows` = 2^lrw complex rows (length n = 2^lg) owned by the CALLING WAVE, in LDS:
-// natural order in, bit-reversed order out; ceil(lg/4) register groups with a wave-level LDS
-// hand-off after each (no workgroup barrier).
-__device__ __forceinline__ void fft_rows_wave(double2 *rows, int lrw, int lg, int rowStride, int lane,
-                                              const double2 *__restrict__ tw) {
-    const int nst = (lg + 3) >> 2;
-    const int baseBits = lg / nst, extra = lg % nst;
-    int sl = lg;
-    for (int st = 0; st < nst; ++st) {
-        const int lr = baseBits + (st < extra ? 1 : 0);
-        const int lpr = lg - lr;                        // log2(butterflies per row)
-        const int total = 1 << (lrw + lpr);
-        for (int b = lane; b < total; b += 64) {
-            double2 *r = rows + (b >> lpr) * rowStride;
-            const int bidx = b & ((1 << lpr) - 1);
-            switch (lr) {
-                case 4: dif_group<4>(r, sl, bidx, lg, tw); break;
-                case 3: dif_group<3>(r, sl, bidx, lg, tw); break;
-                case 2: dif_group<2>(r, sl, bidx, lg, tw); break;
-                default: dif_group<1>(r, sl, bidx, lg, tw); break;
-            }
-        }
-        sl -= lr;
-        wave_lds_sync();
-    }
-}
-
-// Decimation-in-time twin of dif_group: same element set (base + m * S/R), the butterflies of spans S/2^(LR-1),
-// ..., S/2, S in INCREASING order with the twiddle applied before the add / subtract -- bit-reversed input,
-// natural-order output.  Used where the spectrum is needed in place in natural order (fused t-axis solve).
-template <int LR, int LES = 0, class TW = const double2 *>
-__device__ __forceinline__ void dit_group(double2 *__restrict__ row, int sl, int bidx, int lg, TW tw) {
-    constexpr int R = 1 << LR;
-    const int strideLog = sl - LR;
-    const int j = bidx & ((1 << strideLog) - 1);
-    const int base = ((bidx >> strideLog) << sl) + j;
-    double2 x[R];
-#pragma unroll
-    for (int m = 0; m < R; ++m) x[m] = row[padi(base + (m << strideLog)) << LES];
-    const int tj = j << (lg - sl);   // j * N / S
-#pragma unroll
-    for (int u = LR - 1; u >= 0; --u) {
-        const int hm = R >> (u + 1);
-        const double2 bu = tw[tj << u];
-#pragma unroll
-        for (int m = 0; m < R; ++m) {
-            if ((m / hm) & 1) continue;
-            const int mm = m % hm;
-            const double2 a = x[m];
-            const double2 t = cmul(mul_w16(x[m + hm], (mm << u) * (16 / R)), bu);
-            x[m] = make_double2(a.x + t.x, a.y + t.y);
-            x[m + hm] = make_double2(a.x - t.x, a.y - t.y);
-        }
-    }
-#pragma unroll
-    for (int m = 0; m < R; ++m) row[padi(base + (m << strideLog)) << LES] = x[m];
-}
-
-// FFT of the calling wave's rows, bit-reversed order in, natural order out (the register groups of
-// fft_rows_wave in reverse order).
-__device__ __forceinline__ void fft_rows_wave_dit(double2 *rows, int lrw, int lg, int rowStride, int lane,
-                                                  const double2 *__restrict__ tw) {
-    const int nst = (lg + 3) >> 2;
-    const int baseBits = lg / nst, extra = lg % nst;
-    int sl = 0;
-    for (int st = nst - 1; st >= 0; --st) {
-        const int lr = baseBits + (st < extra ? 1 : 0);
-        sl += lr;
-        const int lpr = lg - lr;
-        const int total = 1 << (lrw + lpr);
-        for (int b = lane; b < total; b += 64) {
-            double2 *r = rows + (b >> lpr) * rowStride;
-            const int bidx = b & ((1 << lpr) - 1);
-            switch (lr) {
-                case 4: dit_group<4>(r, sl, bidx, lg, tw); break;
-                case 3: dit_group<3>(r, sl, bidx, lg, tw); break;
-                case 2: dit_group<2>(r, sl, bidx, lg, tw); break;
-                default: dit_group<1>(r, sl, bidx, lg, tw); break;
-            }
-        }
-        wave_lds_sync();
-    }
 }
 
 // Makhoul reordering v[j] = x[2j], v[n-1-j] = x[2j+1] (mirt_dctn.m:71) -- also the output
 // reordering of the inverse (mirt_idctn.m:71-73,120).
 __device__ __forceinline__ int makhoul(int k, int n) { return (k & 1) ? (n - 1 - (k >> 1)) : (k >> 1); }
 
-template <bool RAWB = false>
-__device__ __forceinline__ void fft_rows_wg(double2 *rows, int lrows, int lg, int rowStride, int t, int T,
-                                            const double2 *__restrict__ tw) {
+// ---------------------------------------------------------------------------------------------
+// Drivers over the register groups.  A TEAM is the set of threads that shares the rows: its member t is the calling
+// thread's index in it, T the thread count, sync() the hand-off after every register group.
+//   WaveTeam      one wavefront: DS operations of a wave execute in order, draining them is all the hand-off needed
+//   BlockTeam<T>  the workgroup, __syncthreads()
+//   PipeTeam<T>   the workgroup, lds_barrier(): waits for LDS traffic only, so that the global loads and stores of the
+//                 pipelined kernels stay in flight across it
+// ---------------------------------------------------------------------------------------------
+enum { SYNC_WAVE, SYNC_BLOCK, SYNC_LDS };
+template <int NT, int SYNC>
+struct Team {
+    int t;
+    static constexpr int T = NT;
+    static __device__ __forceinline__ void sync() {
+        if constexpr (SYNC == SYNC_WAVE) wave_lds_sync();
+        else if constexpr (SYNC == SYNC_BLOCK) __syncthreads();
+        else lds_barrier();
+    }
+};
+using WaveTeam = Team<64, SYNC_WAVE>;
+template <int T> using BlockTeam = Team<T, SYNC_BLOCK>;
+template <int T> using PipeTeam = Team<T, SYNC_LDS>;
+
+// FFT of the 2^lrows complex rows (length n = 2^lg, rowStride apart) that the team shares, in LDS: ceil(lg/4) register
+// groups dealt round-robin to the team's threads, a hand-off after each.  DIT = false: natural order in, bit-reversed
+// order out; DIT = true: the same groups in reverse order, bit-reversed order in, natural order out.
+template <bool DIT, class TEAM, class TW = const double2 *>
+__device__ __forceinline__ void fft_rows(double2 *rows, int lrows, int lg, int rowStride, TEAM tm, TW tw) {
     const int nst = (lg + 3) >> 2;
     const int baseBits = lg / nst, extra = lg % nst;
-    int sl = lg;
-    for (int st = 0; st < nst; ++st) {
+    int sl = DIT ? 0 : lg;
+    for (int st = DIT ? nst - 1 : 0; DIT ? st >= 0 : st < nst; st += DIT ? -1 : 1) {
         const int lr = baseBits + (st < extra ? 1 : 0);
-        const int lpr = lg - lr;
+        if (DIT) sl += lr;
+        const int lpr = lg - lr;                        // log2(groups per row)
         const int total = 1 << (lrows + lpr);
-        for (int b = t; b < total; b += T) {
+        for (int b = tm.t; b < total; b += TEAM::T) {
             double2 *r = rows + (b >> lpr) * rowStride;
             const int bidx = b & ((1 << lpr) - 1);
             switch (lr) {
-                case 4: dif_group<4>(r, sl, bidx, lg, tw); break;
-                case 3: dif_group<3>(r, sl, bidx, lg, tw); break;
-                case 2: dif_group<2>(r, sl, bidx, lg, tw); break;
-                default: dif_group<1>(r, sl, bidx, lg, tw); break;
+                case 4: fft_group<DIT, 4>(r, sl, bidx, lg, tw); break;
+                case 3: fft_group<DIT, 3>(r, sl, bidx, lg, tw); break;
+                case 2: fft_group<DIT, 2>(r, sl, bidx, lg, tw); break;
+                default: fft_group<DIT, 1>(r, sl, bidx, lg, tw); break;
             }
         }
-        sl -= lr;
-        if (RAWB) lds_barrier(); else __syncthreads();
+        if (!DIT) sl -= lr;
+        TEAM::sync();
     }
 }
 
-// Decimation-in-time twin of fft_rows_wg: bit-reversed order in, natural order out.
-template <bool RAWB = false>
-__device__ __forceinline__ void fft_rows_wg_dit(double2 *rows, int lrows, int lg, int rowStride, int t, int T,
-                                                const double2 *__restrict__ tw) {
-    const int nst = (lg + 3) >> 2;
-    const int baseBits = lg / nst, extra = lg % nst;
-    int sl = 0;
-    for (int st = nst - 1; st >= 0; --st) {
-        const int lr = baseBits + (st < extra ? 1 : 0);
-        sl += lr;
-        const int lpr = lg - lr;
-        const int total = 1 << (lrows + lpr);
-        for (int b = t; b < total; b += T) {
-            double2 *r = rows + (b >> lpr) * rowStride;
-            const int bidx = b & ((1 << lpr) - 1);
-            switch (lr) {
-                case 4: dit_group<4>(r, sl, bidx, lg, tw); break;
-                case 3: dit_group<3>(r, sl, bidx, lg, tw); break;
-                case 2: dit_group<2>(r, sl, bidx, lg, tw); break;
-                default: dit_group<1>(r, sl, bidx, lg, tw); break;
-            }
+// The same register groups for a length and a tile known at compile time (same plan, same arithmetic), lds_barrier()
+// after each.  RS > 0: 2^LROWS plain rows, RS apart.  RS = 0: a pair-interleaved tile (LES = LROWS above): item b =
+// (row b % rows, group b / rows), so the lanes of a wave sweep the rows of one element first -- consecutive addresses.
+template <bool DIT, int LG, int LROWS, int T, int RS = 0, int I = 0, int SL = (DIT ? 0 : LG), class TW = const double2 *>
+__device__ __forceinline__ void fft_tile(double2 *tile, int t, TW tw) {
+    constexpr int NST = (LG + 3) >> 2;
+    constexpr int BASEB = LG / NST, EXTRA = LG % NST;
+    if constexpr (I < NST) {
+        constexpr int ST = DIT ? NST - 1 - I : I;
+        constexpr int LR = BASEB + (ST < EXTRA ? 1 : 0);
+        constexpr int S = DIT ? SL + LR : SL;           // log2 of the span this group works on
+        constexpr int LPR = LG - LR;
+        constexpr int TOTAL = 1 << (LROWS + LPR);
+#pragma unroll
+        for (int b = t; b < TOTAL; b += T) {
+            if constexpr (RS == 0) fft_group<DIT, LR, LROWS>(tile + (b & ((1 << LROWS) - 1)), S, b >> LROWS, LG, tw);
+            else fft_group<DIT, LR>(tile + (b >> LPR) * RS, S, b & ((1 << LPR) - 1), LG, tw);
         }
-        if (RAWB) lds_barrier(); else __syncthreads();
+        lds_barrier();
+        fft_tile<DIT, LG, LROWS, T, RS, I + 1, (DIT ? S : S - LR)>(tile, t, tw);
     }
 }
 
-// ---- host side: the dynamic-LDS limit of the kernels built on these rows ----
+// ---------------------------------------------------------------------------------------------
+// The arithmetic on a pair (k, n - k) of the spectrum of two real lines (a in the real, b in the imaginary part), shared
+// by every DCT built on a complex FFT here.  These files contract a * b + c, so every expression below is the one its
+// callers used to spell out, term for term: a regrouped sum rounds differently.
+// (pfa.hip keeps its own pfa_pre / pfa_post: it compiles with contraction off and folds the signs so that the two halves
+// of a pair share their products -- gk = (gar - gbi, gai + gbr), gm = (gar + gbi, gbr - gai) -- which is a different
+// expression tree from the two idct_half calls below and rounds differently once contracted.)
+// ---------------------------------------------------------------------------------------------
+// Inverse pre-processing: G[k] = (ww[k] X[k] + conj(ww[n-k]) X[n-k]) / 2, so that fft(G) = real(fft(ww .* X))
+// (mirt_idctn.m:109,119-120), for X = Xa + i Xb.  G[n-k] is the same call with the roles of k and n - k swapped.
+__device__ __forceinline__ double2 idct_half(double2 wk, double2 xk, double2 wm, double2 xm) {
+    const double gar = 0.5 * (wk.x * xk.x + wm.x * xm.x), gai = 0.5 * (wk.y * xk.x - wm.y * xm.x);
+    const double gbr = 0.5 * (wk.x * xk.y + wm.x * xm.y), gbi = 0.5 * (wk.y * xk.y - wm.y * xm.y);
+    return make_double2(gar - gbi, gai + gbr);
+}
+
+// Forward post-processing: the spectra of the two lines from V = fft(va + i vb),
+// V_a = (V[k] + conj(V[n-k])) / 2 = ar + i ai, V_b = (V[k] - conj(V[n-k])) / (2i) = br + i bi, and
+// (Xa[k], Xb[k]) = real(ww[k] V_{a,b}[k]), (Xa[n-k], Xb[n-k]) = real(ww[n-k] conj(V_{a,b}[k]))   (mirt_dctn.m:130)
+struct DctSplit {
+    double ar, ai, br, bi;
+    __device__ __forceinline__ double2 at_k(double2 w) const { return make_double2(w.x * ar - w.y * ai, w.x * br - w.y * bi); }
+    __device__ __forceinline__ double2 at_m(double2 w) const { return make_double2(w.x * ar + w.y * ai, w.x * br + w.y * bi); }
+};
+__device__ __forceinline__ DctSplit dct_split(double2 vk, double2 vm) {
+    return DctSplit{0.5 * (vk.x + vm.x), 0.5 * (vk.y - vm.y), 0.5 * (vk.y + vm.y), -0.5 * (vk.x - vm.x)};
+}
+
+// ---- host side ----
+constexpr int floor_log2(i64 v) {
+    int l = 0;
+    while (((i64)2 << l) <= v) ++l;
+    return l;
+}
+constexpr int ceil_log2(i64 v) {
+    int l = 0;
+    while (((i64)1 << l) < v) ++l;
+    return l;
+}
+
+// the dynamic-LDS limit of the kernels built on these rows
 #define DCT_LDS_MAX (160 * 1024)
 
 template <class K>

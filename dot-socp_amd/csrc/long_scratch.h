@@ -46,18 +46,12 @@ struct LongScratch {
     }
 };
 
-inline int floor_log2_i(i64 v) {
-    int l = 0;
-    while (((i64)2 << l) <= v) ++l;
-    return l;
-}
-
 // log2 of the complex rows of length m a workgroup stages: what the LDS budget holds, at most LONG_MAX_ROWS
 inline int long_log2_rows(int m) {
     i64 rows = (i64)(LONG_LDS_BUDGET / ((size_t)row_stride(m) * sizeof(double2)));
     if (rows > LONG_MAX_ROWS) rows = LONG_MAX_ROWS;
     if (rows < 2) rows = 2;
-    return floor_log2_i(rows);
+    return floor_log2(rows);
 }
 
 // exp(-2 pi i num / den), the index reduced exactly in integers

@@ -94,6 +94,18 @@ class Dual(ctypes.Structure):
                 ("gap0_max", dbl), ("gap0_min", dbl), ("gap0_mean", dbl), ("map_cost_bwd", dbl)]
 
 
+class UpperOpts(ctypes.Structure):
+    """dotsocp_upper_opts"""
+    _fields_ = [("eps_h2", dbl), ("max_sweeps", i64), ("defect_tol", dbl), ("start", ctypes.c_int)]
+
+
+class Upper(ctypes.Structure):
+    """dotsocp_upper"""
+    _fields_ = [("n_nodes", i64), ("sweeps", i64), ("zero0", i64), ("zero1", i64), ("nonfinite", i64),
+                ("eps", dbl), ("mass0", dbl), ("mass1", dbl), ("upper", dbl), ("cost_kept", dbl), ("cost_fill", dbl),
+                ("kept", dbl), ("fill", dbl), ("defect_first", dbl), ("defect_last", dbl)]
+
+
 class ImageOpts(ctypes.Structure):
     """dotsocp_image_opts"""
     _fields_ = [("ny", i64), ("nx", i64), ("layout", ctypes.c_int), ("reverse", ctypes.c_int), ("lower_bound", dbl)]
@@ -157,6 +169,10 @@ SYMBOLS = {
     "dotsocp_render_evolution": (ctypes.c_int, [vp, vp, vp, ctypes.POINTER(RenderOpts), vp, vp, vp, vp, vp, vp, vp,
                                                 ctypes.POINTER(RenderInfo)]),
     "dotsocp_dual_bound": (ctypes.c_int, [vp, vp, vp, ctypes.POINTER(Dual), vp, vp, vp, vp]),
+    "dotsocp_plan_bound": (ctypes.c_int, [vp, vp, i64, i64, vp, ctypes.POINTER(UpperOpts), ctypes.POINTER(Upper), vp, vp, vp, vp,
+                                          vp, vp, ctypes.c_int]),
+    "dotsocp_upper_bound": (ctypes.c_int, [vp, vp, vp, vp, ctypes.POINTER(UpperOpts), ctypes.POINTER(Upper), vp, vp, vp, vp,
+                                           vp, vp]),
     "dotsocp_jump_next_level": (ctypes.c_int, [vp, vp]),
     "dotsocp_finish": (ctypes.c_int, [vp, ctypes.POINTER(Result)]),
     "dotsocp_get_history": (ctypes.c_int, [vp, vp, vp, vp, vp]),

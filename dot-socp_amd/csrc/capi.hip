@@ -430,6 +430,19 @@ int dotsocp_dual_bound(dotsocp_ctx *ctx, const double *rho0, const double *rho1,
     return ctx->s.dual_bound(rho0, rho1, res, H, B, arg_fwd, arg_bwd);
 }
 
+int dotsocp_plan_bound(const double *rho0, const double *rho1, dotsocp_i64 ny, dotsocp_i64 nx, const double *f_start,
+                       const dotsocp_upper_opts *o, dotsocp_upper *res, double *f, double *g, double *E, double *er, double *ec,
+                       double *defects, int device) {
+    return plan_bound(rho0, rho1, ny, nx, f_start, o, res, f, g, E, er, ec, defects, device);
+}
+
+int dotsocp_upper_bound(dotsocp_ctx *ctx, const double *rho0, const double *rho1, const double *f_start,
+                        const dotsocp_upper_opts *o, dotsocp_upper *res, double *f, double *g, double *E, double *er, double *ec,
+                        double *defects) {
+    CTX_OR_FAIL();
+    return ctx->s.upper_bound(rho0, rho1, f_start, o, res, f, g, E, er, ec, defects);
+}
+
 int dotsocp_render_evolution(dotsocp_ctx *ctx, const double *rho0, const double *rho1, const dotsocp_render_opts *opts,
                              const dotsocp_i64 *frame_nodes, const double *levels, const unsigned char *lut,
                              const unsigned char *barrier, unsigned char *image, double *mvx, double *mvy,
@@ -484,7 +497,7 @@ int dotsocp_kernel_time(dotsocp_ctx *ctx, const char *name, double *avg_ms, dots
                                           "cone_fused_a", "cone_fused_b", "materialise", "comm",
                                           "interp", "acc_cone", "acc_gather", "qstep_first", "transpose", "cone_carry", "qcone",
                                           "velocity_layer", "advect", "deposit", "frame_l1", "advect_path", "map_final",
-                                          "hl_pass_x", "hl_pass_y", "hl_reduce"};
+                                          "hl_pass_x", "hl_pass_y", "hl_reduce", "sl_pass_x", "sl_pass_y", "sl_node"};
     for (int i = 0; i < PH_COUNT; ++i)
         if (strcmp(name, names[i]) == 0) {
             const i64 n = ctx->s.phase_launches[i];

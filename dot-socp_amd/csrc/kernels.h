@@ -253,6 +253,50 @@ struct HlReduceArgs {
 i64 hl_blocks(i64 nodes);
 int launch_hl_reduce(const HlReduceArgs &a, double *sums /* HS_COUNT */, hipStream_t st);
 
+// ---------------- softlax.hip: soft Hopf-Lax transform and the node kernels of the upper bound (dotsocp_plan_bound) ----------------
+// One soft pass over `lines` lines of n nodes (include/dotsocp.h, "Soft pass"): out[j] = m - eps log(s), mean[j] = q / s.  The
+// layouts, tiles and chunks are those of launch_hl_pass_y / _x (HL_YOUT, HL_XOUT, DOTSOCP_HL_CHUNK); pm: the prior mean in
+// the layout of `in`, or nullptr (zeros; the x pass has none).  in, out and mean are distinct arrays.
+int launch_sl_pass_y(const double *in, const double *pm, double *out, double *mean, i64 n, i64 lines, i64 pitch, double eps,
+                     hipStream_t st);
+int launch_sl_pass_x(const double *in, double *out, double *mean, i64 n, i64 lines, i64 pitch, double eps, hipStream_t st);
+// All node kernels: one thread per node of an unpitched layer of n = ny * nx nodes in memory order, workgroups of 256
+// (hl_blocks(n) of them); sums by the tree of launch_hl_reduce (partials: [rows][hl_blocks(n)]).
+enum { SM_M0 = 0, SM_M1, SM_COUNT };                            // k_sl_mass: rows of the sums
+enum { SC_ZERO0 = 0, SC_ZERO1, SC_BAD, SC_NONFINITE, SC_COUNT };   // 64-bit counters (zeroed before the first launch)
+enum { SS_KEPT = 0, SS_COST, SS_R0, SS_R1X, SS_R1Y, SS_R2, SS_C0, SS_C1X, SS_C1Y, SS_C2, SS_COUNT };     // k_sl_final
+// sums[SM_COUNT] <- the masses; counts: entries == 0 of rho0 / rho1, entries of either that are negative or not finite
+int launch_sl_mass(const double *rho0, const double *rho1, i64 n, double *partials, double *sums, unsigned long long *counts,
+                   hipStream_t st);
+// a = rho0 / m0, b = rho1 / m1, la = -(eps log a), lb likewise; f = 0.0 (mode 0), -src (1) or src (2), non-finite entries
+// counted (SC_NONFINITE) and replaced by 0.0; in = la - f
+struct SlInitArgs {
+    const double *rho0, *rho1, *src;
+    double *a, *b, *la, *lb, *f, *in;
+    i64 n;
+    double m0, m1, eps;
+    int mode;
+    unsigned long long *counts;
+};
+int launch_sl_init(const SlInitArgs &a, hipStream_t st);
+// x = v < x ? v : x (v != nullptr); in = l - x
+int launch_sl_minsub(const double *l, double *x, const double *v, double *in, i64 n, hipStream_t st);
+// *sum <- sum_i (a_i > 0 ? a_i |exp((f_i - v_i) ieps) - 1| : 0); f = v; in = la - f
+int launch_sl_defect(const double *a, const double *la, double *f, const double *v, double *in, i64 n, double ieps,
+                     double *partials, double *sum, hipStream_t st);
+// the masses of the kept plan, what is missing and the ten sums (include/dotsocp.h, "Rounding"): f = f', fh = f^, g = g', gt = g~
+struct SlFinalArgs {
+    const double *a, *b, *f, *fh, *g, *gt, *E;
+    double *er, *ec;
+    i64 ny, nx;
+    double hx, hy, ieps;            // hx = 0 for a 1-D line
+    double *partials;               // [SS_COUNT][hl_blocks(ny * nx)]
+};
+int launch_sl_final(const SlFinalArgs &a, double *sums /* SS_COUNT */, hipStream_t st);
+// dotsocp_plan_bound behind the C ABI (solver_upper.hip)
+int plan_bound(const double *rho0, const double *rho1, i64 ny, i64 nx, const double *f_start, const dotsocp_upper_opts *o,
+               dotsocp_upper *res, double *f, double *g, double *E, double *er, double *ec, double *defects, int device);
+
 // ---------------- render.hip: pictures of the density evolution (dotsocp_render_evolution) ----------------
 // Slots of the 64-bit counters of the range pass (zeroed before the launch): max / min of the finite unmasked rho as the
 // keys of the report (max: report_key_decode(k, false, .), min: (k, true, .); 0: no value), then two plain counts

@@ -162,7 +162,8 @@ void pencil_range(i64 plane, int world, int j, i64 *l0, i64 *l1);
 
 enum Phase { PH_RHS = 0, PH_POISSON, PH_PROJ, PH_QSTEP, PH_BETA, PH_KKT, PH_FUSED_A, PH_FUSED_B, PH_MATERIALISE,
              PH_COMM, PH_INTERP, PH_ACC_CONE, PH_ACC_GATHER, PH_QSTEP0, PH_TRANSPOSE, PH_CONE_CARRY, PH_QCONE, PH_VELOCITY, PH_ADVECT,
-             PH_DEPOSIT, PH_FRAME_L1, PH_ADVECT_PATH, PH_MAP_FINAL, PH_HL_PASS_X, PH_HL_PASS_Y, PH_HL_REDUCE, PH_COUNT };
+             PH_DEPOSIT, PH_FRAME_L1, PH_ADVECT_PATH, PH_MAP_FINAL, PH_HL_PASS_X, PH_HL_PASS_Y, PH_HL_REDUCE,
+             PH_SL_PASS_X, PH_SL_PASS_Y, PH_SL_NODE, PH_COUNT };
 
 struct Solver {
     // ================ devices, streams, slabs: solver_slabs.hip ================
@@ -317,6 +318,12 @@ struct Solver {
     // Hopf-Lax transforms of phi's first and last node layer and the sums of the Kantorovich dual (hopflax.hip), on the first
     // slab's device; H, B (ny x nx doubles), arg_fwd, arg_bwd (ny x nx ints): host, each may be NULL
     int dual_bound(const double *rho0, const double *rho1, dotsocp_dual *res, double *H, double *B, int *arg_fwd, int *arg_bwd);
+
+    // ================ the upper bound on W2^2: solver_upper.hip ================
+    // Sinkhorn sweeps of soft Hopf-Lax transforms from phi's first node layer, rounded to a feasible plan (softlax.hip), on
+    // the first slab's device; f_start and the output arrays (ny x nx doubles; defects: max_sweeps): host, each may be NULL
+    int upper_bound(const double *rho0, const double *rho1, const double *f_start, const dotsocp_upper_opts *o, dotsocp_upper *res,
+                    double *f, double *g, double *E, double *er, double *ec, double *defects);
 
     // ================ the inPALM loop and its profiling: solver.hip ================
     // ---- loop state (mirrors solver_socp_inPALM.m:11-135) ----

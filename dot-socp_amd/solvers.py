@@ -239,6 +239,20 @@ class InPALMContext:
         capi.check(capi.lib().dotsocp_dual_bound(self._ctx, capi.fptr(r0), capi.fptr(r1), ctypes.byref(res), *[ptr(a) for a in arr]))
         return from_struct(res, *arr)
 
+    def upper_bound(self, eps_h2=0.25, max_sweeps=50, defect_tol=0.0, start=1, f_start=None, arrays=False):
+        """An upper bound on W2^2 between the node histograms of rho0 and rho1, on the device (dotsocp_upper_bound; upper.py):
+        log-domain Sinkhorn sweeps at the temperature eps_h2 hx hy from f = -phi(t = 0) (start=1), f_start (start=2) or zeros
+        (start=0), rounded to an exactly feasible plan -- valid whatever state the solve is in; with dual_bound() the bracket
+        bound <= W2^2 <= upper.  Returns an upper.UpperBound (upper, cost_kept, cost_fill, kept, fill, sweeps, the defects of
+        the first and last sweep, ...); arrays=True adds f, g (the scaled-down potentials), E, er, ec and defects.  Call after
+        finish(); unweighted contexts only."""
+        from . import upper as U
+        m = self.model
+        shp = (int(m.nx),) if not hasattr(m, "ny") else (int(m.ny), int(m.nx))
+        r0, r1 = self._rho_ends()
+        return U.device_call(lambda *a: capi.lib().dotsocp_upper_bound(self._ctx, *a), r0, r1, shp, eps_h2, max_sweeps,
+                             defect_tol, start, f_start, arrays)
+
     def render(self, frames=None, num_frame=6, mode="imshow", nlevels=128, lut=None, barrier=None, vmax=None, arrows=False,
                barrier_index=255, levels=None):
         """Pictures of the density evolution on the device (dotsocp_render_evolution; render.py): uint8 frames at the nodes
@@ -493,7 +507,7 @@ def _weights_mode(weight, weights, transfer, weighted=True):
 
 
 def _solve_levels(rho0, rho1, nt, levelN, opts, method, dim, weighted, device, barrier=None, transfer="device",
-                  weights=None, report=False, advect=None, push=None, map_report=None, render=None, dual=False):
+                  weights=None, report=False, advect=None, push=None, map_report=None, render=None, dual=False, upper=None):
     """The level loop of solver_dotsocp2d.m:154-250 (dot1d / wdot2d twins): restrict the data to
     levelN grids, solve coarse to fine with warm starts; every solve runs on the device.
     transfer = "device": the state never leaves the GPU -- jump_nextLevel and the output recovery run there
@@ -517,7 +531,10 @@ def _solve_levels(rho0, rho1, nt, levelN, opts, method, dim, weighted, device, b
     InPALMContext.map_report_from_nodes() -- what the map realised by the flow costs and how straight and steady its paths
     are -- asked of the last level's context; output["map_report"] holds its result.  Needs transfer="device".
     dual = True: the last level's context is asked for the dual lower bound on W2^2 (InPALMContext.dual_bound(), dual.py);
-    output["dual"] holds it.  Needs transfer="device"; a weighted context refuses (capi.DotsocpError)."""
+    output["dual"] holds it.  Needs transfer="device"; a weighted context refuses (capi.DotsocpError).
+    upper = dict(eps_h2=..., max_sweeps=..., defect_tol=...): the keyword arguments of InPALMContext.upper_bound() -- the
+    upper end of the bracket around W2^2 -- asked of the last level's context; output["upper"] holds its result.  Needs
+    transfer="device"; a weighted context refuses."""
     from . import multilevel as ML
     from .examples import ensure_barrier_validity
     if not (isinstance(levelN, (int, np.integer)) and levelN >= 1):
@@ -534,6 +551,8 @@ def _solve_levels(rho0, rho1, nt, levelN, opts, method, dim, weighted, device, b
         raise ValueError("map_report= needs transfer='device' (the particles move through the device-resident state)")
     if dual and transfer != "device":
         raise ValueError("dual=True needs transfer='device' (the bound is taken from the device-resident potential)")
+    if upper is not None and transfer != "device":
+        raise ValueError("upper= needs transfer='device' (the sweeps start from the device-resident potential)")
     if render is not None and transfer != "device":
         raise ValueError("render= needs transfer='device' (the pictures are made from the device-resident state)")
     wopt = _get(opts, "weight") if weighted else None
@@ -618,6 +637,8 @@ def _solve_levels(rho0, rho1, nt, levelN, opts, method, dim, weighted, device, b
                     output["report"] = ctx.report()
                 if dual:
                     output["dual"] = ctx.dual_bound()
+                if upper is not None:
+                    output["upper"] = ctx.upper_bound(**upper)
                 if advect is not None:
                     output["advect"] = ctx.advect(**advect)
                 if push is not None:
@@ -663,42 +684,43 @@ def _solve_levels(rho0, rho1, nt, levelN, opts, method, dim, weighted, device, b
 
 
 def solver_dotsocp2d(rho0, rho1, nt, levelN, opts, method="inPALM", device=0, transfer="device", report=False,
-                     advect=None, push=None, map_report=None, render=None, dual=False):
+                     advect=None, push=None, map_report=None, render=None, dual=False, upper=None):
     """[output, timeML, runHistML, runHist] = solver_dotsocp2d(rho0, rho1, nt, levelN, opts, method)
     socp/dot2d/solver_dotsocp2d.m:1.  report=True: output["report"] = the device-side solution report; advect=dict(x=..., y=...,
     ...): output["advect"] = the particles carried along the solved flow; push=dict(stride=..., frames=..., ...):
     output["push"] = the given density carried along it and deposited at the frame nodes; map_report=dict(stride=..., ...):
     output["map_report"] = cost, straightness and steadiness of the map the flow realises; render=dict(num_frame=..., mode=...,
     arrows=..., ...): output["render"] = uint8 pictures of the density evolution and the arrows of the flux; dual=True:
-    output["dual"] = the dual lower bound on W2^2 from the potential (all six: _solve_levels)."""
+    output["dual"] = the dual lower bound on W2^2 from the potential; upper=dict(eps_h2=..., max_sweeps=..., defect_tol=...):
+    output["upper"] = the upper bound on it from Sinkhorn sweeps rounded to a plan (all seven: _solve_levels)."""
     output, timeML, runHistML, runHist = _solve_levels(rho0, rho1, nt, levelN, opts, method, 2, False, device,
                                                        transfer=transfer, report=report, advect=advect, push=push, map_report=map_report,
-                                                       render=render, dual=dual)
+                                                       render=render, dual=dual, upper=upper)
     if not check_massConservation(output["rho"], 1e-2):
         print("Warning: The mass conservation constraint violation exceeds 0.01")
     return output, timeML, runHistML, runHist
 
 
 def solver_dotsocp1d(rho0, rho1, nt, levelN, opts, method="inPALM", device=0, transfer="device", report=False,
-                     advect=None, push=None, map_report=None, render=None, dual=False):
-    """socp/dot1d/solver_dotsocp1d.m:1.  report, advect, push, map_report, render, dual: as for solver_dotsocp2d."""
+                     advect=None, push=None, map_report=None, render=None, dual=False, upper=None):
+    """socp/dot1d/solver_dotsocp1d.m:1.  report, advect, push, map_report, render, dual, upper: as for solver_dotsocp2d."""
     output, timeML, runHistML, runHist = _solve_levels(rho0, rho1, nt, levelN, opts, method, 1, False, device,
                                                        transfer=transfer, report=report, advect=advect, push=push, map_report=map_report,
-                                                       render=render, dual=dual)
+                                                       render=render, dual=dual, upper=upper)
     if not check_massConservation(output["rho"], 1e-2):
         print("Warning: The mass conservation constraint violation exceeds 0.01")
     return output, timeML, runHistML, runHist
 
 
 def solver_wdotsocp2d(rho0, rho1, nt, levelN, opts, method="inPALM", barrier=None, device=0, transfer="device",
-                      weights=None, report=False, advect=None, push=None, map_report=None, render=None, dual=False):
+                      weights=None, report=False, advect=None, push=None, map_report=None, render=None, dual=False, upper=None):
     """socp/wdot2d/solver_wdotsocp2d.m:1.  opts["weight"]: the Nq array, or a SpaceWeight (examples.py); weights:
     where the levels' weights are made, "host" or "device" (_solve_levels); report, advect, push, map_report, render: as for
-    solver_dotsocp2d (render: `barrier` is the default mask of the pictures; dual=True raises the library's refusal: the
-    weighted cost is not the Euclidean one)."""
+    solver_dotsocp2d (render: `barrier` is the default mask of the pictures; dual=True and upper= raise the library's refusal:
+    the weighted cost is not the Euclidean one)."""
     output, timeML, runHistML, runHist = _solve_levels(rho0, rho1, nt, levelN, opts, method, 2, True, device,
                                                        barrier=barrier, transfer=transfer, weights=weights, report=report,
-                                                       advect=advect, push=push, map_report=map_report, render=render, dual=dual)
+                                                       advect=advect, push=push, map_report=map_report, render=render, dual=dual, upper=upper)
     if not check_massConservation(output["rho"], 1e-2):
         print("Warning: The tolerance of mass conservation constraint is under 0.01")
     return output, timeML, runHistML, runHist

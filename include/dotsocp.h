@@ -554,6 +554,74 @@ typedef struct {
 int dotsocp_dual_bound(dotsocp_ctx *ctx, const double *rho0, const double *rho1, dotsocp_dual *res, double *H, double *B,
                        int *arg_fwd, int *arg_bwd);
 
+/* An upper bound on the same quantity, so that bound <= W2^2(a, b) <= upper brackets it with both ends certified: a few
+ * log-domain Sinkhorn sweeps for the cost c(x, y) = |x - y|^2 / 2 at a temperature eps of a fraction of h^2, started from the
+ * solve's own potential, rounded to an exactly feasible plan by the scheme of Altschuler, Weed and Rigollet.  The Gaussian
+ * kernel factorises over the axes, so one Sinkhorn update is the soft-min version of the two min-plus passes above -- a
+ * log-sum-exp in the place of the min -- and the row masses, the column masses and the cost sum P c of the plan are node sums
+ * of such transforms: no n x n object exists.  What is certified is again the discrete static cost between the node
+ * histograms, up to the rounding of the sums.
+ *
+ * Setting.  a = rho0 / m0, b = rho1 / m1 (one division per node), m0 = sum rho0, m1 = sum rho1; every sum runs over the nodes
+ *   in memory order by the tree of dotsocp_map_report ("Sums").  eps = (eps_h2 * hx) * hy (1-D: (eps_h2 * hx) * hx),
+ *   hx = 1.0 / (double)(nx - 1), ieps = 1.0 / eps.  Per axis of n nodes w = (0.5 * h) * h as above.
+ * Soft pass along one axis, with a prior mean pm (zeros where none is named).  For output j over the candidates
+ *   c_i = in[i] + (double)((i - j)^2) * w, the square exact in integers, non-finite inputs counting as +Inf:
+ *     m = min_i c_i                                         (the forward pass above)
+ *     s = sum_i e_i,   q = sum_i e_i * ((double)((i - j)^2) * w + pm[i]),   e_i = exp((m - c_i) * ieps)
+ *   both added in ascending i into one accumulator per output that starts at 0.0 -- tiles and chunks change no bit;
+ *     out[j] = m - eps * log(s),   mean[j] = q / s;     a line without a finite entry: out = +Inf, mean = 0.
+ *   A term may be skipped only where e_i is exactly +0.0 (the argument of exp below -746).
+ * Two axes: the pass along x (every row y, no prior mean) and then the pass along y on its values with its means as the
+ *   prior mean: mean(j) is the softmax-weighted mean of |x_i - y_j|^2 / 2.  1-D problems: one pass.  The whole transform:
+ *   S(in) -> (value, mean).  No contraction of a * b + c anywhere; the device's exp and log are the only operations that
+ *   upper.py, which restates all of it in numpy, does not reproduce bit for bit.
+ * Sweeps.  la = -(eps * log(a)), lb = -(eps * log(b)); a zero mass gives +Inf: that node drops out.  Start: f = -(dScale *
+ *   phi(t = 0)) (start = 1), f_start (start = 2) or zeros (start = 0); a non-finite entry of the start is counted
+ *   (nonfinite) and counts as 0.0.  One sweep: g = S(la - f), f_new = S(lb - g),
+ *     defect_k = sum_i (a_i > 0 ? a_i * |exp((f_i - f_new_i) * ieps) - 1.0| : 0.0)
+ *   -- the L1 distance of the plan's row sums from a; it may be +Inf --, then f = f_new.  The sweeps stop after max_sweeps of
+ *   them, or behind the first with defect_k <= defect_tol (one scalar travels to the host per sweep).  Then g = S(la - f).
+ * Rounding.  f~ = S(lb - g), f' = f~ < f ? f~ : f;   (g~, E) = S(la - f'), g' = g~ < g ? g~ : g;   f^ = S(lb - g').  The kept
+ *   plan P_ij = a_i b_j exp((f'_i + g'_j - c_ij) / eps) has the row sums r_i = a_i * exp((f'_i - f^_i) * ieps) and the column
+ *   sums k_j = b_j * exp((g'_j - g~_j) * ieps) (0.0 where the mass is zero), both below the marginals; what is missing is
+ *   er_i = max(a_i - r_i, 0.0), ec_j = max(b_j - k_j, 0.0).  Node sums: kept = sum k_j, cost_kept = sum k_j * E_j, and with
+ *   the node coordinates px = (double)x * hx, py = (double)y * hy (1-D: px = 0.0), p2 = px * px + py * py:
+ *   R0, R1x, R1y, R2 = sum er * (1, px, py, p2) and C0, C1x, C1y, C2 = the same of ec.
+ *     fill = R0 < C0 ? R0 : C0
+ *     cost_fill = fill > 0 ? 0.5 * ((R2 * C0 + R0 * C2) - 2.0 * (R1x * C1x + R1y * C1y)) / fill : 0.0
+ *     upper = 2.0 * (cost_kept + cost_fill)
+ *   The plan P + er ec^T / fill has the marginals a and b for ANY f, g, so upper is a bound whatever state the solve is in.
+ * Results.  f, g: f', g';  E;  er, ec: ny x nx doubles each (1-D: nx);  defects: max_sweeps doubles, NaN behind the last
+ *   sweep made;  defect_first / defect_last: of the first / last sweep made (NaN without one);  zero0 / zero1: the nodes
+ *   with rho0 == 0 / rho1 == 0.  Every optional output (all but res) is written only when its pointer is not NULL.
+ *
+ * dotsocp_plan_bound is stateless like dotsocp_image_density: host arrays ny x nx, y fastest (1-D: ny = 1), on HIP device
+ * `device`.  dotsocp_upper_bound runs on the first slab's device of a finished context and is valid where
+ * dotsocp_dual_bound is (DOTSOCP_ESTATE before finish()).  DOTSOCP_EINVAL, with all outputs untouched: what
+ * dotsocp_dual_bound refuses (a NULL rho0 / rho1 / res, a weighted context, an RCCL communicator, an axis of fewer than 2 or
+ * more than 2^20 nodes, m0 or m1 not positive and finite), a NULL opts, an entry of rho0 or rho1 that is negative or not
+ * finite, eps_h2 not positive and finite, max_sweeps < 0, start outside 0 .. 2, start = 2 without f_start, and for the
+ * stateless call start = 1. */
+typedef struct {
+    double eps_h2;                  /* eps in units of hx * hy; 0.25 is a good start */
+    dotsocp_i64 max_sweeps;
+    double defect_tol;              /* stop behind the first sweep with defect <= defect_tol (0: never early) */
+    int start;                      /* 0: zeros, 1: -(dScale * phi(t = 0)), 2: f_start */
+} dotsocp_upper_opts;
+typedef struct {
+    dotsocp_i64 n_nodes, sweeps, zero0, zero1, nonfinite;
+    double eps, mass0, mass1;
+    double upper, cost_kept, cost_fill, kept, fill;
+    double defect_first, defect_last;
+} dotsocp_upper;
+int dotsocp_plan_bound(const double *rho0, const double *rho1, dotsocp_i64 ny, dotsocp_i64 nx, const double *f_start,
+                       const dotsocp_upper_opts *o, dotsocp_upper *res, double *f, double *g, double *E, double *er,
+                       double *ec, double *defects, int device);
+int dotsocp_upper_bound(dotsocp_ctx *ctx, const double *rho0, const double *rho1, const double *f_start,
+                        const dotsocp_upper_opts *o, dotsocp_upper *res, double *f, double *g, double *E, double *er,
+                        double *ec, double *defects);
+
 /* Pictures of the density evolution on the device: what utils/show_evolution_2d.m, show_movement_2d.m and
  * export_evolution_2d.m draw from the downloaded outputs -- gray or colour-mapped frames, filled log-spaced levels, the
  * arrows of the flux -- formed from the device-resident alpha.  A frame reads the two alpha layers around its node; what
@@ -743,7 +811,8 @@ int dotsocp_get_history(dotsocp_ctx *ctx, double *kkt, double *time, double *ite
  * "deposit", "frame_l1" (the per-frame launches of dotsocp_push_mass on the first slab), "advect_path" (the accumulating
  * march of dotsocp_map_report on the first slab: counted here, not under "advect"), "map_final" (its one reduction, when
  * the first slab runs it: one slab, or direction -1), "hl_pass_x", "hl_pass_y", "hl_reduce" (the min-plus passes along x and y and the
- * reduction of dotsocp_dual_bound). */
+ * reduction of dotsocp_dual_bound), "sl_pass_x", "sl_pass_y", "sl_node" (the soft passes along x and y and the node kernels,
+ * their reductions included, of dotsocp_upper_bound). */
 int dotsocp_set_profiling(dotsocp_ctx *ctx, int on);
 int dotsocp_kernel_time(dotsocp_ctx *ctx, const char *name, double *avg_ms, dotsocp_i64 *launches);
 

@@ -13,7 +13,12 @@ defect of the map) and half-way, and the check that every frame holds exactly th
 Last, the judgement of the map itself (map_report= and report= of the drivers): what the map realised by the flow costs
 (the mass-weighted mean of |end - start|^2), beside the mean squared path length and the kinetic action of the same
 particles -- equal for straight paths at constant speed, as an optimal map gives them -- and beside the Eulerian cost of
-the solution report."""
+the solution report.
+Beside the particles, the static map (plan_map= of the drivers): the barycentric map of the rounded Sinkhorn plan of the
+upper bound, a second map that owes nothing to the march -- its cost and the spread around it (together the certified
+upper bound), the mean squared distance map_gap between the particles' end points and T(x), and l1 between the static
+displacement interpolant and the Eulerian rho at three time nodes.  The map is a barycentric projection: it is not measure
+preserving."""
 import os
 import sys
 
@@ -29,7 +34,9 @@ x0, y0 = D.seeds_on_nodes(nx, nx, stride=4, mask=rho0 > floor)
 output, timeML, runHistML, runHist = D.solver_dotsocp2d(rho0, rho1, nt, levelN, dict(tol=tol, maxit=3000), "inPALM",
                                                         advect=dict(x=x0, y=y0, nsub=2, trajectories=True),
                                                         push=dict(stride=1, frames=[0, nt // 2, nt - 1], nsub=2),
-                                                        map_report=dict(stride=1, nsub=2), report=True)
+                                                        map_report=dict(stride=1, nsub=2), report=True,
+                                                        plan_map=dict(max_sweeps=50, frames=[0, nt // 2, nt - 1],
+                                                                      compare=dict(stride=1, nsub=2)))
 adv = output["advect"]
 dev = np.hypot(adv["x"] - x0 - (-0.5), adv["y"] - y0 - 0.5)
 print(f"{x0.size} particles (every 4th node with rho0 > {floor:.3g}), {adv['n_clamped']} clamped at the boundary")
@@ -60,3 +67,10 @@ print(f"  paths: length / displacement - 1 = {mr['cost_length'] / mr['cost_map']
       f"speed: action / length^2 - 1 = {mr['cost_action'] / mr['cost_length'] - 1:.2e}")
 print(f"  mean displacement {mr['disp_mean']:.4f}, mean path length {mr['len_mean']:.4f}, longest {mr['len_max']:.4f}; "
       f"l1 at t = 1 beside it: {push['l1'][-1]:.4e}")
+# the static map of the rounded plan beside the map of the flow
+pm = output["plan_map"]
+print(f"static map of the plan: map_cost {pm['map_cost']:.6f} + spread {pm['spread']:.6f} = {pm['cost_rows']:.6f} "
+      f"(certified upper {pm['upper']['upper']:.6f}); flow's cost_map {mr['cost_map']:.6f}")
+print(f"  particles against it ({pm['n']} seeds): map_gap {pm['map_gap']:.4e} (root {np.sqrt(pm['map_gap']) * (nx - 1):.3f} cells), "
+      f"worst {np.sqrt(pm['map_gap_max']) * (nx - 1):.3f} cells; {pm['n_clamped']} nodes clamped")
+print("  l1 of the static interpolant against rho at nodes " + ", ".join(f"{int(k)}: {v:.4e}" for k, v in zip(pm["nodes"], pm["l1"])))

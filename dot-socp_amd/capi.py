@@ -106,6 +106,12 @@ class Upper(ctypes.Structure):
                 ("kept", dbl), ("fill", dbl), ("defect_first", dbl), ("defect_last", dbl)]
 
 
+class PlanMap(ctypes.Structure):
+    """dotsocp_plan_map_t"""
+    _fields_ = [("rows", dbl), ("map_cost", dbl), ("spread", dbl), ("cost_rows", dbl), ("disp_mean", dbl), ("disp_max", dbl),
+                ("n_clamped", i64), ("unit", dbl)]
+
+
 class ImageOpts(ctypes.Structure):
     """dotsocp_image_opts"""
     _fields_ = [("ny", i64), ("nx", i64), ("layout", ctypes.c_int), ("reverse", ctypes.c_int), ("lower_bound", dbl)]
@@ -171,6 +177,10 @@ SYMBOLS = {
     "dotsocp_dual_bound": (ctypes.c_int, [vp, vp, vp, ctypes.POINTER(Dual), vp, vp, vp, vp]),
     "dotsocp_plan_bound": (ctypes.c_int, [vp, vp, i64, i64, vp, ctypes.POINTER(UpperOpts), ctypes.POINTER(Upper), vp, vp, vp, vp,
                                           vp, vp, ctypes.c_int]),
+    "dotsocp_plan_map": (ctypes.c_int, [vp, vp, i64, i64, vp, ctypes.POINTER(UpperOpts), ctypes.POINTER(Upper), vp, vp, vp, vp,
+                                        vp, vp, ctypes.POINTER(PlanMap), vp, vp, vp, vp, vp, vp, i64, vp, ctypes.c_int]),
+    "dotsocp_upper_map": (ctypes.c_int, [vp, vp, vp, vp, ctypes.POINTER(UpperOpts), ctypes.POINTER(Upper), vp, vp, vp, vp, vp, vp,
+                                         ctypes.POINTER(PlanMap), vp, vp, vp, vp, vp, vp, i64, vp, vp]),
     "dotsocp_upper_bound": (ctypes.c_int, [vp, vp, vp, vp, ctypes.POINTER(UpperOpts), ctypes.POINTER(Upper), vp, vp, vp, vp,
                                            vp, vp]),
     "dotsocp_jump_next_level": (ctypes.c_int, [vp, vp]),

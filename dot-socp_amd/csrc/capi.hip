@@ -436,11 +436,28 @@ int dotsocp_plan_bound(const double *rho0, const double *rho1, dotsocp_i64 ny, d
     return plan_bound(rho0, rho1, ny, nx, f_start, o, res, f, g, E, er, ec, defects, device);
 }
 
+int dotsocp_plan_map(const double *rho0, const double *rho1, dotsocp_i64 ny, dotsocp_i64 nx, const double *f_start,
+                     const dotsocp_upper_opts *o, dotsocp_upper *res, double *f, double *g, double *E, double *er, double *ec,
+                     double *defects, dotsocp_plan_map_t *map_res, double *Dx, double *Dy, double *C, double *row, double *spread,
+                     const double *taus, dotsocp_i64 nf, double *frames, int device) {
+    return plan_map(rho0, rho1, ny, nx, f_start, o, res, f, g, E, er, ec, defects, map_res, Dx, Dy, C, row, spread, taus, nf,
+                    frames, device);
+}
+
 int dotsocp_upper_bound(dotsocp_ctx *ctx, const double *rho0, const double *rho1, const double *f_start,
                         const dotsocp_upper_opts *o, dotsocp_upper *res, double *f, double *g, double *E, double *er, double *ec,
                         double *defects) {
     CTX_OR_FAIL();
     return ctx->s.upper_bound(rho0, rho1, f_start, o, res, f, g, E, er, ec, defects);
+}
+
+int dotsocp_upper_map(dotsocp_ctx *ctx, const double *rho0, const double *rho1, const double *f_start, const dotsocp_upper_opts *o,
+                      dotsocp_upper *res, double *f, double *g, double *E, double *er, double *ec, double *defects,
+                      dotsocp_plan_map_t *map_res, double *Dx, double *Dy, double *C, double *row, double *spread,
+                      const dotsocp_i64 *frame_nodes, dotsocp_i64 nf, double *frames, double *l1) {
+    CTX_OR_FAIL();
+    return ctx->s.upper_map(rho0, rho1, f_start, o, res, f, g, E, er, ec, defects, map_res, Dx, Dy, C, row, spread, frame_nodes, nf,
+                            frames, l1);
 }
 
 int dotsocp_render_evolution(dotsocp_ctx *ctx, const double *rho0, const double *rho1, const dotsocp_render_opts *opts,

@@ -293,6 +293,36 @@ struct SlFinalArgs {
     double *partials;               // [SS_COUNT][hl_blocks(ny * nx)]
 };
 int launch_sl_final(const SlFinalArgs &a, double *sums /* SS_COUNT */, hipStream_t st);
+// The moment flavour of the soft pass (include/dotsocp.h, "Moment pass"; dotsocp_plan_map): out and mean as above, bit for
+// bit, and da[j] = qa / s, the mean signed displacement along the pass's axis (candidate minus output).  The y pass of a
+// layer carries the x pass's da through as pb: db[j] = qb / s (pb == nullptr, a line: db is not written).
+int launch_sl_mom_y(const double *in, const double *pm, const double *pb, double *out, double *mean, double *da, double *db,
+                    i64 n, i64 lines, i64 pitch, double eps, hipStream_t st);
+int launch_sl_mom_x(const double *in, double *out, double *mean, double *da, i64 n, i64 lines, i64 pitch, double eps,
+                    hipStream_t st);
+// the map of the plan per source node (include/dotsocp.h, "Map"): rows of the sums; disp_max: one 64-bit key, zeroed before
+enum { SP_ROWS = 0, SP_MAP, SP_SPREAD, SP_COST, SP_DISP, SP_COUNT };
+struct SlMapArgs {
+    const double *a, *f, *fh, *er;          // a, f', f^ and er of k_sl_final
+    const double *kc, *kdx, *kdy;           // the kept rows' mean cost and displacement: the moment transform (kdx: nullptr for a line)
+    double *Dx, *Dy, *C, *row, *spread;
+    i64 ny, nx;
+    double hx, hy, ieps;                    // hx = 0 for a 1-D line
+    double kappa, mx, my, m2;               // C0 / fill;  C1x / C0, C1y / C0, C2 / C0  (0 where the divisor is 0)
+    double *partials;                       // [SP_COUNT][hl_blocks(ny * nx)]
+    unsigned long long *disp_max;
+};
+int launch_sl_map(const SlMapArgs &a, double *sums /* SP_COUNT */, hipStream_t st);
+// X, Y <- clamp(node + tau * D) of every node of an unpitched layer; flag[i] = 1 where the clamp changed a node with units > 0
+int launch_sl_frame_pos(const double *Dx, const double *Dy, const i64 *units, i64 ny, i64 nx, double hx, double hy, double tau,
+                        double *X, double *Y, unsigned int *flag, hipStream_t st);
+// the 64-bit counts of launch_deposit -> (double)count * unit, in place
+int launch_sl_frame(double *frame, i64 n, double unit, hipStream_t st);
+// dotsocp_plan_map behind the C ABI (solver_upper.hip)
+int plan_map(const double *rho0, const double *rho1, i64 ny, i64 nx, const double *f_start, const dotsocp_upper_opts *o,
+             dotsocp_upper *res, double *f, double *g, double *E, double *er, double *ec, double *defects,
+             dotsocp_plan_map_t *map_res, double *Dx, double *Dy, double *C, double *row, double *spread, const double *taus,
+             i64 nf, double *frames, int device);
 // dotsocp_plan_bound behind the C ABI (solver_upper.hip)
 int plan_bound(const double *rho0, const double *rho1, i64 ny, i64 nx, const double *f_start, const dotsocp_upper_opts *o,
                dotsocp_upper *res, double *f, double *g, double *E, double *er, double *ec, double *defects, int device);

@@ -1,5 +1,6 @@
 // Soft Hopf-Lax transform of a node layer and the node kernels of the upper bound (include/dotsocp.h: dotsocp_plan_bound,
-// dotsocp_upper_bound; host side: solver_upper.hip; numpy twin: dot-socp_amd/upper.py).
+// dotsocp_upper_bound; host side: solver_upper.hip; numpy twin: dot-socp_amd/upper.py), and of the transport map of its plan
+// (dotsocp_plan_map, dotsocp_upper_map): the moment flavour of the two passes, k_sl_map, the frame kernels.
 //
 // One axis, n nodes, w = (0.5 h) h: for output j over the candidates c_i = in[i] + (double)((i - j)^2) w
 //   m = min_i c_i,   s = sum_i exp((m - c_i) ieps),   q = sum_i exp((m - c_i) ieps) ((double)((i - j)^2) w + pm[i]),
@@ -36,6 +37,17 @@ struct SlArgs {
     i64 pitch;          // y pass: doubles between two lines; x pass: doubles between two nodes of a line (lines are 1 apart)
     double w, eps, ieps;
     int chunk;          // inputs staged at a time
+    static constexpr bool MOM = false;
+};
+// the moment flavour (dotsocp_plan_map): beside s and q the signed displacement along the pass's own axis, candidate minus
+// output, qa = sum e * ((double)(i - j) * h), and a prior displacement of the other axis carried through, qb = sum e * pb[i]
+// (the y pass of a layer; the x pass and a line have none).  da = qa / s, db = qb / s, 0 on a dead line.  The plain kernels
+// are the instantiation without: same statements, same order -- out and mean carry the same bits in both.
+struct SlMomArgs : SlArgs {
+    const double *pb;   // y pass: the x pass's mean displacement, in the layout of `in`, or nullptr
+    double *da, *db;    // db: y pass with pb only
+    double h;
+    static constexpr bool MOM = true;
 };
 
 __device__ __forceinline__ double sl_clean(double v) { return isfinite(v) ? v : INFINITY; }
@@ -54,11 +66,14 @@ __device__ __forceinline__ void sl_min_y(const double *s_in, const double *t, in
     }
 }
 
-template <int NR>
+// MOM: dj = i0 - (j0 + tid), so that candidate ii of the chunk and the output of slice r are dj + ii - 256 r nodes apart
+template <int NR, bool MOM>
 __device__ __forceinline__ void sl_sum_y(const double *s_in, const double *s_pm, const double *t, int cnt, double ieps,
-                                         const double (&m)[SL_R], double (&s)[SL_R], double (&q)[SL_R]) {
+                                         const double (&m)[SL_R], double (&s)[SL_R], double (&q)[SL_R], i64 dj, double h,
+                                         double (&qa)[MOM ? SL_R : 1], double (&qb)[MOM ? SL_R : 1]) {
     for (int ii = 0; ii < cnt; ++ii) {
         const double v = s_in[ii], p = s_pm[ii];
+        const double pb = MOM ? s_pm[HL_CHUNK_MAX + ii] : 0.0;
         // the slices are 256 outputs apart: each has its own window of candidates that count, so each votes for itself
 #pragma unroll
         for (int r = 0; r < NR; ++r) {
@@ -68,13 +83,19 @@ __device__ __forceinline__ void sl_sum_y(const double *s_in, const double *s_pm,
             const double e = exp(x);
             s[r] = s[r] + e;
             q[r] = q[r] + e * (d + p);
+            if constexpr (MOM) {
+                qa[r] = qa[r] + e * ((double)(dj + ii - SL_BLOCK * r) * h);
+                qb[r] = qb[r] + e * pb;
+            }
         }
     }
 }
 
-__global__ void __launch_bounds__(SL_BLOCK) k_sl_pass_y(SlArgs a) {
+template <class Args>
+__global__ void __launch_bounds__(SL_BLOCK) k_sl_pass_y(Args a) {
+    constexpr bool MOM = Args::MOM;
     __shared__ double s_in[HL_CHUNK_MAX];
-    __shared__ double s_pm[HL_CHUNK_MAX];
+    __shared__ double s_pm[(MOM ? 2 : 1) * HL_CHUNK_MAX];     // MOM: the prior displacement behind the prior mean
     __shared__ double s_tab[HL_CHUNK_MAX + HL_YOUT];
     const int tid = threadIdx.x;
     const i64 tiles = (a.n + HL_YOUT - 1) / HL_YOUT;
@@ -87,9 +108,16 @@ __global__ void __launch_bounds__(SL_BLOCK) k_sl_pass_y(SlArgs a) {
     for (int r = 0; r < SL_R; ++r)
         if (j0 + (tid & ~63) + SL_BLOCK * r < a.n) nr = r + 1;
     nr = __builtin_amdgcn_readfirstlane(nr);
-    double m[SL_R], s[SL_R], q[SL_R];
+    double m[SL_R], s[SL_R], q[SL_R], qa[MOM ? SL_R : 1], qb[MOM ? SL_R : 1];
 #pragma unroll
     for (int r = 0; r < SL_R; ++r) { m[r] = INFINITY; s[r] = 0.0; q[r] = 0.0; }
+    if constexpr (MOM) {
+#pragma unroll
+        for (int r = 0; r < SL_R; ++r) { qa[r] = 0.0; qb[r] = 0.0; }
+    }
+    const double *pb = nullptr;
+    double h = 0.0;
+    if constexpr (MOM) { pb = a.pb ? a.pb + line * a.pitch : nullptr; h = a.h; }
     // output o = tid + 256 r of the workgroup and input ii of the chunk are d = (i0 + ii) - (j0 + o) apart: slot ii + (HL_YOUT - 1) - o
     const double *t = s_tab + (HL_YOUT - 1) - tid;
     for (int phase = 0; phase < 2; ++phase) {
@@ -99,6 +127,7 @@ __global__ void __launch_bounds__(SL_BLOCK) k_sl_pass_y(SlArgs a) {
             for (int k = tid; k < cnt; k += SL_BLOCK) {
                 s_in[k] = sl_clean(in[i0 + k]);
                 if (phase) s_pm[k] = pm ? pm[i0 + k] : 0.0;
+                if constexpr (MOM) { if (phase) s_pm[HL_CHUNK_MAX + k] = pb ? pb[i0 + k] : 0.0; }
             }
             for (int k = tid; k < cnt + HL_YOUT - 1; k += SL_BLOCK) {
                 const i64 d = i0 - j0 + (k - (HL_YOUT - 1));
@@ -114,11 +143,12 @@ __global__ void __launch_bounds__(SL_BLOCK) k_sl_pass_y(SlArgs a) {
                     default: break;
                 }
             } else {
+                const i64 dj = i0 - (j0 + tid);
                 switch (nr) {
-                    case 1: sl_sum_y<1>(s_in, s_pm, t, cnt, a.ieps, m, s, q); break;
-                    case 2: sl_sum_y<2>(s_in, s_pm, t, cnt, a.ieps, m, s, q); break;
-                    case 3: sl_sum_y<3>(s_in, s_pm, t, cnt, a.ieps, m, s, q); break;
-                    case 4: sl_sum_y<4>(s_in, s_pm, t, cnt, a.ieps, m, s, q); break;
+                    case 1: sl_sum_y<1, MOM>(s_in, s_pm, t, cnt, a.ieps, m, s, q, dj, h, qa, qb); break;
+                    case 2: sl_sum_y<2, MOM>(s_in, s_pm, t, cnt, a.ieps, m, s, q, dj, h, qa, qb); break;
+                    case 3: sl_sum_y<3, MOM>(s_in, s_pm, t, cnt, a.ieps, m, s, q, dj, h, qa, qb); break;
+                    case 4: sl_sum_y<4, MOM>(s_in, s_pm, t, cnt, a.ieps, m, s, q, dj, h, qa, qb); break;
                     default: break;
                 }
             }
@@ -132,11 +162,17 @@ __global__ void __launch_bounds__(SL_BLOCK) k_sl_pass_y(SlArgs a) {
             const bool dead = !(m[r] < INFINITY);
             a.out[line * a.pitch + j] = dead ? INFINITY : m[r] - a.eps * log(s[r]);
             a.mean[line * a.pitch + j] = dead ? 0.0 : q[r] / s[r];
+            if constexpr (MOM) {
+                a.da[line * a.pitch + j] = dead ? 0.0 : qa[r] / s[r];
+                if (a.db) a.db[line * a.pitch + j] = dead ? 0.0 : qb[r] / s[r];
+            }
         }
     }
 }
 
-__global__ void __launch_bounds__(SL_BLOCK) k_sl_pass_x(SlArgs a) {
+template <class Args>
+__global__ void __launch_bounds__(SL_BLOCK) k_sl_pass_x(Args a) {
+    constexpr bool MOM = Args::MOM;
     __shared__ double s_in[HL_XCHUNK_MAX][64];
     __shared__ double s_tab[HL_XCHUNK_MAX + HL_XOUT];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -144,9 +180,15 @@ __global__ void __launch_bounds__(SL_BLOCK) k_sl_pass_x(SlArgs a) {
     const i64 y = ((i64)blockIdx.x % ltiles) * 64 + lane, j0 = ((i64)blockIdx.x / ltiles) * HL_XOUT;
     const bool live = y < a.lines;
     const bool work = j0 + wv * SL_XR < a.n;      // this wavefront has an output (the same for its 64 lanes)
-    double m[SL_XR], s[SL_XR], q[SL_XR];
+    double m[SL_XR], s[SL_XR], q[SL_XR], qa[MOM ? SL_XR : 1];
 #pragma unroll
     for (int r = 0; r < SL_XR; ++r) { m[r] = INFINITY; s[r] = 0.0; q[r] = 0.0; }
+    double h = 0.0;
+    if constexpr (MOM) {
+#pragma unroll
+        for (int r = 0; r < SL_XR; ++r) qa[r] = 0.0;
+        h = a.h;
+    }
     // output o = SL_XR wv + r and input ii of the chunk are d = (i0 + ii) - (j0 + o) apart: slot ii + (HL_XOUT - 1) - o
     const double *t = s_tab + (HL_XOUT - 1) - wv * SL_XR;
     for (int phase = 0; phase < 2; ++phase) {
@@ -186,6 +228,7 @@ __global__ void __launch_bounds__(SL_BLOCK) k_sl_pass_x(SlArgs a) {
                         const double e = exp(x[r]);
                         s[r] = s[r] + e;
                         q[r] = q[r] + e * d[r];
+                        if constexpr (MOM) qa[r] = qa[r] + e * ((double)(i0 + ii - (j0 + wv * SL_XR + r)) * h);
                     }
                 }
             }
@@ -198,6 +241,7 @@ __global__ void __launch_bounds__(SL_BLOCK) k_sl_pass_x(SlArgs a) {
             const bool dead = !(m[r] < INFINITY);
             a.out[y + a.pitch * j] = dead ? INFINITY : m[r] - a.eps * log(s[r]);
             a.mean[y + a.pitch * j] = dead ? 0.0 : q[r] / s[r];
+            if constexpr (MOM) a.da[y + a.pitch * j] = dead ? 0.0 : qa[r] / s[r];
         }
     }
 }
@@ -216,7 +260,18 @@ int launch_sl_pass_y(const double *in, const double *pm, double *out, double *me
     DS_CHECK(sl_launch_check(n, lines, blocks, eps));
     const double h = 1.0 / (double)(n - 1);
     SlArgs a{in, pm, out, mean, n, lines, pitch, (0.5 * h) * h, eps, 1.0 / eps, hl_chunk(HL_CHUNK_MAX)};
-    DS_KLAUNCH(k_sl_pass_y, dim3((unsigned)blocks), dim3(SL_BLOCK), 0, st, a);
+    DS_KLAUNCH(k_sl_pass_y<SlArgs>, dim3((unsigned)blocks), dim3(SL_BLOCK), 0, st, a);
+    DS_HIP(hipGetLastError());
+    return 0;
+}
+
+int launch_sl_mom_y(const double *in, const double *pm, const double *pb, double *out, double *mean, double *da, double *db,
+                    i64 n, i64 lines, i64 pitch, double eps, hipStream_t st) {
+    const i64 blocks = ((n + HL_YOUT - 1) / HL_YOUT) * lines;
+    DS_CHECK(sl_launch_check(n, lines, blocks, eps));
+    const double h = 1.0 / (double)(n - 1);
+    SlMomArgs a{{in, pm, out, mean, n, lines, pitch, (0.5 * h) * h, eps, 1.0 / eps, hl_chunk(HL_CHUNK_MAX)}, pb, da, pb ? db : nullptr, h};
+    DS_KLAUNCH(k_sl_pass_y<SlMomArgs>, dim3((unsigned)blocks), dim3(SL_BLOCK), 0, st, a);
     DS_HIP(hipGetLastError());
     return 0;
 }
@@ -226,7 +281,18 @@ int launch_sl_pass_x(const double *in, double *out, double *mean, i64 n, i64 lin
     DS_CHECK(sl_launch_check(n, lines, blocks, eps));
     const double h = 1.0 / (double)(n - 1);
     SlArgs a{in, nullptr, out, mean, n, lines, pitch, (0.5 * h) * h, eps, 1.0 / eps, hl_chunk(HL_XCHUNK_MAX)};
-    DS_KLAUNCH(k_sl_pass_x, dim3((unsigned)blocks), dim3(SL_BLOCK), 0, st, a);
+    DS_KLAUNCH(k_sl_pass_x<SlArgs>, dim3((unsigned)blocks), dim3(SL_BLOCK), 0, st, a);
+    DS_HIP(hipGetLastError());
+    return 0;
+}
+
+int launch_sl_mom_x(const double *in, double *out, double *mean, double *da, i64 n, i64 lines, i64 pitch, double eps,
+                    hipStream_t st) {
+    const i64 blocks = ((n + HL_XOUT - 1) / HL_XOUT) * ((lines + 63) / 64);
+    DS_CHECK(sl_launch_check(n, lines, blocks, eps));
+    const double h = 1.0 / (double)(n - 1);
+    SlMomArgs a{{in, nullptr, out, mean, n, lines, pitch, (0.5 * h) * h, eps, 1.0 / eps, hl_chunk(HL_XCHUNK_MAX)}, nullptr, da, nullptr, h};
+    DS_KLAUNCH(k_sl_pass_x<SlMomArgs>, dim3((unsigned)blocks), dim3(SL_BLOCK), 0, st, a);
     DS_HIP(hipGetLastError());
     return 0;
 }
@@ -387,6 +453,103 @@ int launch_sl_final(const SlFinalArgs &a, double *sums, hipStream_t st) {
     DS_KLAUNCH(k_sl_final, dim3((unsigned)blocks), dim3(SL_BLOCK), 0, st, a);
     DS_HIP(hipGetLastError());
     return launch_report_rows(a.partials, blocks, SS_COUNT, sums, st);
+}
+
+// ---------------- the map of the plan (dotsocp_plan_map) ----------------
+
+__global__ void __launch_bounds__(SL_BLOCK) k_sl_map(SlMapArgs a) {
+    __shared__ double s_red[SL_BLOCK / 64][SP_COUNT];
+    __shared__ unsigned long long s_key;
+    if (threadIdx.x == 0) s_key = 0;
+    __syncthreads();
+    const i64 i = (i64)blockIdx.x * SL_BLOCK + threadIdx.x;
+    double v[SP_COUNT];
+#pragma unroll
+    for (int k = 0; k < SP_COUNT; ++k) v[k] = 0.0;
+    double disp = 0.0;
+    if (i < a.ny * a.nx) {
+        const i64 x = i / a.ny, y = i - x * a.ny;
+        const double pa = a.a[i];
+        const double wk = pa > 0.0 ? pa * exp((a.f[i] - a.fh[i]) * a.ieps) : 0.0;      // r_i of k_sl_final
+        const double wf = a.er[i] * a.kappa;
+        const double row = wk + wf;
+        double Dx = 0.0, Dy = 0.0, C = 0.0, spread = 0.0, d2 = 0.0;
+        if (row != 0.0) {
+            const double px = (double)x * a.hx, py = (double)y * a.hy, p2 = px * px + py * py;
+            const double fdx = a.mx - px, fdy = a.my - py;
+            const double fc = 0.5 * ((a.m2 - 2.0 * (px * a.mx + py * a.my)) + p2);
+            const double kdx = a.kdx ? a.kdx[i] : 0.0;
+            Dx = (wk * kdx + wf * fdx) / row;
+            Dy = (wk * a.kdy[i] + wf * fdy) / row;
+            C = (wk * a.kc[i] + wf * fc) / row;
+            d2 = Dx * Dx + Dy * Dy;
+            spread = 2.0 * C - d2;
+            disp = sqrt(d2);
+        }
+        a.Dx[i] = Dx;
+        a.Dy[i] = Dy;
+        a.C[i] = C;
+        a.row[i] = row;
+        a.spread[i] = spread;
+        v[SP_ROWS] = row;
+        v[SP_MAP] = row * d2;
+        v[SP_SPREAD] = row * spread;
+        v[SP_COST] = row * C;
+        v[SP_DISP] = row * disp;
+    }
+    // the largest displacement: the bit patterns of non-negative doubles order as unsigned integers (k_map_final)
+    unsigned long long key = (unsigned long long)__double_as_longlong(disp);
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const unsigned long long o = __shfl_down(key, off, 64);
+        key = o > key ? o : key;
+    }
+    if ((threadIdx.x & 63) == 0 && key) atomicMax(&s_key, key);
+    sl_block_sums<SP_COUNT>(v, s_red, a.partials);      // (its barrier also orders s_key)
+    if (threadIdx.x == 64 && s_key) atomicMax(a.disp_max, s_key);
+}
+
+int launch_sl_map(const SlMapArgs &a, double *sums, hipStream_t st) {
+    const i64 blocks = hl_blocks(a.ny * a.nx);
+    DS_KLAUNCH(k_sl_map, dim3((unsigned)blocks), dim3(SL_BLOCK), 0, st, a);
+    DS_HIP(hipGetLastError());
+    return launch_report_rows(a.partials, blocks, SP_COUNT, sums, st);
+}
+
+__device__ __forceinline__ double sl_clamp(double u) { return u < 0.0 ? 0.0 : (u > 1.0 ? 1.0 : u); }     // adv_clamp of advect.hip
+
+// the particle of node i at time tau: clamp(p + tau * D); flag[i] = 1 where a clamp moved a node that carries units (never cleared)
+__global__ void __launch_bounds__(SL_BLOCK) k_sl_frame_pos(const double *__restrict__ Dx, const double *__restrict__ Dy,
+                                                           const i64 *__restrict__ units, i64 ny, i64 nx, double hx, double hy,
+                                                           double tau, double *__restrict__ X, double *__restrict__ Y,
+                                                           unsigned int *__restrict__ flag) {
+    const i64 i = (i64)blockIdx.x * SL_BLOCK + threadIdx.x;
+    if (i >= ny * nx) return;
+    const i64 x = i / ny, y = i - x * ny;
+    const double ux = (double)x * hx + tau * Dx[i], uy = (double)y * hy + tau * Dy[i];
+    const double cx = sl_clamp(ux), cy = sl_clamp(uy);
+    X[i] = cx;
+    Y[i] = cy;
+    if ((cx != ux || cy != uy) && units[i] > 0) flag[i] = 1u;
+}
+
+int launch_sl_frame_pos(const double *Dx, const double *Dy, const i64 *units, i64 ny, i64 nx, double hx, double hy, double tau,
+                        double *X, double *Y, unsigned int *flag, hipStream_t st) {
+    DS_KLAUNCH(k_sl_frame_pos, dim3((unsigned)hl_blocks(ny * nx)), dim3(SL_BLOCK), 0, st, Dx, Dy, units, ny, nx, hx, hy, tau, X, Y, flag);
+    DS_HIP(hipGetLastError());
+    return 0;
+}
+
+// the counts of launch_deposit -> frame = (double)count * unit, in place
+__global__ void __launch_bounds__(SL_BLOCK) k_sl_frame(double *__restrict__ frame, i64 n, double unit) {
+    const i64 i = (i64)blockIdx.x * SL_BLOCK + threadIdx.x;
+    if (i < n) frame[i] = (double)__double_as_longlong(frame[i]) * unit;
+}
+
+int launch_sl_frame(double *frame, i64 n, double unit, hipStream_t st) {
+    DS_KLAUNCH(k_sl_frame, dim3((unsigned)hl_blocks(n)), dim3(SL_BLOCK), 0, st, frame, n, unit);
+    DS_HIP(hipGetLastError());
+    return 0;
 }
 
 }  // namespace dotsocp

@@ -324,6 +324,10 @@ struct Solver {
     // the first slab's device; f_start and the output arrays (ny x nx doubles; defects: max_sweeps): host, each may be NULL
     int upper_bound(const double *rho0, const double *rho1, const double *f_start, const dotsocp_upper_opts *o, dotsocp_upper *res,
                     double *f, double *g, double *E, double *er, double *ec, double *defects);
+    // dotsocp_upper_map: the bound and the barycentric map of its plan; frames at time nodes with l1 against rho there
+    int upper_map(const double *rho0, const double *rho1, const double *f_start, const dotsocp_upper_opts *o, dotsocp_upper *res,
+                  double *f, double *g, double *E, double *er, double *ec, double *defects, dotsocp_plan_map_t *map_res, double *Dx,
+                  double *Dy, double *C, double *row, double *spread, const i64 *frame_nodes, i64 nf, double *frames, double *l1);
 
     // ================ the inPALM loop and its profiling: solver.hip ================
     // ---- loop state (mirrors solver_socp_inPALM.m:11-135) ----

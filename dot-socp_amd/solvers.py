@@ -253,6 +253,36 @@ class InPALMContext:
         return U.device_call(lambda *a: capi.lib().dotsocp_upper_bound(self._ctx, *a), r0, r1, shp, eps_h2, max_sweeps,
                              defect_tol, start, f_start, arrays)
 
+    def plan_map(self, eps_h2=0.25, max_sweeps=50, defect_tol=0.0, start=1, f_start=None, arrays=False, frames=None, compare=None):
+        """upper_bound() and the transport map of its plan, on the device (dotsocp_upper_map; upper.py): the barycentric map
+        T(x) = x + (Dx, Dy) of the rounded plan -- a second, static map beside the one the flow realises; a projection, not
+        measure preserving --, its cost and the spread around it (map_cost + spread = cost_rows = upper, to rounding).
+        frames: time nodes (any order) at which the displacement interpolant ((1 - tau) Id + tau T)# rho0, tau = node / (nt - 1),
+        is deposited; l1[k] = mean |frames[..., k] - rho(node)|.  compare = dict(stride=1, nsub=1): particles seeded on every
+        stride-th node of positive mass are marched by advect(); map_gap = the mass-weighted mean of |X(1) - T(x)|^2,
+        map_gap_max its maximum (upper.map_gap).  Returns an upper.PlanMap (+ frames, l1, nodes; + map_gap, map_gap_max).
+        Call after finish(); unweighted contexts only."""
+        from . import upper as U
+        from .advect import masses_on_nodes, seeds_on_nodes
+        m = self.model
+        one_d = not hasattr(m, "ny")
+        shp = (int(m.nx),) if one_d else (int(m.ny), int(m.nx))
+        r0, r1 = self._rho_ends()
+        nodes = None if frames is None else np.array(frames, dtype=np.int64).ravel()
+        l1 = np.empty(0 if nodes is None else nodes.size)
+        call = lambda *a: capi.lib().dotsocp_upper_map(self._ctx, *a, l1.ctypes.data if l1.size else None)   # noqa: E731
+        out = U.device_map_call(call, r0, r1, shp, eps_h2, max_sweeps, defect_tol, start, f_start, arrays, nodes, int_times=True)
+        if nodes is not None and nodes.size:
+            out.update(l1=l1, nodes=nodes)
+        if compare is not None:
+            stride, nsub = int(compare.get("stride", 1)), int(compare.get("nsub", 1))
+            mask = np.asarray(m.rho0) > 0
+            x, y = seeds_on_nodes(int(m.nx), None if one_d else int(m.ny), stride=stride, mask=mask)
+            at = lambda t: masses_on_nodes(t, stride=stride, mask=mask)             # noqa: E731
+            end = self.advect(x, y, nsub=nsub)
+            out.update(U.map_gap(x, y, end["x"], end["y"], at(out["Dx"]), None if one_d else at(out["Dy"]), at(m.rho0)))
+        return out
+
     def render(self, frames=None, num_frame=6, mode="imshow", nlevels=128, lut=None, barrier=None, vmax=None, arrows=False,
                barrier_index=255, levels=None):
         """Pictures of the density evolution on the device (dotsocp_render_evolution; render.py): uint8 frames at the nodes
@@ -507,7 +537,7 @@ def _weights_mode(weight, weights, transfer, weighted=True):
 
 
 def _solve_levels(rho0, rho1, nt, levelN, opts, method, dim, weighted, device, barrier=None, transfer="device",
-                  weights=None, report=False, advect=None, push=None, map_report=None, render=None, dual=False, upper=None):
+                  weights=None, report=False, advect=None, push=None, map_report=None, render=None, dual=False, upper=None, plan_map=None):
     """The level loop of solver_dotsocp2d.m:154-250 (dot1d / wdot2d twins): restrict the data to
     levelN grids, solve coarse to fine with warm starts; every solve runs on the device.
     transfer = "device": the state never leaves the GPU -- jump_nextLevel and the output recovery run there
@@ -534,7 +564,11 @@ def _solve_levels(rho0, rho1, nt, levelN, opts, method, dim, weighted, device, b
     output["dual"] holds it.  Needs transfer="device"; a weighted context refuses (capi.DotsocpError).
     upper = dict(eps_h2=..., max_sweeps=..., defect_tol=...): the keyword arguments of InPALMContext.upper_bound() -- the
     upper end of the bracket around W2^2 -- asked of the last level's context; output["upper"] holds its result.  Needs
-    transfer="device"; a weighted context refuses."""
+    transfer="device"; a weighted context refuses.
+    plan_map = dict(eps_h2=..., max_sweeps=..., frames=..., compare=dict(stride=..., nsub=...)): the keyword arguments of
+    InPALMContext.plan_map() -- the static transport map of the rounded plan, its frames and its distance from the flow's
+    own map -- asked of the last level's context; output["plan_map"] holds its result.  Needs transfer="device"; a weighted
+    context refuses."""
     from . import multilevel as ML
     from .examples import ensure_barrier_validity
     if not (isinstance(levelN, (int, np.integer)) and levelN >= 1):
@@ -553,6 +587,8 @@ def _solve_levels(rho0, rho1, nt, levelN, opts, method, dim, weighted, device, b
         raise ValueError("dual=True needs transfer='device' (the bound is taken from the device-resident potential)")
     if upper is not None and transfer != "device":
         raise ValueError("upper= needs transfer='device' (the sweeps start from the device-resident potential)")
+    if plan_map is not None and transfer != "device":
+        raise ValueError("plan_map= needs transfer='device' (the sweeps start from the device-resident potential)")
     if render is not None and transfer != "device":
         raise ValueError("render= needs transfer='device' (the pictures are made from the device-resident state)")
     wopt = _get(opts, "weight") if weighted else None
@@ -639,6 +675,8 @@ def _solve_levels(rho0, rho1, nt, levelN, opts, method, dim, weighted, device, b
                     output["dual"] = ctx.dual_bound()
                 if upper is not None:
                     output["upper"] = ctx.upper_bound(**upper)
+                if plan_map is not None:
+                    output["plan_map"] = ctx.plan_map(**plan_map)
                 if advect is not None:
                     output["advect"] = ctx.advect(**advect)
                 if push is not None:
@@ -684,7 +722,7 @@ def _solve_levels(rho0, rho1, nt, levelN, opts, method, dim, weighted, device, b
 
 
 def solver_dotsocp2d(rho0, rho1, nt, levelN, opts, method="inPALM", device=0, transfer="device", report=False,
-                     advect=None, push=None, map_report=None, render=None, dual=False, upper=None):
+                     advect=None, push=None, map_report=None, render=None, dual=False, upper=None, plan_map=None):
     """[output, timeML, runHistML, runHist] = solver_dotsocp2d(rho0, rho1, nt, levelN, opts, method)
     socp/dot2d/solver_dotsocp2d.m:1.  report=True: output["report"] = the device-side solution report; advect=dict(x=..., y=...,
     ...): output["advect"] = the particles carried along the solved flow; push=dict(stride=..., frames=..., ...):
@@ -695,32 +733,32 @@ def solver_dotsocp2d(rho0, rho1, nt, levelN, opts, method="inPALM", device=0, tr
     output["upper"] = the upper bound on it from Sinkhorn sweeps rounded to a plan (all seven: _solve_levels)."""
     output, timeML, runHistML, runHist = _solve_levels(rho0, rho1, nt, levelN, opts, method, 2, False, device,
                                                        transfer=transfer, report=report, advect=advect, push=push, map_report=map_report,
-                                                       render=render, dual=dual, upper=upper)
+                                                       render=render, dual=dual, upper=upper, plan_map=plan_map)
     if not check_massConservation(output["rho"], 1e-2):
         print("Warning: The mass conservation constraint violation exceeds 0.01")
     return output, timeML, runHistML, runHist
 
 
 def solver_dotsocp1d(rho0, rho1, nt, levelN, opts, method="inPALM", device=0, transfer="device", report=False,
-                     advect=None, push=None, map_report=None, render=None, dual=False, upper=None):
+                     advect=None, push=None, map_report=None, render=None, dual=False, upper=None, plan_map=None):
     """socp/dot1d/solver_dotsocp1d.m:1.  report, advect, push, map_report, render, dual, upper: as for solver_dotsocp2d."""
     output, timeML, runHistML, runHist = _solve_levels(rho0, rho1, nt, levelN, opts, method, 1, False, device,
                                                        transfer=transfer, report=report, advect=advect, push=push, map_report=map_report,
-                                                       render=render, dual=dual, upper=upper)
+                                                       render=render, dual=dual, upper=upper, plan_map=plan_map)
     if not check_massConservation(output["rho"], 1e-2):
         print("Warning: The mass conservation constraint violation exceeds 0.01")
     return output, timeML, runHistML, runHist
 
 
 def solver_wdotsocp2d(rho0, rho1, nt, levelN, opts, method="inPALM", barrier=None, device=0, transfer="device",
-                      weights=None, report=False, advect=None, push=None, map_report=None, render=None, dual=False, upper=None):
+                      weights=None, report=False, advect=None, push=None, map_report=None, render=None, dual=False, upper=None, plan_map=None):
     """socp/wdot2d/solver_wdotsocp2d.m:1.  opts["weight"]: the Nq array, or a SpaceWeight (examples.py); weights:
     where the levels' weights are made, "host" or "device" (_solve_levels); report, advect, push, map_report, render: as for
     solver_dotsocp2d (render: `barrier` is the default mask of the pictures; dual=True and upper= raise the library's refusal:
     the weighted cost is not the Euclidean one)."""
     output, timeML, runHistML, runHist = _solve_levels(rho0, rho1, nt, levelN, opts, method, 2, True, device,
                                                        barrier=barrier, transfer=transfer, weights=weights, report=report,
-                                                       advect=advect, push=push, map_report=map_report, render=render, dual=dual, upper=upper)
+                                                       advect=advect, push=push, map_report=map_report, render=render, dual=dual, upper=upper, plan_map=plan_map)
     if not check_massConservation(output["rho"], 1e-2):
         print("Warning: The tolerance of mass conservation constraint is under 0.01")
     return output, timeML, runHistML, runHist

@@ -622,6 +622,67 @@ int dotsocp_upper_bound(dotsocp_ctx *ctx, const double *rho0, const double *rho1
                         const dotsocp_upper_opts *o, dotsocp_upper *res, double *f, double *g, double *E, double *er,
                         double *ec, double *defects);
 
+/* The transport map of that plan.  The bound above builds a feasible plan and returns its cost; the plan also determines a
+ * map, again without any n x n object: T(x_i) = E[y | x_i], the barycentric projection of the plan P + er ec^T / fill, and
+ * the displacement interpolant ((1 - tau) Id + tau T)# rho0 as frames.  The map is a projection: it is NOT measure preserving
+ * (T# rho0 is close to rho1 only as far as the plan is close to a deterministic one); `spread` says how far it is.
+ *
+ * Moment pass.  The soft pass of dotsocp_plan_bound ("Soft pass") with two more accumulators of the same kind beside s and q,
+ *   both from 0.0 and added in ascending i, with h = 1.0 / (double)(n - 1):
+ *     qa = sum_i e_i * ((double)(i - j) * h)      candidate minus output along the pass's axis, the difference exact
+ *     qb = sum_i e_i * pb[i]                      a prior displacement of the other axis, carried through
+ *   da[j] = qa / s, db[j] = qb / s, 0 on a line without a finite entry.  A term is skipped where the plain pass skips it.  out
+ *   and mean carry the bits of the plain pass.  Two axes: the pass along x gives (value, mean, da); the pass along y takes its
+ *   mean as pm and its da as pb:  kc = mean, kdy = da, kdx = db.  1-D: one pass, kc = mean, kdy = da, kdx = 0.
+ * Map.  dotsocp_plan_bound runs as it is, except that the last transform f^ = S(lb - g') is a moment pass: its softmax
+ *   weights at source node i are the conditional law of the kept plan P, so kc, kdx, kdy are the kept row's mean cost and mean
+ *   displacement.  The fill row er_i ec^T / fill has closed-form moments from the sums of "Rounding":
+ *     kappa = fill > 0 ? C0 / fill : 0.0;   mx = C1x / C0, my = C1y / C0, m2 = C2 / C0  (each 0.0 if C0 == 0)
+ *   Per source node i in memory order, with px, py, p2 as above:
+ *     wk = r_i;  wf = er_i * kappa;  row = wk + wf                                (the row sum of the plan)
+ *     fdx = mx - px;  fdy = my - py;  fc = 0.5 * ((m2 - 2.0 * (px * mx + py * my)) + p2)
+ *     Dx = (wk * kdx + wf * fdx) / row;  Dy = (wk * kdy + wf * fdy) / row;  C = (wk * kc + wf * fc) / row
+ *     d2 = Dx * Dx + Dy * Dy;  spread_i = 2.0 * C - d2  (not clamped);  disp = sqrt(d2)
+ *   row == 0 (a node without mass): Dx = Dy = C = spread_i = disp = 0.  T(x_i) = x_i + (Dx, Dy); C is the conditional mean
+ *   cost, spread_i the trace of the conditional covariance of y given x_i.  Sums (the tree of "Sums", no floating-point atomic):
+ *     rows = sum row;  map_cost = sum row * d2;  spread = sum row * spread_i;  cost_rows = 2.0 * sum row * C;
+ *     disp_mean = sum row * disp;  disp_max = max disp  (order-free: an integer atomic on the bit pattern)
+ *   Exact arithmetic gives rows = 1, cost_rows = upper and cost_rows = map_cost + spread: the certified bound splits into the
+ *   cost of a deterministic map and the blur around it (the entropic blur plus whatever splitting the histograms force).
+ * Frames.  unit: the rule of dotsocp_push_mass with n = the node count and the largest entry of rho0 (as given, not
+ *   normalised: a frame compares with rho directly);  M_i = llrint(rho0_i / unit).  For every tau_k the particle of node i
+ *   stands at  X = clamp(px + tau_k * Dx),  Y = clamp(py + tau_k * Dy)  (clamp to [0, 1]) and deposits its M_i units by the
+ *   weights and counts of dotsocp_push_mass;  frames[:, :, k] = (double)count * unit.  Every frame holds sum M_i units.
+ *   n_clamped: the nodes with M_i > 0 whose position a clamp changed in some frame, each once.
+ * No contraction of a * b + c anywhere; upper.barycentric_map and upper.plan_frames restate all of it in numpy.
+ *
+ * dotsocp_plan_map is dotsocp_plan_bound with the map: res and its six optional arrays come back with the same bits.  Dx, Dy,
+ * C, row, spread: ny x nx doubles each, y fastest, each optional (1-D: the displacement comes back in Dx, Dy is ignored).
+ * taus: nf doubles in [0, 1], any order, repeats allowed;  frames: ny x nx x nf;  nf = 0 with both NULL is allowed.
+ * DOTSOCP_EINVAL, with all outputs untouched: what dotsocp_plan_bound refuses, a NULL map_res, nf < 0, nf > 0 without taus or
+ * without frames, a tau that is not finite or outside [0, 1] (dotsocp_upper_map: nf > 0 without frame_nodes, a frame node outside
+ * [0, nt)), a rho0 for which the unit rule fails. */
+typedef struct {
+    double rows, map_cost, spread, cost_rows, disp_mean, disp_max;
+    dotsocp_i64 n_clamped;          /* 0 without frames */
+    double unit;
+} dotsocp_plan_map_t;
+int dotsocp_plan_map(const double *rho0, const double *rho1, dotsocp_i64 ny, dotsocp_i64 nx, const double *f_start,
+                     const dotsocp_upper_opts *o, dotsocp_upper *res, double *f, double *g, double *E, double *er,
+                     double *ec, double *defects, dotsocp_plan_map_t *map_res, double *Dx, double *Dy, double *C,
+                     double *row, double *spread, const double *taus, dotsocp_i64 nf, double *frames, int device);
+/* The context call: valid exactly where dotsocp_upper_bound is, and equal to dotsocp_plan_map where both apply (start = 1
+ * against f_start = -(dScale * phi(t = 0))).  The frames stand at time nodes: tau_k = (double)frame_nodes[k] / (double)(nt - 1),
+ * nodes in [0, nt), any order, repeats allowed.  l1[k] (nf doubles, may be NULL) = the mean over the nodes of
+ * |frames[:, :, k] - rho(:, :, frame_nodes[k])|, formed by the kernel and in the order of dotsocp_push_mass's l1 on the slab
+ * that owns the node (the counts plane travels there through the host): the distance between the dynamic solve's density and
+ * the static displacement interpolant. */
+int dotsocp_upper_map(dotsocp_ctx *ctx, const double *rho0, const double *rho1, const double *f_start,
+                      const dotsocp_upper_opts *o, dotsocp_upper *res, double *f, double *g, double *E, double *er,
+                      double *ec, double *defects, dotsocp_plan_map_t *map_res, double *Dx, double *Dy, double *C,
+                      double *row, double *spread, const dotsocp_i64 *frame_nodes, dotsocp_i64 nf, double *frames,
+                      double *l1);
+
 /* Pictures of the density evolution on the device: what utils/show_evolution_2d.m, show_movement_2d.m and
  * export_evolution_2d.m draw from the downloaded outputs -- gray or colour-mapped frames, filled log-spaced levels, the
  * arrows of the flux -- formed from the device-resident alpha.  A frame reads the two alpha layers around its node; what

@@ -73,8 +73,8 @@ def set_state(var, start):
 
 # --------------------------------------------------------------------------------------------------
 # The cases the generic-start tests run (tests/test_generic_state_conditions.py on the CPU asserts for each that the
-# start does its job; tests/test_gpu_generic_state.py and tests/test_gpu_generic_accadmm.py compare the device loops with
-# the same oracle runs).
+# start does its job; tests/test_gpu_generic_state.py, tests/test_gpu_generic_accadmm.py and tests/test_gpu_generic_palm.py
+# compare the device loops with the same oracle runs).
 # shape: (ny, nx, nt), or (nx, nt) for the 1-D problem.  Every entry may carry seed / amplitudes / shift of its own, and
 # solver options (restart, rho, theta, ifCheckStepByStep) under `opts`.
 # --------------------------------------------------------------------------------------------------
@@ -146,6 +146,14 @@ CASES = {
     "acc-ADMM-checkstep-40x12x13": dict(method="acc-ADMM", shape=(40, 12, 13), K=8, shift=20.0, amplitudes=dict(phi=0.02),
                                         opts=dict(ifCheckStepByStep=True, rho=1.5)),
     "PALM-40x12x13": dict(method="PALM", shape=(40, 12, 13), K=7, shift=20.0, amplitudes=dict(phi=0.02, beta=0.1)),
+    # --- PALM on the tile-crossing grids and with a check in every iteration (tests/test_gpu_generic_palm.py).  The polar
+    # rows are gone after iteration 7 on every grid: K <= 7, checks at 1, 4, 7.
+    # 130 x 9 x 7 with phi = 0.02 leaves the inside branch a share of 0.0016 (alpha = 2.5, beta = 0.4 and phi = 0.05 make it
+    # smaller); phi = 0.01 gives 0.0037
+    "PALM-130x9x7": dict(method="PALM", shape=(130, 9, 7), K=7, shift=20.0, amplitudes=dict(phi=0.01, beta=0.1)),
+    "PALM-100x70x20": dict(method="PALM", shape=(100, 70, 20), K=7, shift=20.0, amplitudes=dict(phi=0.02, beta=0.1)),
+    "PALM-checkstep-66x10x6": dict(method="PALM", shape=(66, 10, 6), K=6, shift=20.0, amplitudes=dict(phi=0.02, beta=0.1),
+                                   opts=dict(ifCheckStepByStep=True)),
 }
 
 # KKT column 5 (index 4), sigma ||F*B*beta + D_w alpha||, is zero in exact arithmetic for the loops whose multiplier step
@@ -204,9 +212,9 @@ def oracle_run(case, perturb=False):
     """The oracle's free-running loop of a case from its generic start, computed once per process and shared (treat
     the result as read-only).  Returns a dict: var (the finished level), start, hist, sigma, shares (one
     (polar, inside, surface) triple per z-step projection, the projection inside the KKT block not counted),
-    weight, and the level's opts; for acc-ADMM also sigma_updates ((iteration, factor) of every check that changed
-    sigma), restarts (the iterations whose extrapolation ended with the count back at 0) and interps ((iteration, k)
-    of every extrapolation, k the count it ran with)."""
+    weight, and the level's opts; for acc-ADMM and PALM also sigma_updates ((iteration, factor) of every check that
+    changed sigma), for acc-ADMM restarts (the iterations whose extrapolation ended with the count back at 0) and
+    interps ((iteration, k) of every extrapolation, k the count it ran with)."""
     key = (case, bool(perturb))
     if key in _runs:
         return _runs[key]
@@ -227,15 +235,19 @@ def oracle_run(case, perturb=False):
             shares.append(branch_shares(inp))
         plain(out, inp)
 
-    # acc-ADMM: the iterations at which a check changed sigma (with the factor), and those at which the extrapolation
-    # count returned to 0 inside _interpolate (a restart by count, as opposed to the reset a sigma update makes)
+    # acc-ADMM and PALM: the iterations at which a check changed sigma (with the factor); acc-ADMM: those at which the
+    # extrapolation count returned to 0 inside _interpolate (a restart by count, as opposed to the reset a sigma update makes)
     sigma_updates, restarts, interps = [], [], []
-    if hasattr(st, "_interpolate"):
-        apply_factor, interpolate = st._apply_sigma_factor, st._interpolate
+    if hasattr(st, "_interpolate") or spec["method"] == "PALM":
+        apply_factor = st._apply_sigma_factor
 
         def recording_factor(factor):
             sigma_updates.append((st.it, float(factor)))
             apply_factor(factor)
+
+        st._apply_sigma_factor = recording_factor
+    if hasattr(st, "_interpolate"):
+        interpolate = st._interpolate
 
         def recording_interpolate():
             k = st.k
@@ -244,7 +256,7 @@ def oracle_run(case, perturb=False):
             if st.k == 0:
                 restarts.append(st.it)
 
-        st._apply_sigma_factor, st._interpolate = recording_factor, recording_interpolate
+        st._interpolate = recording_interpolate
 
     mexops.mexProjSoc = counting
     try:

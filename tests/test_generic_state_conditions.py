@@ -17,7 +17,8 @@ tests/test_gpu_generic_state.py runs, the free-running loop started there
     comparison are 10x and 1e4x what rounding alone can explain.
 
 For the acc-ADMM cases the schedule of the extrapolation is asserted as well (test_the_accadmm_cases_...): which checks
-change sigma, where the count restarts, which branches of the theta != 2 interpolation run.
+change sigma, where the count restarts, which branches of the theta != 2 interpolation run.  For the PALM cases (test_the_palm_cases_take_every_path): a check that changes sigma and one that
+leaves it alone, each followed by further iterations, and a case that checks in every iteration.
 
 A later change of the recipe, of a case or of the oracle that empties one of these fails here, on the CPU."""
 import numpy as np
@@ -151,6 +152,41 @@ def test_the_accadmm_cases_take_every_path_of_the_extrapolation(case):
             assert stores == {True, False}
             # ... and both for k == 0 and for k > 0 where the count allows it (k + 1 < restart needs k <= 1)
             assert any(k > 0 and k + 1 < restart for k in ks) and any(k > 0 and k + 1 >= restart for k in ks)
+
+
+PALM_CASES = [c for c, spec in G.CASES.items() if spec["method"] == "PALM"]
+
+
+def test_the_palm_cases_take_every_path():
+    """What Solver::palm_step does in the iteration after a check hangs on that check: the multiplier step is executed and
+    z regenerated either way, but a check that changed sigma has divided alpha, beta and c by the factor in between, one
+    that left it alone has not.  Over the PALM cases together both kinds occur at a check that is not the last one (the
+    pass after the last check never runs), and the checkstep case checks in every iteration, so that none of its
+    iterations ever takes the one-pass form (k_cone_fused mode 5).  PALM-130x9x7 is the case whose first check leaves
+    sigma alone; in the other cases every check changes it."""
+    assert len(PALM_CASES) >= 5
+    changed, alone = {}, {}
+    for case in PALM_CASES:
+        spec = G.CASES[case]
+        run = G.oracle_run(case)
+        checks = [int(i) for i in run["hist"]["iter"]]
+        factors = dict(run["sigma_updates"])
+        assert set(factors) <= set(checks) and all(f != 1.0 for f in factors.values())
+        changed[case] = [i for i in checks[:-1] if i in factors]
+        alone[case] = [i for i in checks[:-1] if i not in factors]
+        print("\n%s: checks %s  sigma factors %s  left alone at %s"
+              % (case, checks, {i: round(f, 3) for i, f in factors.items()}, alone[case]))
+        if spec.get("opts", {}).get("ifCheckStepByStep"):
+            assert checks == list(range(1, spec["K"] + 1))
+            # sigma may change only where the schedule of IfAdjustSigma says so: the other checks all leave it alone
+            assert len(alone[case]) >= 2 and len(changed[case]) >= 1
+        else:
+            assert len(checks) < spec["K"]
+    assert any(G.CASES[c].get("opts", {}).get("ifCheckStepByStep") for c in PALM_CASES)
+    free = [c for c in PALM_CASES if not G.CASES[c].get("opts", {}).get("ifCheckStepByStep")]
+    assert sum(1 for c in free if changed[c]) >= 2
+    assert alone["PALM-130x9x7"] == [1] and changed["PALM-130x9x7"] == [4]
+    assert any(alone[c] for c in free)
 
 
 def test_column_5_of_the_weighted_accadmm_cases():

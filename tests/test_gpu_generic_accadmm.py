@@ -22,7 +22,8 @@ sides: below 1e-13, and below 3.1e-10 under 1e6 weights (tests/test_generic_stat
     switched off are held against the oracle too.
 (c) time slabs (ship_tails, the raw q^+ halo, the u0 tail with launch_rhs_fixup, the phi^+ head in front of the unfolded
     KKT block): 40 x 12 x 13 in two and three slabs, on a stream pair per slab, under both t solves; DOTSOCP_ACC_POST
-    to the bit on three slabs; PALM's one-pass dataflow on slabs.
+    to the bit on three slabs.
+PALM from the generic start, on one slab and on time slabs, is in tests/test_gpu_generic_palm.py.
 
 Measured errors are recorded in DESIGN.md (section 5, "acc-ADMM from a generic start")."""
 import numpy as np
@@ -170,9 +171,3 @@ def test_the_pass_after_a_check_changes_no_bit_on_three_slabs(case, monkeypatch)
     off = _run(monkeypatch, case, {"DOTSOCP_ACC_POST": "0"}, nslabs=3)
     _identical(_run(monkeypatch, case, {"DOTSOCP_ACC_POST": "1"}, nslabs=3), off)
     _against_the_oracle(case, "acc_post=0, nslabs=3", off)
-
-
-@pytest.mark.parametrize("nslabs", [2, 3])
-def test_palm_on_time_slabs_from_the_generic_start(nslabs, monkeypatch):
-    case = "PALM-40x12x13"
-    _against_the_oracle(case, "nslabs=%d" % nslabs, _gpu_run(monkeypatch, case, nslabs=nslabs))

@@ -17,6 +17,9 @@ so iteration 2 writes gamma, 3 is steady, 4 exits into a check, and from 19 on t
     The accelerated ADMM loop has a file of its own, tests/test_gpu_generic_accadmm.py, which reuses the helpers here:
     _gpu_run clears every switch of the library, DOTSOCP_ACC_POST and DOTSOCP_TSOLVE included, and counts the launches
     of the acc-ADMM phases as well.
+    The proximal ALM loop likewise: tests/test_gpu_generic_palm.py (tile-crossing grids, a check in every iteration,
+    DOTSOCP_PALM_FAST, DOTSOCP_KKT_FOLD, the bit-exact switches, time slabs); here PALM runs once, on 66 x 10 x 6 under the
+    default switches.  _gpu_run clears DOTSOCP_PALM_FAST and counts PALM's first q-step (qstep_first) too.
 (b) the switches of the library, on the same data: bit-identical, or (DOTSOCP_KKT_FOLD) at the bounds of
     tests/test_gpu_kkt_fold.py without the absolute floor.
 (c) time slabs against the oracle, and DOTSOCP_CONE_CARRY to the bit on them.
@@ -33,10 +36,10 @@ from test_generic_state_conditions import noise_bound          # NOISE, or NOISE
 pytestmark = pytest.mark.gpu
 FIELDS = G.FIELDS
 SWITCHES = ("DOTSOCP_QCONE", "DOTSOCP_QCONE_TC", "DOTSOCP_FUSED", "DOTSOCP_CONE_CARRY", "DOTSOCP_C_ENDS", "DOTSOCP_QTX",
-            "DOTSOCP_NT", "DOTSOCP_KKT_FOLD", "DOTSOCP_ACC_POST", "DOTSOCP_TSOLVE")
+            "DOTSOCP_NT", "DOTSOCP_KKT_FOLD", "DOTSOCP_ACC_POST", "DOTSOCP_TSOLVE", "DOTSOCP_PALM_FAST")
 SETTINGS = {"default": {}, "qcone": {"DOTSOCP_QCONE": "1"}, "qcone-tc3": {"DOTSOCP_QCONE": "1", "DOTSOCP_QCONE_TC": "3"},
             "unfused": {"DOTSOCP_FUSED": "0"}}
-PHASES = ("cone_fused_a", "cone_fused_b", "cone_carry", "qcone", "qstep", "acc_cone", "acc_gather")
+PHASES = ("cone_fused_a", "cone_fused_b", "cone_carry", "qcone", "qstep", "acc_cone", "acc_gather", "qstep_first")
 
 
 def _gpu_run(monkeypatch, case, env=None, profiling=False, **split):

@@ -5,12 +5,13 @@ Import as `import dotsocp_amd` (alias module at the repository root; the directo
 `dot-socp_amd` is not a Python identifier).  The compute path is lib/libdotsocp.so -- there is
 no CPU fallback; see include/dotsocp.h for the C ABI and INTEGRATION.md for the MATLAB binding.
 """
-from . import advect, capi, dual, render, upper  # noqa: F401
+from . import advect, capi, dual, geodesic, render, upper  # noqa: F401
 from .advect import default_rho_floor, map_report, masses_on_nodes, push_forward, seeds_on_nodes  # noqa: F401
 from .capi import cdft_levels, dct_algorithm, dct_levels  # noqa: F401
 from .dual import DualBound, dual_bound, hopf_lax  # noqa: F401
 from .upper import (PlanMap, UpperBound, barycentric_map, plan_bound, plan_dense, plan_frames, plan_map, sinkhorn_round,  # noqa: F401
                     soft_transform, upper_bound)
+from .geodesic import GeodesicProfile, geodesic_profile  # noqa: F401
 from .examples import (SpaceWeight, ensure_barrier_validity, gene_barrier_of_circle_pillar,  # noqa: F401
                        gene_barrier_of_love_heart, gene_space_weight_circle, gene_space_weight_circleInv,
                        gene_weight_circle, gene_weight_circleInv, get_example_1d, get_example_2d,

@@ -57,6 +57,15 @@ class Report(ctypes.Structure):
                 ("cost", dbl), ("nonfinite", i64)]
 
 
+GEO_SUMS = 11                  # DOTSOCP_GEO_SUMS
+
+
+class Geodesic(ctypes.Structure):
+    """dotsocp_geodesic"""
+    _fields_ = [("nt", i64), ("n_nodes", i64), ("cost", dbl), ("energy_min", dbl), ("energy_max", dbl), ("speed_spread", dbl),
+                ("com_defect", dbl), ("momentum_defect", dbl), ("entropy_defect", dbl), ("peak_excess", dbl), ("nonfinite", i64)]
+
+
 class AdvectOpts(ctypes.Structure):
     """dotsocp_advect_opts"""
     _fields_ = [("n", i64), ("nsub", ctypes.c_int), ("direction", ctypes.c_int), ("rho_floor", dbl)]
@@ -166,6 +175,7 @@ SYMBOLS = {
     "dotsocp_recover_outputs": (ctypes.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "dotsocp_report_edges": (ctypes.c_int, [vp]),
     "dotsocp_solution_report": (ctypes.c_int, [vp, vp, vp, ctypes.POINTER(Report), vp, vp]),
+    "dotsocp_geodesic_profile": (ctypes.c_int, [vp, vp, vp, ctypes.POINTER(Geodesic), vp, vp, vp]),
     "dotsocp_recover_velocity": (ctypes.c_int, [vp, vp, vp, dbl, vp, vp]),
     "dotsocp_advect_particles": (ctypes.c_int, [vp, vp, vp, ctypes.POINTER(AdvectOpts), vp, vp, vp, vp, ctypes.POINTER(i64)]),
     "dotsocp_push_mass": (ctypes.c_int, [vp, vp, vp, ctypes.POINTER(PushOpts), vp, vp, vp, vp, vp, ctypes.POINTER(i64),

@@ -392,6 +392,12 @@ int dotsocp_solution_report(dotsocp_ctx *ctx, const double *rho0, const double *
     return ctx->s.solution_report(rho0, rho1, rep, layer_mass, layer_neg);
 }
 
+int dotsocp_geodesic_profile(dotsocp_ctx *ctx, const double *rho0, const double *rho1, dotsocp_geodesic *res, double *sums,
+                             double *rho_max, dotsocp_i64 *n_support) {
+    CTX_OR_FAIL();
+    return ctx->s.geodesic_profile(rho0, rho1, res, sums, rho_max, n_support);
+}
+
 int dotsocp_recover_velocity(dotsocp_ctx *ctx, const double *rho0, const double *rho1, double rho_floor, double *vx, double *vy) {
     CTX_OR_FAIL();
     if (ctx->s.prob.dim == 1)     // 1-D problems live in the y slot of the engine (ny = nx1d, nx = 1)

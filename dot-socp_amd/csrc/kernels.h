@@ -224,6 +224,17 @@ int launch_report(const Grid &g, const double *q, const double *alpha, const dou
                   const double *rho1, const double *a_prev, double sig, double cD, double dD, bool dim1, const double *edges,
                   double *partials, double *sums, unsigned long long *counts, hipStream_t st);
 
+// ---------------- geodesic.hip: the geodesic's profile (layer sums of moments, momentum, energy, entropy) in one pass over alpha ----------------
+// doubles / 64-bit counts of a slab's buffers: [partials ntl x DOTSOCP_GEO_SUMS x tiles | maxima ntl x tiles | sums ntl x
+// DOTSOCP_GEO_SUMS | max ntl] and [counts ntl x tiles | count ntl]; every slot is written by every launch
+i64 geodesic_doubles(const Grid &g);
+i64 geodesic_counts(const Grid &g);
+// one slab: sums (layer tl, quantity i at sums[tl * DOTSOCP_GEO_SUMS + i]) <- the layer sums added in the report's order, max[tl]
+// <- the largest finite rho (-Inf: none), count[tl] <- nodes with rho > DOTSOCP_REPORT_RHO_FLOOR; they stand at
+// buf + (DOTSOCP_GEO_SUMS + 1) * ntl * tiles (sums, then max) and cnt + ntl * tiles.  rho0 / rho1 / a_prev as for launch_outputs.
+int launch_geodesic(const Grid &g, const double *alpha, const double *weight, const double *rho0, const double *rho1,
+                    const double *a_prev, double sig, double cD, bool dim1, double *buf, unsigned long long *cnt, hipStream_t st);
+
 // ---------------- hopflax.hip: Hopf-Lax transform of a node layer, sums of the dual bound (dotsocp_dual_bound) ----------------
 #define HL_MAX_LEN (1 << 20)        // nodes of a line (the limit of the DCT)
 #define HL_YOUT 1024                // outputs of a workgroup of the y pass: one line, 256 threads with 4 outputs each

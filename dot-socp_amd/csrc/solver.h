@@ -147,6 +147,9 @@ struct Slab {
     // [ntl][3], the 64-bit counters [RC_COUNT]
     double *rep_edges = nullptr, *rep_part = nullptr, *rep_sums = nullptr;
     unsigned long long *rep_counts = nullptr;
+    // the geodesic's profile (geodesic.hip; allocated at its first use): geodesic_doubles / geodesic_counts of the slab
+    double *geo_buf = nullptr;
+    unsigned long long *geo_cnt = nullptr;
     // particle transport (advect.hip; allocated at its first use): a ring of two velocity layers, slot (global node & 1) at
     // adv_vel + 2 * plane * slot = [vX | vY]; adv_have: the global node each slot holds (-1: none)
     double *adv_vel = nullptr;
@@ -294,6 +297,9 @@ struct Solver {
     // mass / negativity / f(q) histograms / cost of the finished solve in one pass over alpha and q (report.hip);
     // layer_mass, layer_neg: nt doubles each or NULL
     int solution_report(const double *rho0, const double *rho1, dotsocp_report *rep, double *layer_mass, double *layer_neg);
+    // the profile of the finished solve per time node in one pass over alpha (geodesic.hip, geodesic_summary.h); sums
+    // (nt x DOTSOCP_GEO_SUMS), rho_max, n_support (nt each): host, each may be NULL
+    int geodesic_profile(const double *rho0, const double *rho1, dotsocp_geodesic *res, double *sums, double *rho_max, i64 *n_support);
     // frames (and arrows) of the density evolution (render.hip).  Engine coordinates: mvX is the component along the second
     // array index, mvY along the first; a 1-D problem lives in Y (capi.hip hands its mvx over as mvY, its skip_x as skip_y)
     int render_evolution(const double *rho0, const double *rho1, const dotsocp_render_opts *o, const i64 *frame_nodes,

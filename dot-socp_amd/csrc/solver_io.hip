@@ -8,6 +8,7 @@
 #include <cmath>
 #include <cstring>
 
+#include "geodesic_summary.h"
 #include "solver.h"
 
 namespace dotsocp {
@@ -147,6 +148,53 @@ int Solver::solution_report(const double *rho0, const double *rho1, dotsocp_repo
     }
     rep->rho_min = report_key_decode(kmin, true, INFINITY);
     rep->fq_max = report_key_decode(kmax, false, -INFINITY);
+    return 0;
+}
+
+// What separates a geodesic from a curve that joins rho0 to rho1, per time node (include/dotsocp.h:
+// dotsocp_geodesic_profile): one launch_geodesic per slab over the device-resident alpha, staged like solution_report;
+// DOTSOCP_GEO_SUMS sums, one maximum and one count per layer come back, are put in layer order and summarised on the host
+// (geodesic_summary.h).  Every output is written behind the last step that can fail.
+int Solver::geodesic_profile(const double *rho0, const double *rho1, dotsocp_geodesic *res, double *sums, double *rho_max, i64 *n_support) {
+    DS_ARG(rho0 != nullptr && rho1 != nullptr && res != nullptr, "geodesic_profile() needs rho0, rho1 and res (one of them is NULL)");
+    DS_ARG(!remote(), "geodesic_profile() serves the slabs of one process; contexts with an RCCL communicator are not profiled");
+    if (!finished) { set_error("geodesic_profile() needs finish()"); return DOTSOCP_ESTATE; }
+    DS_CHECK(need_beta_form("geodesic_profile"));
+    cur_dev = -1;
+    DS_CHECK(use_dev(device));
+    const i64 plane = slabs[0].g.plane;
+    const double cD = cScale * D;                          // recoverOrgVar (solver_dotsocp2d.m:368-386)
+    DS_CHECK(stage_left_tail());
+    // host side of the copies: lives until the sync_all() below; per layer [sums | max] and the count
+    const int R = DOTSOCP_GEO_SUMS;
+    std::vector<double> rows((size_t)((R + 1) * nt));
+    std::vector<unsigned long long> counts((size_t)nt);
+    double *h_max = rows.data() + R * nt;
+    FOR_SLABS(s) {
+        const Grid &g = s.g;
+        if (!s.geo_buf) {
+            DS_CHECK(s.alloc(&s.geo_buf, geodesic_doubles(g)));
+            DS_CHECK(s.alloc(&s.geo_cnt, geodesic_counts(g)));
+        }
+        DS_CHECK(stage_rho_ends(s, rho0, rho1));
+        DS_CHECK(launch_geodesic(g, s.alpha, s.weight, s.w1, s.w1 + plane, s.a0_prev, sigma, cD, prob.dim == 1, s.geo_buf, s.geo_cnt, s.st));
+        const i64 tiles = report_tiles(g);
+        const double *d_sums = s.geo_buf + (R + 1) * g.ntl * tiles;
+        DS_HIP(ds_memcpy_async(rows.data() + R * g.t0, d_sums, sizeof(double) * R * g.ntl, hipMemcpyDeviceToHost, s.st));
+        DS_HIP(ds_memcpy_async(h_max + g.t0, d_sums + R * g.ntl, sizeof(double) * g.ntl, hipMemcpyDeviceToHost, s.st));
+        DS_HIP(ds_memcpy_async(counts.data() + g.t0, s.geo_cnt + g.ntl * tiles, sizeof(unsigned long long) * g.ntl, hipMemcpyDeviceToHost,
+                               s.st));
+    }
+    DS_CHECK(sync_all());
+    DS_CHECK(canary_after());                   // the kernels wrote inside their buffers
+    std::vector<double> by_quantity((size_t)(R * nt));     // the public layout: quantity q of layer t at [t + nt * q]
+    for (i64 t = 0; t < nt; ++t)
+        for (int q = 0; q < R; ++q) by_quantity[(size_t)(t + nt * q)] = rows[(size_t)(R * t + q)];
+    geodesic_summarize(nt, ny * nx, by_quantity.data(), h_max, res);
+    if (sums) memcpy(sums, by_quantity.data(), sizeof(double) * by_quantity.size());
+    if (rho_max) memcpy(rho_max, h_max, sizeof(double) * (size_t)nt);
+    if (n_support)
+        for (i64 t = 0; t < nt; ++t) n_support[t] = (i64)counts[(size_t)t];
     return 0;
 }
 

@@ -222,6 +222,22 @@ class InPALMContext:
                                                       capi.fptr(mass), capi.fptr(neg)))
         return from_struct(rep, mass, neg)
 
+    def geodesic(self):
+        """The geodesic's profile on the device (dotsocp_geodesic_profile; geodesic.py): per time node the mass, the moments,
+        the momentum, the kinetic energy, the entropy, the largest density and the support of the finished solve, and what
+        they say about it as a geodesic (constant speed, straight centre line, convex entropy, bounded peak), from one pass
+        over the device-resident alpha -- no output array is made or downloaded.  Call after finish(); the numbers of
+        geodesic.geodesic_profile(self.outputs()), the sums to rounding."""
+        from .geodesic import from_struct
+        m = self.model
+        nt = int(m.nt)
+        r0, r1 = self._rho_ends()
+        res, sums = capi.Geodesic(), np.empty((nt, capi.GEO_SUMS), order="F")
+        rho_max, n_support = np.empty(nt), np.empty(nt, dtype=np.int64)
+        capi.check(capi.lib().dotsocp_geodesic_profile(self._ctx, capi.fptr(r0), capi.fptr(r1), ctypes.byref(res), capi.fptr(sums),
+                                                       capi.fptr(rho_max), n_support.ctypes.data))
+        return from_struct(res, sums, rho_max, n_support, r0.size)
+
     def dual_bound(self, arrays=False):
         """A lower bound on W2^2 between the node histograms of rho0 and rho1, on the device (dotsocp_dual_bound; dual.py):
         the Hopf-Lax transform of phi(t = 0) forward to t = 1 and of phi(t = 1) back to t = 0, and the Kantorovich dual of
@@ -537,7 +553,8 @@ def _weights_mode(weight, weights, transfer, weighted=True):
 
 
 def _solve_levels(rho0, rho1, nt, levelN, opts, method, dim, weighted, device, barrier=None, transfer="device",
-                  weights=None, report=False, advect=None, push=None, map_report=None, render=None, dual=False, upper=None, plan_map=None):
+                  weights=None, report=False, advect=None, push=None, map_report=None, render=None, dual=False, upper=None, plan_map=None,
+                  geodesic=False):
     """The level loop of solver_dotsocp2d.m:154-250 (dot1d / wdot2d twins): restrict the data to
     levelN grids, solve coarse to fine with warm starts; every solve runs on the device.
     transfer = "device": the state never leaves the GPU -- jump_nextLevel and the output recovery run there
@@ -551,6 +568,8 @@ def _solve_levels(rho0, rho1, nt, levelN, opts, method, dim, weighted, device, b
     expanded on the host).
     report = True: the last level's context is asked for its solution report (InPALMContext.report(), report.py) before it
     is closed; output["report"] holds it.  Needs transfer="device".
+    geodesic = True: the last level's context is asked for the geodesic's profile (InPALMContext.geodesic(), geodesic.py) in
+    the same way; output["geodesic"] holds it.  Needs transfer="device".
     advect = dict(x=..., y=..., nsub=..., direction=..., rho_floor=..., trajectories=...): the keyword arguments of
     InPALMContext.advect(), which is asked of the last level's context in the same way; output["advect"] holds its
     result.  Needs transfer="device".
@@ -577,6 +596,8 @@ def _solve_levels(rho0, rho1, nt, levelN, opts, method, dim, weighted, device, b
         raise ValueError("transfer must be 'device' or 'host'")
     if report and transfer != "device":
         raise ValueError("report=True needs transfer='device' (the report is taken from the device-resident state)")
+    if geodesic and transfer != "device":
+        raise ValueError("geodesic=True needs transfer='device' (the profile is taken from the device-resident state)")
     if advect is not None and transfer != "device":
         raise ValueError("advect= needs transfer='device' (the particles move through the device-resident state)")
     if push is not None and transfer != "device":
@@ -671,6 +692,8 @@ def _solve_levels(rho0, rho1, nt, levelN, opts, method, dim, weighted, device, b
                 output = ctx.outputs()
                 if report:
                     output["report"] = ctx.report()
+                if geodesic:
+                    output["geodesic"] = ctx.geodesic()
                 if dual:
                     output["dual"] = ctx.dual_bound()
                 if upper is not None:
@@ -722,7 +745,8 @@ def _solve_levels(rho0, rho1, nt, levelN, opts, method, dim, weighted, device, b
 
 
 def solver_dotsocp2d(rho0, rho1, nt, levelN, opts, method="inPALM", device=0, transfer="device", report=False,
-                     advect=None, push=None, map_report=None, render=None, dual=False, upper=None, plan_map=None):
+                     advect=None, push=None, map_report=None, render=None, dual=False, upper=None, plan_map=None,
+                     geodesic=False):
     """[output, timeML, runHistML, runHist] = solver_dotsocp2d(rho0, rho1, nt, levelN, opts, method)
     socp/dot2d/solver_dotsocp2d.m:1.  report=True: output["report"] = the device-side solution report; advect=dict(x=..., y=...,
     ...): output["advect"] = the particles carried along the solved flow; push=dict(stride=..., frames=..., ...):
@@ -730,35 +754,38 @@ def solver_dotsocp2d(rho0, rho1, nt, levelN, opts, method="inPALM", device=0, tr
     output["map_report"] = cost, straightness and steadiness of the map the flow realises; render=dict(num_frame=..., mode=...,
     arrows=..., ...): output["render"] = uint8 pictures of the density evolution and the arrows of the flux; dual=True:
     output["dual"] = the dual lower bound on W2^2 from the potential; upper=dict(eps_h2=..., max_sweeps=..., defect_tol=...):
-    output["upper"] = the upper bound on it from Sinkhorn sweeps rounded to a plan (all seven: _solve_levels)."""
+    output["upper"] = the upper bound on it from Sinkhorn sweeps rounded to a plan; geodesic=True: output["geodesic"] = the
+    profile of the solution per time node (energy, moments, entropy; geodesic.py) (all of them: _solve_levels)."""
     output, timeML, runHistML, runHist = _solve_levels(rho0, rho1, nt, levelN, opts, method, 2, False, device,
                                                        transfer=transfer, report=report, advect=advect, push=push, map_report=map_report,
-                                                       render=render, dual=dual, upper=upper, plan_map=plan_map)
+                                                       render=render, dual=dual, upper=upper, plan_map=plan_map, geodesic=geodesic)
     if not check_massConservation(output["rho"], 1e-2):
         print("Warning: The mass conservation constraint violation exceeds 0.01")
     return output, timeML, runHistML, runHist
 
 
 def solver_dotsocp1d(rho0, rho1, nt, levelN, opts, method="inPALM", device=0, transfer="device", report=False,
-                     advect=None, push=None, map_report=None, render=None, dual=False, upper=None, plan_map=None):
-    """socp/dot1d/solver_dotsocp1d.m:1.  report, advect, push, map_report, render, dual, upper: as for solver_dotsocp2d."""
+                     advect=None, push=None, map_report=None, render=None, dual=False, upper=None, plan_map=None,
+                     geodesic=False):
+    """socp/dot1d/solver_dotsocp1d.m:1.  report, advect, push, map_report, render, dual, upper, geodesic: as for solver_dotsocp2d."""
     output, timeML, runHistML, runHist = _solve_levels(rho0, rho1, nt, levelN, opts, method, 1, False, device,
                                                        transfer=transfer, report=report, advect=advect, push=push, map_report=map_report,
-                                                       render=render, dual=dual, upper=upper, plan_map=plan_map)
+                                                       render=render, dual=dual, upper=upper, plan_map=plan_map, geodesic=geodesic)
     if not check_massConservation(output["rho"], 1e-2):
         print("Warning: The mass conservation constraint violation exceeds 0.01")
     return output, timeML, runHistML, runHist
 
 
 def solver_wdotsocp2d(rho0, rho1, nt, levelN, opts, method="inPALM", barrier=None, device=0, transfer="device",
-                      weights=None, report=False, advect=None, push=None, map_report=None, render=None, dual=False, upper=None, plan_map=None):
+                      weights=None, report=False, advect=None, push=None, map_report=None, render=None, dual=False, upper=None, plan_map=None,
+                      geodesic=False):
     """socp/wdot2d/solver_wdotsocp2d.m:1.  opts["weight"]: the Nq array, or a SpaceWeight (examples.py); weights:
-    where the levels' weights are made, "host" or "device" (_solve_levels); report, advect, push, map_report, render: as for
+    where the levels' weights are made, "host" or "device" (_solve_levels); report, geodesic, advect, push, map_report, render: as for
     solver_dotsocp2d (render: `barrier` is the default mask of the pictures; dual=True and upper= raise the library's refusal:
     the weighted cost is not the Euclidean one)."""
     output, timeML, runHistML, runHist = _solve_levels(rho0, rho1, nt, levelN, opts, method, 2, True, device,
                                                        barrier=barrier, transfer=transfer, weights=weights, report=report,
-                                                       advect=advect, push=push, map_report=map_report, render=render, dual=dual, upper=upper, plan_map=plan_map)
+                                                       advect=advect, push=push, map_report=map_report, render=render, dual=dual, upper=upper, plan_map=plan_map, geodesic=geodesic)
     if not check_massConservation(output["rho"], 1e-2):
         print("Warning: The tolerance of mass conservation constraint is under 0.01")
     return output, timeML, runHistML, runHist

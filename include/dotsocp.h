@@ -362,6 +362,41 @@ int dotsocp_report_edges(double edges[DOTSOCP_REPORT_BINS + 1]);
 int dotsocp_solution_report(dotsocp_ctx *ctx, const double *rho0, const double *rho1, dotsocp_report *rep,
                             double *layer_mass /* nt or NULL */, double *layer_neg /* nt or NULL */);
 
+/* The geodesic's profile: what separates a geodesic from a curve that merely joins rho0 to rho1, per time node, in ONE pass
+ * over the device-resident alpha (and the weight; q is not read); nothing grid-sized is written or crosses PCIe.
+ * rho, Ex, Ey at a node are the values dotsocp_recover_outputs writes, bit for bit.  Coordinates: X = (double)i / (double)(nx - 1)
+ * along the SECOND array index, Y = (double)j / (double)(ny - 1) along the first; 1-D: X along the only axis, every Y / Ey
+ * term is 0.  Eleven sums per node layer t over its nodes, each term formed in IEEE doubles without contraction:
+ *   0 mass  rho               3 mxx  (rho*X)*X        6 px   Ex          9 ent  rho > 0 ? rho*log(rho) : 0
+ *   1 mx    rho*X             4 myy  (rho*Y)*Y        7 py   Ey         10 sq   rho*rho
+ *   2 my    rho*Y             5 mxy  (rho*X)*Y        8 kin  rho > DOTSOCP_REPORT_RHO_FLOOR ? (Ex*Ex + Ey*Ey)/rho : 0
+ * added in the order of dotsocp_solution_report's layer sums (it depends on (ny, nx) alone: two calls, any slab split and
+ * any row pitch give the same bits; sums of row 0 are the sums behind its layer_mass, those of row 8 the ones behind its cost).
+ * rho_max[t]: the largest finite rho of the layer (-Inf if there is none; a -0.0 counts as +0.0); n_support[t]: nodes with
+ * rho > DOTSOCP_REPORT_RHO_FLOOR.
+ * The summary (csrc/geodesic_summary.h states every operation and the NaN rule), with a[t] = (layer sum a)[t] / (double)(ny*nx):
+ *   cost             (kin sums added in layer order) / (double)n_nodes: the bits of dotsocp_solution_report's cost
+ *   energy_min, energy_max   over kin[t];  speed_spread = cost > 0 ? (energy_max - energy_min) / cost : 0
+ *   com_defect       max_t |c[t] - ((1 - s) c[0] + s c[nt-1])|, c = (mx / mass, my / mass), s = (double)t / (double)(nt - 1)
+ *   momentum_defect  max_t |(px[t], py[t]) - ((mx, my)[nt-1] - (mx, my)[0])|        (d/dt of the first moment is the momentum)
+ *   entropy_defect   max(0, max over inner t of -((ent[t-1] + ent[t+1]) - 2 ent[t]))  (0: the entropy is convex in t)
+ *   peak_excess      max(0, max_t rho_max[t] - max(rho_max[0], rho_max[nt-1]))
+ *   nonfinite        layers whose mass is not finite */
+#define DOTSOCP_GEO_SUMS 11
+typedef struct {
+    dotsocp_i64 nt, n_nodes;
+    double cost, energy_min, energy_max, speed_spread, com_defect, momentum_defect, entropy_defect, peak_excess;
+    dotsocp_i64 nonfinite;
+} dotsocp_geodesic;
+/* Call after finish() (DOTSOCP_ESTATE before it); inPALM / ALG2, PALM and acc-ADMM contexts, weighted and 1-D ones; one
+ * slab, `nslabs` slabs and dotsocp_create_multi (per-slab layer rows are combined on the host in layer order).  rho0, rho1
+ * as for dotsocp_solution_report.  sums: the layer sums as the kernel adds them (not divided by ny*nx).  DOTSOCP_EINVAL for
+ * a NULL rho0, rho1 or res, and for a context with an RCCL communicator attached; a refused call leaves every output
+ * untouched. */
+int dotsocp_geodesic_profile(dotsocp_ctx *ctx, const double *rho0, const double *rho1, dotsocp_geodesic *res,
+                             double *sums      /* nt x DOTSOCP_GEO_SUMS, quantity q of layer t at sums[t + nt*q], or NULL */,
+                             double *rho_max   /* nt or NULL */, dotsocp_i64 *n_support /* nt or NULL */);
+
 /* Where the mass goes: the velocity v = E / rho of the solved flow (the arrows of utils/show_movement_2d.m:31-40, masked
  * where rho is small) and particles carried along it -- the transport (Monge) map -- from the device-resident alpha.
  *
